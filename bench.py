@@ -29,6 +29,16 @@ and disagreements travel over the control-plane group: `parity`, `status_ok` / `
 
 `--dry` rehearses the rank plumbing without a GPU (tests/test_bench_ranks_cpu.py: gloo, world size 2): the launch is replaced
 by a no-op and no device is touched; the JSON line then carries "dry": true and no measurement.
+
+A plain run does only what the headline figure needs: set up, warm up, time the `--steps` steps, write the outputs (`--dump-outputs`)
+and print the line (metric, value, unit, ms_per_step, ...).  `roofline`, `cpu_baseline`, `parity`, `status_ok` / `status_total` and
+`sustained` described above are computed only under `--full`.
+
+`--dump-outputs DIR` writes what the last timed step handed back to its caller as DIR/<name>.npy (rank 0's shard): `delta`, `alpha`,
+`status` for a step; `variables`, `termination_state`, `num_iterations`, `iterations`, `lagrange_multipliers`, `status` for a Solve.
+Floating outputs keep the workload's dtype, integer ones are written as float64.  Above DUMP_BUDGET_BYTES the same fixed, seeded
+sample of problems is taken from every array; `sample_index.npy` names the problems written.  The inputs are generated from a fixed
+seed, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -45,6 +55,28 @@ FP32_MFMA_PEAK_TFLOPS = 157.3  # dense fp32 matrix peak (MI355X_MICROARCH.md); v
 FP64_PEAK_TFLOPS = 78.6  # datasheet fp64 matrix = vector rate; tools/microbench.hip measures 64 cycles per v_mfma_f64_16x16x4_f64
 CFG5_TOTAL = 1 << 20   # BASELINE.json configs[4]
 BASELINE_INDEX = {"cfg2": 1, "cfg3": 2, "cfg4": 3, "cfg5": 4}
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: array data written in all (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 20240601      # --dump-outputs: the problems written when the whole batch exceeds the budget
+
+
+def dump_outputs(path, arrays, batch):
+    """Write each [batch, ...] tensor of `arrays` as path/<name>.npy, plus sample_index.npy (the problems written, as float64).
+    Floating tensors keep their dtype, integer ones become float64 (exact).  When the whole batch exceeds DUMP_BUDGET_BYTES, every
+    array is cut to the same fixed, seeded sample of problems (sorted), so that runs with the same arguments write the same rows."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    row_bytes = 8 + sum(a.nbytes // batch for a in host.values())   # (8: the sample_index entry)
+    rows = min(batch, DUMP_BUDGET_BYTES // row_bytes)
+    idx = np.arange(batch)
+    if rows < batch:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(batch, rows, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a if rows == batch else a[idx])
 
 
 def kernel_source_digest() -> str:
@@ -187,7 +219,13 @@ def main():
     ap.add_argument("--sustain-seconds", type=float, default=2.0,
                     help="after the K timed steps: back-to-back launches for at least this long, reported as `sustained` (0 = skip)")
     ap.add_argument("--dry", action="store_true", help="rank plumbing only: no GPU, the launch is a no-op (CPU tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: oracle parity, status counts, sustained rate, roofline and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0; a seeded sample of problems above 60 MB)")
     args = ap.parse_args()
+    if args.dry and args.dump_outputs:
+        ap.error("--dump-outputs: a --dry run computes nothing")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a bare `python bench.py --gpus N`: become the launcher.  This parent never imports torch or touches a device; it starts one
@@ -328,65 +366,74 @@ def main():
             "timing_sync": tlabel,   # what carried the barrier + MAX / SUM between the ranks ("none" at N = 1)
         }
 
-    # ---- correctness figure of the timed launch, on every rank (the checker leg: the only place besides cpu_baseline where bench.py touches
-    # oracle/).  Sample: the whole shard at N = 1, a strided sample per rank at N > 1; reduced over the control-plane (gloo) group.
-    import numpy as np
-    ns = args.parity_sample if args.parity_sample > 0 else (batch if info.world_size == 1 else min(batch, 256))
-    ns = max(1, min(ns, batch))
-    idx = np.unique(np.linspace(0, batch - 1, ns).astype(np.int64))
-    tol = 1e-10 if T == 8 else 2e-3
-    local = {"max_err": 0.0, "p999": 0.0, "disagree": 0, "ok": batch, "checked": int(len(idx)), "error": None, "extra": {}}
-    if not args.dry and not args.no_cpu_baseline:
-        try:
-            from oracle import oracle as orc
-            tix = torch.as_tensor(idx, device=dev)
-            h = lambda t: t.index_select(0, tix).double().cpu().numpy()
-            pr = dict(J=h(prob.J), r=h(prob.r), lam=float(np.float32(prob.lam)) if T == 4 else prob.lam, A_eq=h(prob.A_eq), b_eq=h(prob.b_eq),
-                      cons_var=prob.cons_var.index_select(0, tix).cpu().numpy(), cons_a=h(prob.cons_a), cons_b=h(prob.cons_b))
-            if solve_mode:
-                rterm, rnit, rvars, _ = orc.batched_solve(n, k, m, **pr, **solve_kw)
-                gterm, gnit, gvars = term.index_select(0, tix).cpu().numpy(), nit.index_select(0, tix).cpu().numpy(), h(svars)
-                xerr = np.max(np.abs(gvars[:, :n] - rvars[:, :n]), axis=1) / np.maximum(1.0, np.max(np.abs(rvars[:, :n]), axis=1))
-                same = (gterm == rterm) & (gnit == rnit)
-                # fp64: termination state and iteration count of every checked problem as the oracle's; the optimum within 1e-6 (the reference's own
-                # bound on its Solve KATs, qp_test.cc:252-471).  fp32 (no reference counterpart): iteration count within 2, optimum within 2e-2.
-                if T == 4:
-                    same = (gterm == rterm) & (np.abs(gnit - rnit) <= 2)
-                xtol = 1e-6 if T == 8 else 2e-2
-                local.update(max_err=float(xerr.max()), p999=float(np.quantile(xerr, 0.999)), disagree=int((~same).sum() + (xerr[same] >= xtol).sum()))
-                local["extra"] = {"oracle_mean_iterations": float(rnit.mean()), "oracle_satisfied_frac": float((rterm == 0).mean())}
-                tol = xtol
-            else:
-                delta, alpha, st_t = res["out"]
-                ref, ref_alpha, ref_status, _ = orc.batched_newton_step(n, k, m, **pr, vars_=h(vars_), mu=h(mu))
-                got = delta.index_select(0, tix).double().cpu().numpy()
-                err = np.max(np.abs(got - ref), axis=1) / np.max(np.abs(ref), axis=1)
-                st_s = st_t.index_select(0, tix).cpu().numpy()
-                local.update(max_err=float(err.max()), p999=float(np.quantile(err, 0.999)), disagree=int((ref_status != st_s).sum()))
-        except Exception as exc:  # the oracle is only the checker; never let it hide the measurement
-            local["error"] = repr(exc)[:300]
-    if not args.dry:
-        st_all = status if solve_mode else res["out"][2]
-        local["ok"] = int((st_all == 0).sum().item())
-    red = sharding.reduce_scalars(info, maxima=[local["max_err"], local["p999"], 1.0 if local["error"] else 0.0],
-                                  sums=[local["disagree"], local["ok"], batch, local["checked"]])
-    parity = None
-    if not args.no_cpu_baseline or args.dry:
-        parity = {"sample": int(red["sums"][3]), "sample_per_rank": int(len(idx)), "ranks": info.world_size, "max_rel_inf": red["maxima"][0],
-                  "p999_rel_inf": red["maxima"][1], "tolerance": tol,
-                  ("solve_disagreements" if solve_mode else "status_disagreements"): int(red["sums"][0]),
-                  "passed": bool(red["maxima"][0] < tol and red["sums"][0] == 0 and red["maxima"][2] == 0.0), **local["extra"]}
+    if args.dump_outputs and info.rank == 0:
         if solve_mode:
-            parity["what"] = ("termination state and iteration count equal to the oracle's Solve on every checked problem, x within "
-                              f"{tol:g} rel-inf (max_rel_inf is the x error)")
-        if red["maxima"][2] != 0.0:
-            parity["error"] = local["error"] or "the checker failed on another rank"
-        if args.dry:
-            parity["dry"] = True
-            parity["passed"] = None   # nothing was launched, nothing was checked: only the reduction ran
-    if info.rank == 0:
-        out["parity"] = parity
-        out["status_ok"], out["status_total"] = int(red["sums"][1]), int(red["sums"][2])
+            outputs = {"variables": svars, "termination_state": term, "num_iterations": nit, "iterations": its, "lagrange_multipliers": lag,
+                       "status": status}
+        else:
+            outputs = dict(zip(("delta", "alpha", "status"), res["out"]))
+        dump_outputs(args.dump_outputs, {name: t for name, t in outputs.items() if t is not None}, batch)
+
+    import numpy as np
+    if args.full:
+        # ---- correctness figure of the timed launch, on every rank (the checker leg: the only place besides cpu_baseline where bench.py touches
+        # oracle/).  Sample: the whole shard at N = 1, a strided sample per rank at N > 1; reduced over the control-plane (gloo) group.
+        ns = args.parity_sample if args.parity_sample > 0 else (batch if info.world_size == 1 else min(batch, 256))
+        ns = max(1, min(ns, batch))
+        idx = np.unique(np.linspace(0, batch - 1, ns).astype(np.int64))
+        tol = 1e-10 if T == 8 else 2e-3
+        local = {"max_err": 0.0, "p999": 0.0, "disagree": 0, "ok": batch, "checked": int(len(idx)), "error": None, "extra": {}}
+        if not args.dry and not args.no_cpu_baseline:
+            try:
+                from oracle import oracle as orc
+                tix = torch.as_tensor(idx, device=dev)
+                h = lambda t: t.index_select(0, tix).double().cpu().numpy()
+                pr = dict(J=h(prob.J), r=h(prob.r), lam=float(np.float32(prob.lam)) if T == 4 else prob.lam, A_eq=h(prob.A_eq), b_eq=h(prob.b_eq),
+                          cons_var=prob.cons_var.index_select(0, tix).cpu().numpy(), cons_a=h(prob.cons_a), cons_b=h(prob.cons_b))
+                if solve_mode:
+                    rterm, rnit, rvars, _ = orc.batched_solve(n, k, m, **pr, **solve_kw)
+                    gterm, gnit, gvars = term.index_select(0, tix).cpu().numpy(), nit.index_select(0, tix).cpu().numpy(), h(svars)
+                    xerr = np.max(np.abs(gvars[:, :n] - rvars[:, :n]), axis=1) / np.maximum(1.0, np.max(np.abs(rvars[:, :n]), axis=1))
+                    same = (gterm == rterm) & (gnit == rnit)
+                    # fp64: termination state and iteration count of every checked problem as the oracle's; the optimum within 1e-6 (the reference's own
+                    # bound on its Solve KATs, qp_test.cc:252-471).  fp32 (no reference counterpart): iteration count within 2, optimum within 2e-2.
+                    if T == 4:
+                        same = (gterm == rterm) & (np.abs(gnit - rnit) <= 2)
+                    xtol = 1e-6 if T == 8 else 2e-2
+                    local.update(max_err=float(xerr.max()), p999=float(np.quantile(xerr, 0.999)), disagree=int((~same).sum() + (xerr[same] >= xtol).sum()))
+                    local["extra"] = {"oracle_mean_iterations": float(rnit.mean()), "oracle_satisfied_frac": float((rterm == 0).mean())}
+                    tol = xtol
+                else:
+                    delta, alpha, st_t = res["out"]
+                    ref, ref_alpha, ref_status, _ = orc.batched_newton_step(n, k, m, **pr, vars_=h(vars_), mu=h(mu))
+                    got = delta.index_select(0, tix).double().cpu().numpy()
+                    err = np.max(np.abs(got - ref), axis=1) / np.max(np.abs(ref), axis=1)
+                    st_s = st_t.index_select(0, tix).cpu().numpy()
+                    local.update(max_err=float(err.max()), p999=float(np.quantile(err, 0.999)), disagree=int((ref_status != st_s).sum()))
+            except Exception as exc:  # the oracle is only the checker; never let it hide the measurement
+                local["error"] = repr(exc)[:300]
+        if not args.dry:
+            st_all = status if solve_mode else res["out"][2]
+            local["ok"] = int((st_all == 0).sum().item())
+        red = sharding.reduce_scalars(info, maxima=[local["max_err"], local["p999"], 1.0 if local["error"] else 0.0],
+                                      sums=[local["disagree"], local["ok"], batch, local["checked"]])
+        parity = None
+        if not args.no_cpu_baseline or args.dry:
+            parity = {"sample": int(red["sums"][3]), "sample_per_rank": int(len(idx)), "ranks": info.world_size, "max_rel_inf": red["maxima"][0],
+                      "p999_rel_inf": red["maxima"][1], "tolerance": tol,
+                      ("solve_disagreements" if solve_mode else "status_disagreements"): int(red["sums"][0]),
+                      "passed": bool(red["maxima"][0] < tol and red["sums"][0] == 0 and red["maxima"][2] == 0.0), **local["extra"]}
+            if solve_mode:
+                parity["what"] = ("termination state and iteration count equal to the oracle's Solve on every checked problem, x within "
+                                  f"{tol:g} rel-inf (max_rel_inf is the x error)")
+            if red["maxima"][2] != 0.0:
+                parity["error"] = local["error"] or "the checker failed on another rank"
+            if args.dry:
+                parity["dry"] = True
+                parity["passed"] = None   # nothing was launched, nothing was checked: only the reduction ran
+        if info.rank == 0:
+            out["parity"] = parity
+            out["status_ok"], out["status_total"] = int(red["sums"][1]), int(red["sums"][2])
 
     if args.dry:
         if info.rank == 0:
@@ -403,7 +450,7 @@ def main():
     # The K timed steps above are the contract's figure; K x ~1.4 ms is a short region, so the same launch is also run back to back
     # for >= --sustain-seconds (clock ramp, thermal state and the ticket counter's behaviour over thousands of launches included).
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         chunk = max(1, int(0.25 / max(kernel_ms * 1e-3, 1e-6)))
         launches, ts = 0, time.perf_counter()
         while True:
@@ -416,7 +463,7 @@ def main():
                 break
         sustained = {"value": batch * launches / dt, "unit": unit, "seconds": dt, "launches": launches,
                      "ms_per_step": 1e3 * dt / launches, "scope": "rank 0" if info.world_size > 1 else "the GPU"}
-    if info.rank == 0:
+    if args.full and info.rank == 0:
         alg_bytes = synth.algorithmic_bytes(n, k, m, m_r, T)
         flops = synth.algorithmic_flops(n, k, m, m_r)
         out["sustained"] = sustained
@@ -512,6 +559,7 @@ def main():
             pass
         except Exception as exc:  # the oracle is only the checker; never let it hide the measurement
             out["cpu_baseline"] = {"error": repr(exc)}
+    if info.rank == 0:
         print(json.dumps(out), flush=True)
     if info.world_size > 1:
         dist.barrier()

@@ -79,7 +79,7 @@ def test_product_never_imports_oracle():
 
 def test_only_tests_smoke_and_the_cpu_baseline_leg_touch_the_oracle():
     """tools/ never imports the oracle; bench.py does so only BEHIND its timed region, as the checker of the launch just timed (every rank,
-    on a sample of its own shard) and as the timed CPU baseline (rank 0 at N = 1) -- both skipped by --no-cpu-baseline."""
+    on a sample of its own shard) and as the timed CPU baseline (rank 0 at N = 1) -- both only under --full, both skipped by --no-cpu-baseline."""
     import re
     for dirpath, _, files in os.walk(os.path.join(ROOT, "tools")):
         for f in files:
@@ -92,8 +92,10 @@ def test_only_tests_smoke_and_the_cpu_baseline_leg_touch_the_oracle():
     checker = bench.index("from oracle import oracle")
     baseline = bench.index("from oracle import oracle", checker + 1)
     assert timed_region_end < checker < baseline                       # never inside what is measured
+    assert timed_region_end < bench.index("    if args.full:\n") < checker       # and only in a --full run
     assert bench.index("if not args.dry and not args.no_cpu_baseline:") < checker
     assert checker < bench.index("if info.world_size > 1 or args.no_cpu_baseline:") < baseline
+    assert checker < bench.index("if args.full and info.rank == 0:") < baseline
 
 
 def test_ctypes_mirrors_match_the_header_layout(tmp_path):

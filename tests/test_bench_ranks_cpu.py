@@ -31,7 +31,7 @@ def _run(world, extra):
 
 
 def test_two_ranks_default_to_config5_sharded():
-    out = _run(2, [])
+    out = _run(2, ["--full"])
     assert out["dry"] is True and out["value"] is None
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1
     assert out["scaling"] == "strong" and out["config"]["name"] == "cfg5"
@@ -50,11 +50,56 @@ def test_two_ranks_default_to_config5_sharded():
 
 def test_two_ranks_solve_mode_schema():
     """`--mode solve`: one mo_qp_solve launch per step, unit solves/s, same line contract and the same all-rank parity block."""
-    out = _run(2, ["--mode", "solve", "--config", "cfg3", "--batch", "4096", "--parity-sample", "64"])
+    out = _run(2, ["--mode", "solve", "--config", "cfg3", "--batch", "4096", "--parity-sample", "64", "--full"])
     assert out["unit"] == "solves/s" and out["config"]["mode"] == "solve" and "mo_qp_solve" in out["config"]["workload"]
     assert out["config"]["batch_total"] == 8192 and out["units_per_step_all_ranks"] == 8192
     assert out["parity"]["sample"] == 128 and "solve_disagreements" in out["parity"]
     assert out["status_ok"] == out["status_total"] == 8192
+
+
+def test_plain_run_carries_the_headline_only():
+    """Without --full the line is the headline figure and its context: no parity reduction, no status counts (and on a real run no
+    roofline, cpu_baseline or sustained rate)."""
+    out = _run(2, [])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"} <= set(out)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["units_per_step_all_ranks"] == 2 ** 20
+    assert not {"parity", "status_ok", "status_total", "roofline", "cpu_baseline", "sustained"} & set(out)
+
+
+def test_dump_outputs_is_refused_on_a_dry_run():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry", "--dump-outputs", "unused"], cwd=ROOT,
+                         capture_output=True, text=True, timeout=120)
+    assert res.returncode != 0 and "--dump-outputs" in res.stderr
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    """bench.dump_outputs on host tensors: every array keeps its leading problem dimension, floats keep their dtype, integers become
+    float64, and above the budget the same seeded sample of problems is taken from every array, run after run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B, V = 70000, 136                                      # the cfg3 step's delta alone would be 76 MB in float64
+    delta = torch.arange(B * V, dtype=torch.float64).reshape(B, V)
+    alpha = torch.rand(B, 2, dtype=torch.float32)
+    status = torch.arange(B, dtype=torch.int32) % 5
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"delta": delta, "alpha": alpha, "status": status}, B)
+    files = {f: np.load(tmp_path / "a" / f) for f in ("sample_index.npy", "delta.npy", "alpha.npy", "status.npy")}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    idx = files["sample_index.npy"]
+    rows = len(idx)
+    assert 0 < rows < B and np.all(np.diff(idx) > 0) and idx.dtype == np.float64
+    i = idx.astype(np.int64)
+    assert files["delta.npy"].dtype == np.float64 and np.array_equal(files["delta.npy"], delta.numpy()[i])
+    assert files["alpha.npy"].dtype == np.float32 and np.array_equal(files["alpha.npy"], alpha.numpy()[i])
+    assert files["status.npy"].dtype == np.float64 and np.array_equal(files["status.npy"], (i % 5).astype(np.float64))
+    for f, a in files.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f), a)   # the same sample in a second run
+    small = {"delta": delta[:100], "status": status[:100]}      # within the budget: the whole batch, in order
+    bench.dump_outputs(str(tmp_path / "c"), small, 100)
+    assert np.array_equal(np.load(tmp_path / "c" / "sample_index.npy"), np.arange(100.0))
+    assert np.array_equal(np.load(tmp_path / "c" / "delta.npy"), delta[:100].numpy())
 
 
 def test_two_ranks_weak_scaling_config():

@@ -25,7 +25,7 @@ def test_two_ranks_on_one_gpu_run_config5_shards():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--config", "cfg5", "--batch", "16384"]
+           "--config", "cfg5", "--batch", "16384", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -53,7 +53,7 @@ def test_bare_gpus_flag_runs_two_real_ranks():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--config", "cfg5",
-           "--batch", "16384", "--no-cpu-baseline", "--sustain-seconds", "0.3"]
+           "--batch", "16384", "--no-cpu-baseline", "--sustain-seconds", "0.3", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -72,7 +72,7 @@ def test_two_ranks_on_one_gpu_fall_back_from_rccl_to_gloo():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "MO_BENCH_BACKEND"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "cfg5",
-           "--batch", "8192", "--no-cpu-baseline", "--sustain-seconds", "0"]
+           "--batch", "8192", "--no-cpu-baseline", "--sustain-seconds", "0", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -90,7 +90,7 @@ def test_solve_mode_two_ranks_and_single_rank():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--mode", "solve", "--steps", "3", "--warmup", "1", "--config", "cfg3",
-           "--batch", "8192", "--sustain-seconds", "0"]
+           "--batch", "8192", "--sustain-seconds", "0", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
@@ -100,10 +100,83 @@ def test_solve_mode_two_ranks_and_single_rank():
     assert out["roofline"]["bound"] == "mfma" and out["roofline"]["unit"] == "TFLOP/s" and 0 < out["roofline"]["frac"] < 1
     assert 6.0 < out["roofline"]["mean_iterations"] < 10.0
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "solve", "--steps", "3", "--warmup", "1", "--batch", "4096", "--sustain-seconds", "0",
-           "--cpu-seconds", "2"]
+           "--cpu-seconds", "2", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["parity"]["passed"] is True and out["parity"]["sample"] == 4096      # the whole batch at N = 1
     assert out["cpu_baseline"]["unit"] == "solves/s" and out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["one_core"]["cores"] == 1
     assert out["value"] > 20 * out["cpu_baseline"]["value"]
+
+
+def _plain_env():
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "MO_BENCH_BACKEND"):
+        env.pop(k, None)
+    return env
+
+
+def _line(res):
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), res.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --steps K --warmup W --dump-outputs DIR` at the default workload (cfg3, batch 65 536): K timed steps, the headline
+    line only, and the last step's delta / alpha / status -- a seeded sample of the batch, the whole of it exceeds the budget -- written
+    identically by two runs and equal to the oracle's step on the same problems, regenerated here from the same seed."""
+    import numpy as np
+    import torch
+
+    from mini_opt_amd import synth
+    from oracle import oracle as orc
+    runs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / d)]
+        runs.append(_line(subprocess.run(cmd, cwd=ROOT, env=_plain_env(), capture_output=True, text=True, timeout=600)))
+    out = runs[0]
+    assert out["steps"] == 7 and out["warmup"] == 2 and out["unit"] == "steps/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["metric"] == "batched dense KKT Newton steps/sec, n=64 fp64" and out["config"]["batch_per_gpu"] == 65536
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 65536) < 1e-3 * 65536
+    assert not {"parity", "status_ok", "roofline", "cpu_baseline", "sustained"} & set(out)
+    names = ("sample_index", "delta", "alpha", "status")
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f + ".npy" for f in names)
+    assert sum(os.path.getsize(tmp_path / "a" / (f + ".npy")) for f in names) <= 64 * 10 ** 6
+    a = {f: np.load(tmp_path / "a" / (f + ".npy")) for f in names}
+    b = {f: np.load(tmp_path / "b" / (f + ".npy")) for f in names}
+    idx = a["sample_index"].astype(np.int64)
+    V = 64 + 2 * 32 + 8
+    assert 0 < len(idx) < 65536 and np.all(np.diff(idx) > 0)
+    assert a["delta"].shape == (len(idx), V) and a["alpha"].shape == (len(idx), 2) and a["status"].shape == (len(idx),)
+    assert all(v.dtype == np.float64 for v in a.values()) and np.all(a["status"] == 0)
+    for f in names:
+        assert np.array_equal(a[f], b[f]), f
+    d = synth.CONFIGS["cfg3"]
+    dev = torch.device("cuda:0")
+    prob, vars_, mu = synth.make_batch_torch(d["n"], d["k"], d["m"], d["m_r"], 65536, dev, torch.float64, seed=synth.SEED)
+    pick = np.arange(0, len(idx), max(1, len(idx) // 64))
+    tix = torch.as_tensor(idx[pick], device=dev)
+    h = lambda t: t.index_select(0, tix).double().cpu().numpy()
+    ref, ref_alpha, ref_status, _ = orc.batched_newton_step(
+        d["n"], d["k"], d["m"], J=h(prob.J), r=h(prob.r), lam=prob.lam, A_eq=h(prob.A_eq), b_eq=h(prob.b_eq),
+        cons_var=prob.cons_var.index_select(0, tix).cpu().numpy(), cons_a=h(prob.cons_a), cons_b=h(prob.cons_b), vars_=h(vars_), mu=h(mu))
+    got = a["delta"][pick]
+    assert np.all(ref_status == 0)
+    assert (np.max(np.abs(got - ref), axis=1) / np.max(np.abs(ref), axis=1)).max() < 1e-10
+    assert np.max(np.abs(a["alpha"][pick] - ref_alpha)) < 1e-9
+
+
+def test_plain_solve_run_dumps_the_solver_outputs(tmp_path):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "solve", "--batch", "2048", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
+    out = _line(subprocess.run(cmd, cwd=ROOT, env=_plain_env(), capture_output=True, text=True, timeout=600))
+    assert out["steps"] == 2 and out["unit"] == "solves/s" and "parity" not in out
+    import numpy as np
+    f = {name[:-4]: np.load(tmp_path / name) for name in os.listdir(tmp_path)}
+    assert set(f) == {"sample_index", "variables", "termination_state", "num_iterations", "iterations", "lagrange_multipliers", "status"}
+    assert np.array_equal(f["sample_index"], np.arange(2048.0))
+    assert f["variables"].shape == (2048, 64 + 2 * 32 + 8) and f["iterations"].shape == (2048, 10, 14)
+    assert np.all(f["status"] == 0) and np.all((f["num_iterations"] >= 1) & (f["num_iterations"] <= 10))
+    assert np.all(np.isfinite(f["variables"]))

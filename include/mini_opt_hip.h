@@ -358,6 +358,45 @@ int mo_residual_eval(mo_plan* plan, int32_t family, int32_t rows, const void* pa
                      int64_t batch, void* r, int64_t r_stride, void* J, int64_t J_stride, int32_t J_ld, int32_t J_layout,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Residual-block input: the reference's own model of a cost (mini_opt::Problem::costs, nonlinear.hpp:33-52).  Each residual b is an
+ * R_b x P_b local Jacobian over an index list of P_b of the n variables (Residual::Model, residual.hpp:60-143).  A residual LAYOUT
+ * describes the block structure once and is shared by the whole batch, like Problem::costs.
+ * Packed values of one problem: block b's local Jacobian is R_b x P_b COLUMN-major (Eigen's JacobianType, what the functor fills) and
+ * starts at offset sum_{b' < b} R_b' P_b'; r is the stacked residual values in block order (the dense stack's r).  Strides in elements,
+ * stride 0 = one instance shared by the batch. */
+typedef struct mo_residual_layout mo_residual_layout;
+/* rows[b] = R_b >= 1, params[b] = P_b >= 1, index = the concatenated index lists (sum P_b entries), all HOST arrays.
+ * 0 <= index < plan n, else MO_ERR_DIMENSION (F_ASSERT_LT of GatherValues / UpdateHessian, residual.hpp:160-162, :209).
+ * Builds the gather schedule on the host and uploads it to the plan's device: all allocation happens here, none in a launch.
+ * The layout may be used with any plan of the same n on the same device. */
+int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int32_t* rows, const int32_t* params,
+                              const int32_t* index, mo_residual_layout** out);
+int mo_residual_layout_destroy(mo_residual_layout* layout);
+int64_t mo_residual_layout_values(const mo_residual_layout* layout);   /* sum R_b P_b: packed Jacobian length per problem (-1: NULL) */
+int32_t mo_residual_layout_rows(const mo_residual_layout* layout);     /* sum R_b (-1: NULL) */
+
+/* The cost half of LinearizeAndFillQP (nonlinear.cc:182-189) for block input: G_out (n x n col-major, lower written, strict upper written
+ * as 0) = sum_b UpdateHessian (residual.hpp:186-226, the reference's summation order) + lambda I after the sum (lambda[_vec] added iff
+ * > 0; lambda_vec NULL = the scalar), c_out = sum_b J_b^T r_b, half_sq_out[p] (may be NULL) = sum_b 0.5 |r_b|^2.  Requires sum R_b ==
+ * plan m_r.  Deterministic: every cell is summed by one lane in a fixed order. */
+int mo_linearize_blocks(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
+                        int64_t r_stride, double lambda, const void* lambda_vec, int64_t lambda_stride, int64_t batch, void* G_out,
+                        int64_t G_stride, int32_t G_ld, void* c_out, int64_t c_stride, void* half_sq_out, void* stream);
+/* UpdateJacobian stacked (nonlinear.cc:191-206, residual.hpp:230-250): J_out = the dense (sum R_b) x n matrix, zeros, then every block's
+ * columns ASSIGNED in local order (a duplicate index keeps the last column); J_out_layout MO_COL_MAJOR gives QP::A_eq.
+ * abs_sum_out[p] (may be NULL) = |r|_1, Errors::equality (nonlinear.cc:204). */
+int mo_jacobian_blocks(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
+                       int64_t r_stride, int64_t batch, void* J_out, int64_t J_out_stride, int32_t J_out_ld, int32_t J_out_layout,
+                       void* abs_sum_out, void* stream);
+/* mo_nls_solve with block input: eval(MO_NLS_EVAL_LINEARIZE) fills np->J / np->J_eq with PACKED block Jacobians of cost_layout /
+ * eq_layout (J_ld, J_layout and J_eq_ld are ignored; J_stride / J_eq_stride are per-problem strides of the packed values).  Every outer
+ * iteration forms G, c (with the problem's lambda) and A_eq with the two calls above into per-call scratch and hands the QP over as
+ * (G, c) input.  fp64 only; eq_layout is NULL iff k == 0; sum R_b of cost_layout == m_r and of eq_layout == k. */
+int mo_nls_solve_blocks(mo_plan* plan, const mo_nls_problem* np, const mo_residual_layout* cost_layout,
+                        const mo_residual_layout* eq_layout, int64_t batch, const mo_nls_params* params, mo_nls_eval_fn eval, void* user,
+                        int32_t* termination, int32_t* num_iterations, void* iterations, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

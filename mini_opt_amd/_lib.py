@@ -31,7 +31,9 @@ MO_KKT_RECORD, MO_IP_RECORD, MO_ITER_RECORD = 4, 6, 14
 EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default_solve_params", "mo_plan_create",
            "mo_plan_destroy", "mo_plan_step_kernel", "mo_plan_solve_kernel", "mo_plan_nls_uses_nullspace", "mo_linearize", "mo_kkt_residual", "mo_newton_step", "mo_iterate",
            "mo_qp_solve", "mo_fill_qp", "mo_nonlinear_errors", "mo_qp_cost_derivative",
-           "mo_default_nls_params", "mo_nls_solve", "mo_nullspace_solve", "mo_residual_eval", "mo_qp_eigenvalue_stats"]
+           "mo_default_nls_params", "mo_nls_solve", "mo_nullspace_solve", "mo_residual_eval", "mo_qp_eigenvalue_stats",
+           "mo_residual_layout_create", "mo_residual_layout_destroy", "mo_residual_layout_values", "mo_residual_layout_rows",
+           "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks"]
 
 
 class PlanDesc(C.Structure):
@@ -144,6 +146,16 @@ def lib() -> C.CDLL:
     L.mo_default_nls_params.argtypes = [C.POINTER(NlsParams)]
     L.mo_default_nls_params.restype = None
     L.mo_nls_solve.argtypes = [vp, C.POINTER(NlsProblem), i64, C.POINTER(NlsParams), NLS_EVAL_FN, vp, vp, vp, vp, vp, vp]
+    i32p = C.POINTER(C.c_int32)
+    L.mo_residual_layout_create.argtypes = [vp, i32, i32p, i32p, i32p, C.POINTER(vp)]
+    L.mo_residual_layout_destroy.argtypes = [vp]
+    L.mo_residual_layout_values.argtypes = [vp]
+    L.mo_residual_layout_values.restype = i64
+    L.mo_residual_layout_rows.argtypes = [vp]
+    L.mo_residual_layout_rows.restype = i32
+    L.mo_linearize_blocks.argtypes = [vp, vp, vp, i64, vp, i64, dbl, vp, i64, i64, vp, i64, i32, vp, i64, vp, vp]
+    L.mo_jacobian_blocks.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, i64, i32, i32, vp, vp]
+    L.mo_nls_solve_blocks.argtypes = [vp, C.POINTER(NlsProblem), vp, vp, i64, C.POINTER(NlsParams), NLS_EVAL_FN, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what the header declares
     _lib = L

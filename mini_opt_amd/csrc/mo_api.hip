@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <new>
+#include <vector>
 
 #include "mo_kernels.h"
 
@@ -47,6 +48,14 @@ struct mo_plan {
   long long H_work_slots;   // workgroup slots allocated: a launch's grid is clamped to it
   void* tile_scratch;  // fused Solve: per wave slot of the persistent grid, the G tiles a wave cannot park in LDS between passes
   unsigned long long* ticket;  // device work counter of the fused kernels (zeroed on the stream before each launch)
+};
+
+// Residual-block layout: the gather schedule of residual_blocks.hip, built once on the host and uploaded in one allocation.
+struct mo_residual_layout {
+  int device, n, num_blocks, rows;
+  long long values;
+  void* dev;
+  const int* g_ptr; const int4* g_ent; const int* c_ptr; const int4* c_ent; const int2* row_info; const int* win;
 };
 
 namespace {
@@ -648,8 +657,30 @@ static bool nls_takes_nullspace_path(const mo_plan* plan) {
 
 int mo_plan_nls_uses_nullspace(const mo_plan* plan) { return plan && nls_takes_nullspace_path(plan) ? 1 : 0; }
 
-int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const mo_nls_params* prm, mo_nls_eval_fn eval,
-                 void* user, int32_t* termination, int32_t* num_iterations, void* iterations, int32_t* status, void* stream) {
+}  // extern "C"
+
+namespace {
+mo::BlocksArgs blocks_args(const mo_residual_layout* l, long long batch) {
+  mo::BlocksArgs b;
+  memset(&b, 0, sizeof(b));
+  b.n = l->n; b.rows = l->rows; b.values = l->values; b.batch = batch;
+  b.g_ptr = l->g_ptr; b.g_ent = l->g_ent; b.c_ptr = l->c_ptr; b.c_ent = l->c_ent; b.row_info = l->row_info; b.win = l->win;
+  return b;
+}
+
+int check_layout(const mo_plan* plan, const mo_residual_layout* layout) {
+  if (!layout) return fail(MO_ERR_INVALID_ARGUMENT, "layout is NULL");
+  if (layout->n != plan->desc.n) return fail(MO_ERR_DIMENSION, "layout built for n = %d, plan n = %d", layout->n, plan->desc.n);
+  if (layout->device != plan->desc.device) return fail(MO_ERR_INVALID_ARGUMENT, "layout lives on device %d, plan on %d", layout->device, plan->desc.device);
+  return MO_OK;
+}
+
+// The SQP loop of mo_nls_solve and mo_nls_solve_blocks.  Without block input (dense stacks) it launches exactly the kernels of
+// mo_nls_solve; with block input every outer iteration first forms G, c and A_eq from the packed blocks into per-call scratch and the QP,
+// the eigenvalue statistics and the directional derivatives read that (G, c) input.
+int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const mo_residual_layout* cost_layout,
+                   const mo_residual_layout* eq_layout, int64_t batch, const mo_nls_params* prm, mo_nls_eval_fn eval, void* user, int32_t* termination, int32_t* num_iterations,
+                   void* iterations, int32_t* status, void* stream) {
   g_err[0] = 0;
   if (int rc = check_plan(plan)) return rc;
   const mo_plan_desc& d = plan->desc;
@@ -684,6 +715,16 @@ int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const m
   if (d.m > 0 && (!np->cons_var || !np->cons_a || !np->cons_b)) return fail(MO_ERR_INVALID_ARGUMENT, "m = %d but constraint arrays are NULL", d.m);
   if (prm->log_qp_eigenvalues && !np->qp_eigenvalues) return fail(MO_ERR_INVALID_ARGUMENT, "log_qp_eigenvalues needs the qp_eigenvalues buffer");
   if (!termination) return fail(MO_ERR_INVALID_ARGUMENT, "termination is NULL");
+  if (blocks) {
+    if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
+    if (int rc = check_layout(plan, cost_layout)) return rc;
+    if (cost_layout->rows != d.m_r) return fail(MO_ERR_DIMENSION, "cost layout has %d rows, plan m_r = %d", cost_layout->rows, d.m_r);
+    if ((eq_layout != nullptr) != (d.k > 0)) return fail(MO_ERR_DIMENSION, "eq_layout must be given iff k > 0 (k = %d)", d.k);
+    if (eq_layout) {
+      if (int rc = check_layout(plan, eq_layout)) return rc;
+      if (eq_layout->rows != d.k) return fail(MO_ERR_DIMENSION, "equality layout has %d rows, plan k = %d", eq_layout->rows, d.k);
+    }
+  }
   if (batch == 0) return MO_OK;
   MO_HIP_CHECK(hipSetDevice(d.device));
   hipStream_t s = (hipStream_t)stream;
@@ -703,6 +744,12 @@ int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const m
   for (int i = 0; i < 3; ++i) scratch.reserve<int>((size_t)batch);
   scratch.reserve<int>((size_t)batch * mo::NLS_SI);
   scratch.reserve<int>(2);
+  double *G_blk = nullptr, *c_blk = nullptr, *A_blk = nullptr;
+  if (blocks) {  // the QP of every outer iteration as (G, c, A_eq)
+    scratch.reserve<double>((size_t)batch * n * n);
+    scratch.reserve<double>((size_t)batch * n);
+    scratch.reserve<double>((size_t)batch * k * n);
+  }
   MO_HIP_CHECK(scratch.commit());
   MO_HIP_CHECK(scratch.alloc(&qp_vars, (size_t)batch * Vs));
   MO_HIP_CHECK(scratch.alloc(&cons_b, (size_t)batch * m));  // the QP's constraints: one stride for (variable, a, shifted b)
@@ -719,6 +766,11 @@ int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const m
   MO_HIP_CHECK(scratch.alloc(&qp_nit, (size_t)batch));
   MO_HIP_CHECK(scratch.alloc(&si, (size_t)batch * mo::NLS_SI));
   MO_HIP_CHECK(scratch.alloc(&counters, 2));
+  if (blocks) {
+    MO_HIP_CHECK(scratch.alloc(&G_blk, (size_t)batch * n * n));
+    MO_HIP_CHECK(scratch.alloc(&c_blk, (size_t)batch * n));
+    MO_HIP_CHECK(scratch.alloc(&A_blk, (size_t)batch * k * n));
+  }
 
   mo::NlsArgs na;
   memset(&na, 0, sizeof(na));
@@ -753,6 +805,23 @@ int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const m
   qp.A_eq = np->J_eq; qp.A_stride = np->J_eq_stride; qp.A_ld = np->J_eq_ld;
   qp.b_eq = np->r_eq; qp.b_stride = np->r_eq_stride;
   qp.cons_var = cons_var; qp.cons_a = cons_a; qp.cons_b = cons_b; qp.cons_stride = m;
+  mo::BlocksArgs cost_ba, eq_ba;
+  if (blocks) {  // QP-level input: lambda is already on G's diagonal
+    qp.J = nullptr; qp.r = nullptr; qp.lambda_vec = nullptr;
+    qp.G = G_blk; qp.G_stride = (int64_t)n * n; qp.G_ld = n;
+    qp.c = c_blk; qp.c_stride = n;
+    if (k > 0) { qp.A_eq = A_blk; qp.A_stride = (int64_t)k * n; qp.A_ld = k; }
+    cost_ba = blocks_args(cost_layout, batch);
+    cost_ba.J = np->J; cost_ba.J_stride = np->J_stride; cost_ba.r = np->r; cost_ba.r_stride = np->r_stride;
+    cost_ba.lambda_vec = sd + mo::NLS_SD_LAMBDA; cost_ba.lambda_vec_stride = mo::NLS_SD;
+    cost_ba.G_out = G_blk; cost_ba.G_out_stride = (long long)n * n; cost_ba.G_out_ld = n;
+    cost_ba.c_out = c_blk; cost_ba.c_out_stride = n;
+    if (k > 0) {
+      eq_ba = blocks_args(eq_layout, batch);
+      eq_ba.J = np->J_eq; eq_ba.J_stride = np->J_eq_stride; eq_ba.r = np->r_eq; eq_ba.r_stride = np->r_eq_stride;
+      eq_ba.J_out = A_blk; eq_ba.J_out_stride = (long long)k * n; eq_ba.J_out_ld = k; eq_ba.J_out_row_major = 0;
+    }
+  }
   mo_solve_params sp;
   mo_default_solve_params(&sp);       // ComputeStepDirection, nonlinear.cc:226-241
   sp.max_iterations = prm->max_qp_iterations;
@@ -776,12 +845,22 @@ int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const m
   da.A = np->J_eq; da.A_stride = np->J_eq_stride; da.A_ld = np->J_eq_ld; da.b = np->r_eq; da.b_stride = np->r_eq_stride;
   da.lambda_vec = sd + mo::NLS_SD_LAMBDA; da.lambda_vec_stride = mo::NLS_SD;
   da.out2 = deriv; da.quad_out = quad;
+  if (blocks) {  // c^T dx and dx^T G dx from the assembled (G, c)
+    da.J = nullptr; da.r = nullptr; da.lambda_vec = nullptr;
+    da.G = G_blk; da.G_stride = (long long)n * n; da.G_ld = n;
+    da.c = c_blk; da.c_stride = n;
+    da.A = A_blk; da.A_stride = (long long)k * n; da.A_ld = k;
+  }
 
   int host_counters[2];
   long long still_active = batch;  // problems the previous outer iteration left active (a hint for the QP kernel's ticket size)
   for (int iter = 0; iter < prm->max_iterations; ++iter) {
     na.iter = iter;
     if (eval(user, MO_NLS_EVAL_LINEARIZE, stream) != 0) return fail(MO_ERR_CALLBACK, "eval(LINEARIZE) failed at iteration %d", iter);
+    if (blocks) {  // LinearizeAndFillQP (nonlinear.cc:182-206) from the packed blocks
+      MO_HIP_CHECK(mo::launch_blocks_linearize(cost_ba, d.dtype, plan->num_cus, s));
+      if (k > 0) MO_HIP_CHECK(mo::launch_blocks_jacobian(eq_ba, d.dtype, plan->num_cus, s));
+    }
     // errors_pre (nonlinear.cc:184-186, 203) and the shifted constraints (:209-212)
     ea.r = np->r; ea.r_stride = np->r_stride; ea.b = np->r_eq; ea.b_stride = np->r_eq_stride; ea.out2 = errors_pre;
     MO_HIP_CHECK(mo::launch_nonlinear_errors(ea, d.dtype, s));
@@ -842,6 +921,173 @@ int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const m
     still_active = host_counters[1];
   }
   MO_HIP_CHECK(hipStreamSynchronize(s));  // the scratch is released on return
+  return MO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const mo_nls_params* prm, mo_nls_eval_fn eval,
+                 void* user, int32_t* termination, int32_t* num_iterations, void* iterations, int32_t* status, void* stream) {
+  return nls_solve_impl(plan, np, false, nullptr, nullptr, batch, prm, eval, user, termination, num_iterations, iterations, status, stream);
+}
+
+int mo_nls_solve_blocks(mo_plan* plan, const mo_nls_problem* np, const mo_residual_layout* cost_layout,
+                        const mo_residual_layout* eq_layout, int64_t batch, const mo_nls_params* params, mo_nls_eval_fn eval, void* user,
+                        int32_t* termination, int32_t* num_iterations, void* iterations, int32_t* status, void* stream) {
+  return nls_solve_impl(plan, np, true, cost_layout, eq_layout, batch, params, eval, user, termination, num_iterations, iterations, status,
+                        stream);
+}
+
+int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int32_t* rows, const int32_t* params,
+                              const int32_t* index, mo_residual_layout** out) {
+  g_err[0] = 0;
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  *out = nullptr;
+  if (int rc = check_plan(plan)) return rc;
+  if (!rows || !params || !index) return fail(MO_ERR_INVALID_ARGUMENT, "rows / params / index is NULL");
+  if (num_blocks <= 0) return fail(MO_ERR_INVALID_ARGUMENT, "num_blocks must be >= 1 (got %d)", num_blocks);
+  const int n = plan->desc.n;
+  long long values = 0, total_rows = 0, total_idx = 0, pairs = 0;
+  for (int b = 0; b < num_blocks; ++b) {
+    if (rows[b] <= 0 || params[b] <= 0) return fail(MO_ERR_INVALID_ARGUMENT, "block %d: R = %d, P = %d (both must be >= 1)", b, rows[b], params[b]);
+    values += (long long)rows[b] * params[b];
+    total_rows += rows[b];
+    total_idx += params[b];
+    pairs += (long long)params[b] * (params[b] + 1) / 2;
+  }
+  const long long lim = 0x7fffffffll;
+  if (values + total_rows > lim || total_rows * n > lim || pairs > lim || (long long)num_blocks * n > lim)
+    return fail(MO_ERR_UNSUPPORTED, "layout too large for 32-bit offsets (%lld values, %lld rows)", values, total_rows);
+  for (long long i = 0; i < total_idx; ++i)
+    if (index[i] < 0 || index[i] >= n) return fail(MO_ERR_DIMENSION, "index[%lld] = %d outside [0, %d)", i, index[i], n);
+
+  // contributions in the reference's order: blocks in order, then row_local, col_local <= row_local (residual.hpp:206-222)
+  const size_t nn = (size_t)n * n;
+  std::vector<int> g_ptr(nn + 1, 0), c_ptr((size_t)n + 1, 0);
+  auto cell_of = [n](int rg, int cg) { return cg <= rg ? (size_t)cg * n + rg : (size_t)rg * n + cg; };  // lower triangle, column-major
+  {
+    long long ib = 0;
+    for (int b = 0; b < num_blocks; ++b) {
+      const int32_t* idx = index + ib;
+      for (int a = 0; a < params[b]; ++a) {
+        for (int c = 0; c <= a; ++c) ++g_ptr[cell_of(idx[a], idx[c]) + 1];
+        ++c_ptr[(size_t)idx[a] + 1];
+      }
+      ib += params[b];
+    }
+  }
+  for (size_t i = 0; i < nn; ++i) g_ptr[i + 1] += g_ptr[i];
+  for (int i = 0; i < n; ++i) c_ptr[i + 1] += c_ptr[i];
+  std::vector<int4> g_ent((size_t)g_ptr[nn]), c_ent((size_t)c_ptr[n]);
+  std::vector<int> g_cur(g_ptr.begin(), g_ptr.end() - 1), c_cur(c_ptr.begin(), c_ptr.end() - 1);
+  std::vector<int2> row_info((size_t)total_rows);
+  std::vector<int> win((size_t)num_blocks * n, -1);
+  {
+    long long ib = 0, off = 0, roff = 0;
+    for (int b = 0; b < num_blocks; ++b) {
+      const int R = rows[b], P = params[b];
+      const int32_t* idx = index + ib;
+      for (int a = 0; a < P; ++a) {
+        for (int c = 0; c <= a; ++c) g_ent[g_cur[cell_of(idx[a], idx[c])]++] = make_int4((int)(off + (long long)a * R), (int)(off + (long long)c * R), R, 0);
+        c_ent[c_cur[idx[a]]++] = make_int4((int)(off + (long long)a * R), (int)roff, R, 0);
+        win[(size_t)b * n + idx[a]] = (int)(off + (long long)a * R);  // UpdateJacobian assigns: the last local column wins
+      }
+      for (int q = 0; q < R; ++q) row_info[(size_t)(roff + q)] = make_int2(b * n, q);
+      ib += P; off += (long long)R * P; roff += R;
+    }
+  }
+  // one device allocation: [g_ent | c_ent | g_ptr | c_ptr | row_info | win], 16-byte aligned pieces
+  auto pad = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
+  const size_t b_ge = pad(g_ent.size() * sizeof(int4)), b_ce = pad(c_ent.size() * sizeof(int4)), b_gp = pad(g_ptr.size() * sizeof(int)),
+               b_cp = pad(c_ptr.size() * sizeof(int)), b_ri = pad(row_info.size() * sizeof(int2)), b_w = pad(win.size() * sizeof(int));
+  mo_residual_layout* L = new (std::nothrow) mo_residual_layout();
+  if (!L) return fail(MO_ERR_HIP, "out of host memory");
+  L->device = plan->desc.device; L->n = n; L->num_blocks = num_blocks; L->rows = (int)total_rows; L->values = values;
+  L->dev = nullptr;
+  const size_t total = b_ge + b_ce + b_gp + b_cp + b_ri + b_w;
+  if (hipSetDevice(plan->desc.device) != hipSuccess || hipMalloc(&L->dev, total) != hipSuccess) {
+    (void)hipGetLastError();
+    delete L;
+    return fail(MO_ERR_HIP, "hipMalloc of the %zu B layout schedule failed", total);
+  }
+  char* base = (char*)L->dev;
+  struct Piece { const void* src; size_t bytes, padded; } pieces[] = {
+      {g_ent.data(), g_ent.size() * sizeof(int4), b_ge}, {c_ent.data(), c_ent.size() * sizeof(int4), b_ce},
+      {g_ptr.data(), g_ptr.size() * sizeof(int), b_gp},  {c_ptr.data(), c_ptr.size() * sizeof(int), b_cp},
+      {row_info.data(), row_info.size() * sizeof(int2), b_ri}, {win.data(), win.size() * sizeof(int), b_w}};
+  size_t at = 0;
+  const void* dst[6];
+  for (int i = 0; i < 6; ++i) {
+    dst[i] = base + at;
+    if (pieces[i].bytes && hipMemcpy(base + at, pieces[i].src, pieces[i].bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(L->dev);
+      delete L;
+      return fail(MO_ERR_HIP, "upload of the layout schedule failed");
+    }
+    at += pieces[i].padded;
+  }
+  L->g_ent = (const int4*)dst[0]; L->c_ent = (const int4*)dst[1]; L->g_ptr = (const int*)dst[2]; L->c_ptr = (const int*)dst[3];
+  L->row_info = (const int2*)dst[4]; L->win = (const int*)dst[5];
+  *out = L;
+  return MO_OK;
+}
+
+int mo_residual_layout_destroy(mo_residual_layout* layout) {
+  if (!layout) return MO_OK;
+  if (layout->dev) {
+    (void)hipSetDevice(layout->device);
+    (void)hipFree(layout->dev);
+  }
+  delete layout;
+  return MO_OK;
+}
+
+int64_t mo_residual_layout_values(const mo_residual_layout* layout) { return layout ? layout->values : -1; }
+int32_t mo_residual_layout_rows(const mo_residual_layout* layout) { return layout ? layout->rows : -1; }
+
+int mo_linearize_blocks(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
+                        int64_t r_stride, double lambda, const void* lambda_vec, int64_t lambda_stride, int64_t batch, void* G_out,
+                        int64_t G_stride, int32_t G_ld, void* c_out, int64_t c_stride, void* half_sq_out, void* stream) {
+  g_err[0] = 0;
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, layout)) return rc;
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (layout->rows != plan->desc.m_r) return fail(MO_ERR_DIMENSION, "layout has %d rows, plan m_r = %d", layout->rows, plan->desc.m_r);
+  if (!J_blocks || !r) return fail(MO_ERR_INVALID_ARGUMENT, "J_blocks / r is NULL");
+  if (!G_out || !c_out) return fail(MO_ERR_INVALID_ARGUMENT, "G_out / c_out is NULL");
+  if (G_ld < plan->desc.n) return fail(MO_ERR_DIMENSION, "G_ld %d < n", G_ld);
+  if (batch == 0) return MO_OK;
+  mo::BlocksArgs a = blocks_args(layout, batch);
+  a.J = J_blocks; a.J_stride = J_stride; a.r = r; a.r_stride = r_stride;
+  a.lambda = lambda; a.lambda_vec = lambda_vec; a.lambda_vec_stride = lambda_stride;
+  a.G_out = G_out; a.G_out_stride = G_stride; a.G_out_ld = G_ld;
+  a.c_out = c_out; a.c_out_stride = c_stride; a.half_sq_out = half_sq_out;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_blocks_linearize(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+int mo_jacobian_blocks(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
+                       int64_t r_stride, int64_t batch, void* J_out, int64_t J_out_stride, int32_t J_out_ld, int32_t J_out_layout,
+                       void* abs_sum_out, void* stream) {
+  g_err[0] = 0;
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, layout)) return rc;
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (!J_blocks || !J_out) return fail(MO_ERR_INVALID_ARGUMENT, "J_blocks / J_out is NULL");
+  if (abs_sum_out && !r) return fail(MO_ERR_INVALID_ARGUMENT, "abs_sum_out needs r");
+  if (J_out_layout != MO_ROW_MAJOR && J_out_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad J_out_layout");
+  const int min_ld = J_out_layout == MO_ROW_MAJOR ? plan->desc.n : layout->rows;
+  if (J_out_ld < min_ld) return fail(MO_ERR_DIMENSION, "J_out_ld %d < %d", J_out_ld, min_ld);
+  if (batch == 0) return MO_OK;
+  mo::BlocksArgs a = blocks_args(layout, batch);
+  a.J = J_blocks; a.J_stride = J_stride; a.r = r; a.r_stride = r_stride;
+  a.J_out = J_out; a.J_out_stride = J_out_stride; a.J_out_ld = J_out_ld; a.J_out_row_major = J_out_layout == MO_ROW_MAJOR;
+  a.abs_sum_out = abs_sum_out;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_blocks_jacobian(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
   return MO_OK;
 }
 

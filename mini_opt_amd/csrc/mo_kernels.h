@@ -167,4 +167,28 @@ hipError_t launch_nls_search_step(const NlsArgs& a, hipStream_t stream);
 hipError_t launch_nls_update(const NlsArgs& a, hipStream_t stream);
 hipError_t launch_nls_user_exit(const NlsArgs& a, hipStream_t stream);
 
+// residual-block input (mo_linearize_blocks / mo_jacobian_blocks), residual_blocks.hip.  The schedule is built on the host by
+// mo_residual_layout_create and shared by every problem of the batch; all offsets index one problem's packed values / residual rows.
+struct BlocksArgs {
+  int n, rows;                // plan n, sum R_b
+  long long values;           // sum R_b P_b: packed Jacobian length per problem
+  long long batch;
+  const int* g_ptr;           // [n * n + 1] CSR over the cells of G in column-major order (strict upper cells: empty lists)
+  const int4* g_ent;          // {offset of J col a, offset of J col b, R_b, 0}: G(i, j) += J_a . J_b, in the reference's order
+  const int* c_ptr;           // [n + 1]
+  const int4* c_ent;          // {offset of J col a, offset of block b's rows in r, R_b, 0}: c(i) += J_a . r_b
+  const int2* row_info;       // [rows] {b * n, row within block b}
+  const int* win;             // [num_blocks * n] offset of the column block b assigns to global column j (last wins), -1: none
+  const void* J; long long J_stride;
+  const void* r; long long r_stride;
+  double lambda; const void* lambda_vec; long long lambda_vec_stride;
+  void* G_out; long long G_out_stride; int G_out_ld;
+  void* c_out; long long c_out_stride;
+  void* half_sq_out;          // [batch] or NULL
+  void* J_out; long long J_out_stride; int J_out_ld; int J_out_row_major;
+  void* abs_sum_out;          // [batch] or NULL
+};
+hipError_t launch_blocks_linearize(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
+hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
+
 }  // namespace mo

@@ -1,0 +1,159 @@
+// residual_blocks.hip -- the cost and equality halves of LinearizeAndFillQP (nonlinear.cc:182-206) for residual-BLOCK input: every
+// residual is an R_b x P_b column-major local Jacobian over an index list of P_b of the n variables (Residual::Model, residual.hpp:60-143).
+//   blocks_linearize_kernel   sum_b UpdateHessian (residual.hpp:186-226) + lambda I: G (lower, strict upper 0), c, 0.5 |r|^2
+//   blocks_jacobian_kernel    UpdateJacobian stacked (residual.hpp:230-250): the dense (sum R_b) x n matrix, |r|_1
+// Gather formulation: mo_residual_layout_create lists, for every cell of G and every entry of c, its contributions
+// in the reference's order (blocks in order, then row_local / col_local).  A lane owns one cell at a time and sums its list in that order,
+// so there are no atomics, no G accumulator and the result is the same on every launch.  The schedule is shared by the batch: it stays in
+// L2 while the workgroups stream their problems' packed J and r (through LDS when they fit) and write whole lines of G.
+#include "mo_kernels.h"
+
+namespace mo {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr size_t kStageBudget = 48 * 1024;  // per workgroup: above it the packed values are read straight from global memory
+
+template <typename T> __device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// sum over the workgroup, valid in thread 0; `red` holds one value per wave
+template <typename T> __device__ __forceinline__ T block_sum(T v, T* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T s = 0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < kThreads / 64; ++w) s += red[w];
+  return s;
+}
+
+template <typename T, bool kStaged>
+__global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const BlocksArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ T red[kThreads / 64];
+  T* sJ = reinterpret_cast<T*>(smem);
+  T* sR = sJ + a.values;
+  const int tid = threadIdx.x;
+  const int n = a.n, nn = n * n;
+  for (long long p = blockIdx.x; p < a.batch; p += gridDim.x) {
+    const T* gJ = (const T*)a.J + p * a.J_stride;
+    const T* gR = (const T*)a.r + p * a.r_stride;
+    const T* Jv = gJ;
+    const T* rv = gR;
+    if (kStaged) {
+      for (long long i = tid; i < a.values; i += kThreads) sJ[i] = gJ[i];
+      for (int i = tid; i < a.rows; i += kThreads) sR[i] = gR[i];
+      __syncthreads();
+      Jv = sJ;
+      rv = sR;
+    }
+    const T lam = a.lambda_vec ? ((const T*)a.lambda_vec)[p * a.lambda_vec_stride] : (T)a.lambda;
+    T* G = (T*)a.G_out + p * a.G_out_stride;
+    // consecutive lanes own consecutive cells of G's column-major order: whole-line stores when G_ld == n
+    for (int cell = tid; cell < nn; cell += kThreads) {
+      const int col = cell / n, row = cell - col * n;
+      const int e1 = a.g_ptr[cell + 1];
+      T s = 0;
+      for (int e = a.g_ptr[cell]; e < e1; ++e) {
+        const int4 c = a.g_ent[e];
+        T d = 0;
+        for (int q = 0; q < c.z; ++q) d += Jv[c.x + q] * Jv[c.y + q];
+        s += d;
+      }
+      if (row == col && lam > (T)0) s += lam;  // nonlinear.cc:187-189, after the sum
+      G[(size_t)col * a.G_out_ld + row] = s;
+    }
+    T* cv = (T*)a.c_out + p * a.c_out_stride;
+    for (int i = tid; i < n; i += kThreads) {
+      const int e1 = a.c_ptr[i + 1];
+      T s = 0;
+      for (int e = a.c_ptr[i]; e < e1; ++e) {
+        const int4 c = a.c_ent[e];
+        T d = 0;
+        for (int q = 0; q < c.z; ++q) d += Jv[c.x + q] * rv[c.y + q];
+        s += d;
+      }
+      cv[i] = s;
+    }
+    if (a.half_sq_out) {
+      T sq = 0;
+      for (int i = tid; i < a.rows; i += kThreads) sq += rv[i] * rv[i];
+      sq = block_sum(sq, red);
+      if (tid == 0) ((T*)a.half_sq_out)[p] = (T)0.5 * sq;
+    }
+    __syncthreads();  // the next problem overwrites the staged values and the reduction slots
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void blocks_jacobian_kernel(const BlocksArgs a) {
+  __shared__ T red[kThreads / 64];
+  const int tid = threadIdx.x;
+  const int n = a.n, rows = a.rows, total = rows * n;
+  for (long long p = blockIdx.x; p < a.batch; p += gridDim.x) {
+    const T* J = (const T*)a.J + p * a.J_stride;
+    T* out = (T*)a.J_out + p * a.J_out_stride;
+    // consecutive lanes own consecutive elements of the output's own order (down a column, or along a row)
+    for (int e = tid; e < total; e += kThreads) {
+      int row, col;
+      if (a.J_out_row_major) { row = e / n; col = e - row * n; }
+      else { col = e / rows; row = e - col * rows; }
+      const int2 ri = a.row_info[row];
+      const int w = a.win[ri.x + col];
+      const T v = w >= 0 ? J[w + ri.y] : (T)0;
+      if (a.J_out_row_major) out[(size_t)row * a.J_out_ld + col] = v;
+      else out[(size_t)col * a.J_out_ld + row] = v;
+    }
+    if (a.abs_sum_out) {  // Errors::equality, nonlinear.cc:204
+      const T* r = (const T*)a.r + p * a.r_stride;
+      T s = 0;
+      for (int i = tid; i < rows; i += kThreads) s += fabs(r[i]);
+      s = block_sum(s, red);
+      if (tid == 0) ((T*)a.abs_sum_out)[p] = s;
+      __syncthreads();
+    }
+  }
+}
+
+// a workgroup per problem in turn: as many resident workgroups as the LDS allows, at most eight per CU (eight waves per SIMD)
+unsigned grid_for(long long batch, int num_cus, size_t lds_bytes) {
+  long long per_cu = 8;
+  if (lds_bytes > 0) {
+    const long long fit = (long long)((160 * 1024) / (lds_bytes + 64));
+    per_cu = fit < per_cu ? (fit < 1 ? 1 : fit) : per_cu;
+  }
+  long long g = (long long)num_cus * per_cu;
+  if (g > batch) g = batch;
+  return (unsigned)(g < 1 ? 1 : g);
+}
+
+template <typename T> hipError_t launch_linearize_t(const BlocksArgs& a, int num_cus, hipStream_t stream) {
+  const size_t stage = (size_t)(a.values + a.rows) * sizeof(T);
+  if (stage <= kStageBudget) {
+    hipLaunchKernelGGL((blocks_linearize_kernel<T, true>), dim3(grid_for(a.batch, num_cus, stage)), dim3(kThreads), stage, stream, a);
+  } else {
+    hipLaunchKernelGGL((blocks_linearize_kernel<T, false>), dim3(grid_for(a.batch, num_cus, 0)), dim3(kThreads), 0, stream, a);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_blocks_linearize(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream) {
+  if (a.batch <= 0) return hipSuccess;
+  return dtype == MO_F64 ? launch_linearize_t<double>(a, num_cus, stream) : launch_linearize_t<float>(a, num_cus, stream);
+}
+
+hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream) {
+  if (a.batch <= 0) return hipSuccess;
+  const dim3 g(grid_for(a.batch, num_cus, 0)), b(kThreads);
+  if (dtype == MO_F64) hipLaunchKernelGGL(blocks_jacobian_kernel<double>, g, b, 0, stream, a);
+  else hipLaunchKernelGGL(blocks_jacobian_kernel<float>, g, b, 0, stream, a);
+  return hipGetLastError();
+}
+
+}  // namespace mo

@@ -174,6 +174,8 @@ class Problem:
     equality: Optional[ResidualFn] = None
     equality_rows: int = 0                          # k
     inequality_constraints: Sequence[Tuple[int, float, float]] = field(default_factory=list)  # (variable, a, b): a x + b >= 0
+    cost_residuals: Optional[Sequence[Residual]] = None        # the Residual lists of FromResiduals (Problem::costs / equality_constraints):
+    equality_residuals: Optional[Sequence[Residual]] = None    # what ConstrainedNonlinearLeastSquares(residual_blocks=True) evaluates
 
     @staticmethod
     def FromResiduals(dimension: int, costs: Sequence[Residual], equality_constraints: Sequence[Residual] = (),
@@ -181,7 +183,8 @@ class Problem:
         """The reference's own shape: Problem{costs, inequality_constraints, equality_constraints, dimension} of Residuals."""
         k = sum(r.rows for r in equality_constraints)
         return Problem(dimension, stack_residuals(costs, dimension), sum(r.rows for r in costs),
-                       stack_residuals(equality_constraints, dimension) if k else None, k, list(inequality_constraints))
+                       stack_residuals(equality_constraints, dimension) if k else None, k, list(inequality_constraints),
+                       list(costs), list(equality_constraints))
 
 
 @dataclass
@@ -224,9 +227,11 @@ class _Plan:
 class ConstrainedNonlinearLeastSquares:
     """Batched mirror of mini_opt::ConstrainedNonlinearLeastSquares (nonlinear.hpp:127-230)."""
 
-    def __init__(self, problem: Problem, batch: int, device=None, dtype=torch.float64, retraction=None):
+    def __init__(self, problem: Problem, batch: int, device=None, dtype=torch.float64, retraction=None, residual_blocks: bool = False):
         """retraction: None = x + alpha dx; WRAP_PI = the built-in angle wrap; or a callable (x [B, n], dx [B, n], alpha [B]) ->
-        candidate [B, n] on torch tensors -- the reference's custom Retraction (nonlinear.hpp:127, nonlinear.cc:160-168)."""
+        candidate [B, n] on torch tensors -- the reference's custom Retraction (nonlinear.hpp:127, nonlinear.cc:160-168).
+        residual_blocks: for a Problem.FromResiduals, hand every residual's local Jacobian to the library as a packed block
+        (mo_nls_solve_blocks: UpdateHessian / UpdateJacobian on device) instead of scattering it into a dense stack."""
         if problem is None:
             raise L.MiniOptError(-1, "Must have a valid problem")          # F_ASSERT nonlinear.cc:78
         if dtype != torch.float64:
@@ -241,8 +246,21 @@ class ConstrainedNonlinearLeastSquares:
         B = self.batch
         self.variables_ = z(B, n)
         self.candidate_vars_ = z(B, n)
-        self.J, self.r, self.r_cand = z(B, m_r, n), z(B, m_r), z(B, m_r)
-        self.J_eq, self.r_eq, self.r_eq_cand = (z(B, n, k), z(B, k), z(B, k)) if k else (None, None, None)   # J_eq: k x n col-major
+        self.residual_blocks = bool(residual_blocks)
+        self._cost_layout = self._eq_layout = None
+        if self.residual_blocks:
+            if problem.cost_residuals is None or (k and problem.equality_residuals is None):
+                raise L.MiniOptError(-1, "residual_blocks needs a Problem built by Problem.FromResiduals")
+            from .qp import create_layout
+            self._cost_layout = create_layout(self._plan.h, [(res.index, res.rows) for res in problem.cost_residuals])
+            self._eq_layout = create_layout(self._plan.h, [(res.index, res.rows) for res in problem.equality_residuals]) if k else None
+            self._vals = int(L.lib().mo_residual_layout_values(self._cost_layout))
+            self._vals_eq = int(L.lib().mo_residual_layout_values(self._eq_layout)) if k else 0
+            self.J, self.r, self.r_cand = z(B, self._vals), z(B, m_r), z(B, m_r)            # J: packed blocks
+            self.J_eq, self.r_eq, self.r_eq_cand = (z(B, self._vals_eq), z(B, k), z(B, k)) if k else (None, None, None)
+        else:
+            self.J, self.r, self.r_cand = z(B, m_r, n), z(B, m_r), z(B, m_r)
+            self.J_eq, self.r_eq, self.r_eq_cand = (z(B, n, k), z(B, k), z(B, k)) if k else (None, None, None)   # J_eq: k x n col-major
         if m:
             self.cons_var = torch.tensor([[c[0] for c in problem.inequality_constraints]], dtype=torch.int32, device=dev)
             self.cons_a = torch.tensor([[c[1] for c in problem.inequality_constraints]], dtype=dtype, device=dev)
@@ -280,6 +298,11 @@ class ConstrainedNonlinearLeastSquares:
             lin = what == L.MO_NLS_EVAL_LINEARIZE
             x = self.variables_ if lin else self.candidate_vars_
             r_buf = self.r if lin else self.r_cand
+            if self.residual_blocks and lin:   # every residual's local J straight into its packed block: no dense scatter
+                self._eval_blocks(x, self.p_.cost_residuals, self.r, self.J)
+                if self.k:
+                    self._eval_blocks(x, self.p_.equality_residuals, self.r_eq, self.J_eq)
+                return 0
             if isinstance(self.p_.cost, DeviceFamily):          # a HIP kernel writes the solver's buffers directly
                 self.p_.cost.eval_into(self._plan, x, r_buf, self.J if lin else None, self.n, True)
             else:
@@ -301,6 +324,25 @@ class ConstrainedNonlinearLeastSquares:
             self._callback_error = e
             return 1
 
+    @staticmethod
+    def _eval_blocks(x, residuals, r_buf, J_buf):
+        B, row, off = int(x.shape[0]), 0, 0
+        for res in residuals:
+            R, P = res.rows, len(res.index)
+            r, Jl = res.fn(x[:, list(res.index)], True)
+            r_buf[:, row:row + R].copy_(r)
+            J_buf[:, off:off + R * P].view(B, P, R).copy_(Jl.transpose(1, 2))   # column-major R x P
+            row += R
+            off += R * P
+
+    def __del__(self):
+        try:
+            for h in (self._cost_layout, self._eq_layout):
+                if h is not None:
+                    L.lib().mo_residual_layout_destroy(h)
+        except Exception:
+            pass
+
     def _problem_struct(self) -> L.NlsProblem:
         n, k, m, m_r = self.n, self.k, self.m, self.m_r
         p = L.NlsProblem()
@@ -309,8 +351,10 @@ class ConstrainedNonlinearLeastSquares:
         p.J, p.J_stride, p.J_ld, p.J_layout = _ptr(self.J), m_r * n, n, L.MO_ROW_MAJOR
         p.r, p.r_stride = _ptr(self.r), m_r
         p.r_cand, p.r_cand_stride = _ptr(self.r_cand), m_r
+        if self.residual_blocks:
+            p.J_stride = self._vals
         if k:
-            p.J_eq, p.J_eq_stride, p.J_eq_ld = _ptr(self.J_eq), n * k, k
+            p.J_eq, p.J_eq_stride, p.J_eq_ld = _ptr(self.J_eq), (self._vals_eq if self.residual_blocks else n * k), k
             p.r_eq, p.r_eq_stride = _ptr(self.r_eq), k
             p.r_eq_cand, p.r_eq_cand_stride = _ptr(self.r_eq_cand), k
         if m:
@@ -353,8 +397,12 @@ class ConstrainedNonlinearLeastSquares:
         null_path = bool(L.lib().mo_plan_nls_uses_nullspace(self._plan.h))   # the C side's own predicate (shape AND kernel capacity)
         self._outputs_view = NLSSolverOutputs(term, nit, its, status, qp_its, qp_lag, qp_eig, null_path)
         cb = L.NLS_EVAL_FN(self._eval)
-        rc = L.lib().mo_nls_solve(self._plan.h, C.byref(prob), B, C.byref(sp), cb, None, _ptr(term), _ptr(nit), _ptr(its),
-                                  _ptr(status), _stream())
+        if self.residual_blocks:
+            rc = L.lib().mo_nls_solve_blocks(self._plan.h, C.byref(prob), self._cost_layout, self._eq_layout, B, C.byref(sp), cb, None,
+                                             _ptr(term), _ptr(nit), _ptr(its), _ptr(status), _stream())
+        else:
+            rc = L.lib().mo_nls_solve(self._plan.h, C.byref(prob), B, C.byref(sp), cb, None, _ptr(term), _ptr(nit), _ptr(its),
+                                      _ptr(status), _stream())
         if self._callback_error is not None:
             raise self._callback_error
         L.check(rc)

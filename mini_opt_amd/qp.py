@@ -388,3 +388,100 @@ def linearize(problem: BatchedQP, force_generic: bool = False):
     finally:
         lib.mo_plan_destroy(plan)
     return G, c, f
+
+
+# ---- residual-block input (mini_opt::Problem::costs: residual.hpp:60-250, nonlinear.cc:170-214) ---------------------------------------
+def pack_blocks(J_blocks) -> torch.Tensor:
+    """Packed values of a list of residual Jacobians [B, R_b, P_b] (each the local Jacobian a Residual's functor fills): [B, sum R_b P_b],
+    block b column-major at offset sum_{b' < b} R_b' P_b' -- the J_blocks input of linearize_blocks / jacobian_blocks."""
+    return torch.cat([J.transpose(1, 2).reshape(J.shape[0], -1) for J in J_blocks], dim=1).contiguous()
+
+
+def unpack_blocks(packed: torch.Tensor, shapes):
+    """Inverse of pack_blocks: shapes = [(R_b, P_b), ...] -> list of [B, R_b, P_b] views."""
+    out, off = [], 0
+    for R, P in shapes:
+        out.append(packed[:, off:off + R * P].reshape(packed.shape[0], P, R).transpose(1, 2))
+        off += R * P
+    return out
+
+
+class ResidualLayout:
+    """A residual-block layout (mo_residual_layout): blocks = [(index, rows), ...], one per Residual in order, shared by every problem of a
+    batch.  Owns an n-variable plan with m_r = sum rows on `device`, which linearize_blocks / jacobian_blocks launch on."""
+
+    def __init__(self, n: int, blocks, dtype=torch.float64, device="cuda:0"):
+        lib = L.lib()
+        self.n = int(n)
+        self.blocks = [(tuple(int(i) for i in idx), int(R)) for idx, R in blocks]
+        self.dtype = dtype
+        self.device = torch.device(device)
+        self.shapes = [(R, len(idx)) for idx, R in self.blocks]
+        self.rows = sum(R for _, R in self.blocks)
+        self._plan = None
+        self.h = None
+        desc = L.PlanDesc(self.n, 0, 0, max(self.rows, 1), _DT[dtype], self.device.index or 0, L.EXTRA_PLAN_FLAGS, 0, 0)
+        plan = C.c_void_p()
+        L.check(lib.mo_plan_create(C.byref(desc), C.byref(plan)))
+        self._plan = plan
+        self.h = create_layout(plan, self.blocks)
+        self.values = int(lib.mo_residual_layout_values(self.h))
+
+    def __del__(self):
+        try:
+            if self.h is not None:
+                L.lib().mo_residual_layout_destroy(self.h)
+            if self._plan is not None:
+                L.lib().mo_plan_destroy(self._plan)
+        except Exception:
+            pass
+
+
+def create_layout(plan, blocks) -> C.c_void_p:
+    """mo_residual_layout_create for a plan handle and [(index, rows), ...]; the caller destroys the handle."""
+    rows = (C.c_int32 * len(blocks))(*[int(R) for _, R in blocks])
+    params = (C.c_int32 * len(blocks))(*[len(idx) for idx, _ in blocks])
+    flat = [int(i) for idx, _ in blocks for i in idx]
+    index = (C.c_int32 * max(len(flat), 1))(*flat)
+    h = C.c_void_p()
+    L.check(L.lib().mo_residual_layout_create(plan, len(blocks), rows, params, index, C.byref(h)))
+    return h
+
+
+def _check_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor):
+    for t, w in ((J_blocks, layout.values), (r, layout.rows)):
+        if t.dim() != 2 or int(t.shape[1]) != w or not t.is_contiguous() or t.dtype != layout.dtype or t.device != layout.device:
+            raise ValueError(f"expected a contiguous [B, {w}] {layout.dtype} tensor on {layout.device}, got {tuple(t.shape)} {t.dtype}")
+    B = max(int(J_blocks.shape[0]), int(r.shape[0]))
+    return B, (0 if J_blocks.shape[0] == 1 else layout.values), (0 if r.shape[0] == 1 else layout.rows)
+
+
+def linearize_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, lam: float = 0.0, lam_vec: Optional[torch.Tensor] = None):
+    """Cost part of LinearizeAndFillQP (nonlinear.cc:182-189) from packed residual blocks: sum_b UpdateHessian (residual.hpp:186-226) +
+    lambda I.  Returns (G [B,n,n] col-major lower, strict upper 0; c [B,n]; sum_b 0.5 |r_b|^2 [B])."""
+    B, js, rs = _check_blocks(layout, J_blocks, r)
+    n = layout.n
+    G = torch.empty(B, n, n, dtype=layout.dtype, device=layout.device)
+    c = torch.empty(B, n, dtype=layout.dtype, device=layout.device)
+    f = torch.empty(B, dtype=layout.dtype, device=layout.device)
+    ls = 0
+    if lam_vec is not None:
+        if lam_vec.dtype != layout.dtype or not lam_vec.is_contiguous() or lam_vec.dim() != 1:
+            raise ValueError("lam_vec must be a contiguous [B] tensor of the layout's dtype")
+        ls = 0 if lam_vec.shape[0] == 1 else 1
+    L.check(L.lib().mo_linearize_blocks(layout._plan, layout.h, _ptr(J_blocks), js, _ptr(r), rs, float(lam), _ptr(lam_vec), ls, B,
+                                        _ptr(G), n * n, n, _ptr(c), n, _ptr(f), _stream()))
+    return G, c, f
+
+
+def jacobian_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, row_major: bool = False):
+    """UpdateJacobian stacked (residual.hpp:230-250, nonlinear.cc:191-206): the dense (sum R_b) x n matrix with every block's columns
+    assigned (the last of a repeated index wins) and |r|_1 [B].  row_major=False: [B, n, rows] (memory = rows x n column-major, QP::A_eq);
+    row_major=True: [B, rows, n]."""
+    B, js, rs = _check_blocks(layout, J_blocks, r)
+    n, m = layout.n, layout.rows
+    J = torch.empty((B, m, n) if row_major else (B, n, m), dtype=layout.dtype, device=layout.device)
+    s = torch.empty(B, dtype=layout.dtype, device=layout.device)
+    L.check(L.lib().mo_jacobian_blocks(layout._plan, layout.h, _ptr(J_blocks), js, _ptr(r), rs, B, _ptr(J), m * n, n if row_major else m,
+                                       L.MO_ROW_MAJOR if row_major else L.MO_COL_MAJOR, _ptr(s), _stream()))
+    return J, s

@@ -38,7 +38,7 @@ extern "C" {
 #endif
 
 #define MO_VERSION_MAJOR 0
-#define MO_VERSION_MINOR 1
+#define MO_VERSION_MINOR 2
 
 /* return codes */
 #define MO_OK 0
@@ -135,6 +135,7 @@ typedef struct {
                                          (qp.cc:366-386, used by the initial guess :455-460): only dx, dy are written,
                                          ds = dz = 0, alpha = 1 */
 #define MO_STEP_PREDICTOR_CORRECTOR 2u /* mo_iterate only: the Mehrotra double solve of qp.cc:170-187 */
+#define MO_KKT_TRANSPOSE 4u            /* mo_kkt_solve only: solve K^T u = rhs instead of K delta = -rhs */
 
 const char* mo_version_string(void);
 const char* mo_status_string(int32_t status);
@@ -396,6 +397,55 @@ int mo_jacobian_blocks(mo_plan* plan, const mo_residual_layout* layout, const vo
 int mo_nls_solve_blocks(mo_plan* plan, const mo_nls_problem* np, const mo_residual_layout* cost_layout,
                         const mo_residual_layout* eq_layout, int64_t batch, const mo_nls_params* params, mo_nls_eval_fn eval, void* user,
                         int32_t* termination, int32_t* num_iterations, void* iterations, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Differentiating through a solve: the KKT system of a state for a CALLER's right-hand side, and the gradients of a loss.
+ * With the reference's residual (qp.cc:391-420) F(v; theta) = [r_d | r_comp - mu | r_pe | r_pi], v = [x | s | y | z], C the m x n matrix
+ * with C[i, var_i] = a_i, S = diag(s), Z = diag(z):
+ *   r_d = G x + c - A_eq^T y - C^T z     r_comp = s o z     r_pe = A_eq x + b_eq     r_pi = C x + b - s
+ *           | G     0   -A_eq^T  -C^T |
+ *   K(v) =  | 0     Z     0       S   |     the matrix of BuildFullSystem; SolveForUpdate solves K delta = -r through the reduced system
+ *           | A_eq  0     0       0   |     H = G + C^T S^-1 Z C (qp.cc:275-364)
+ *           | C    -I     0       0   |
+ *
+ * The call below factorises at `vars` exactly as the Newton step does (ComputeLDLT, qp.cc:275-316: s > 0 required; status[p] =
+ * NONPOSITIVE_SLACK / FACTORIZATION_FAILED / NONFINITE / BAD_INDEX as there, `out` NaN-filled for such problems) and then runs
+ * SolveForUpdate (qp.cc:318-364) with r_ := rhs, mu = 0, delta_affine_ = 0:
+ *   flags = 0                 out = delta with K delta = -rhs.  With rhs = the r_out of the residual call above, mu subtracted from its r_comp
+ *                             block, this is the Newton direction of the hot path, bit for bit on the generic kernel.
+ *   MO_KKT_TRANSPOSE          out = u with K^T u = rhs: the kernel solves K delta = -[-g_x | -s o g_s | g_y | g_z] and returns
+ *                             [delta_x | delta_s / s | -delta_y | -delta_z], so the adjoint shares the factorisation code of the step.
+ *   MO_STEP_NO_INEQUALITIES   as in the Newton step: the system of [x | y] alone; the s and z blocks of rhs are ignored and written as 0.
+ * rhs, out: [batch][V]; rhs may alias neither vars nor out.  J-level and (G, c) input are both accepted.  The call always runs the
+ * shape-generic kernel, whatever the plan would pick for a step: the fused kernels take no right-hand side (a run-time branch there would
+ * cost registers in every one of their instantiations).  No allocation and no synchronisation on the launch path. */
+int mo_kkt_solve(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* rhs,
+                 int64_t rhs_stride, uint32_t flags, void* out, int64_t out_stride, int32_t* status, void* stream);
+
+/* Gradients of a loss l through v*(theta), the root of F(v; theta) = 0, from g = dl/dv and u = K^-T g (MO_KKT_TRANSPOSE above):
+ *   dc = -u_x                 dG = -1/2 (u_x x^T + x u_x^T)         dA_eq = y u_x^T - u_y x^T         db_eq = -u_y
+ *   dcons_a[i] = z_i u_x[var_i] - u_z[i] x[var_i]                   dcons_b[i] = -u_z[i]   (NaN for a var_i outside [0, n))
+ * and for J-level input (G = J^T J + lambda I, c = J^T r), without forming an n x n matrix:
+ *   dJ = -(J u_x) x^T - (J x + r) u_x^T        dr = -J u_x        dlambda = -u_x . x
+ * dG is the gradient with respect to a SYMMETRIC G, returned full and exactly symmetric; the library reads only the lower triangle of G
+ * (qp.cc:289), so a caller who owns just the lower entries adds dG[i][j] + dG[j][i] for i > j.
+ * Every output is optional: a NULL member is neither computed nor written.  Layouts as the inputs: dG n x n and dA_eq k x n column-major
+ * with a leading dimension, dJ m_r x n in dJ_layout (mo_layout) with dJ_ld; strides per problem, in elements.  dG with J-level input, and
+ * dJ / dr / dlambda with (G, c) input, are MO_ERR_INVALID_ARGUMENT.  Only prob->J / r (for dJ, dr) and prob->cons_var (for dcons_a) are
+ * read.  Pure data movement: one workgroup per problem in turn, every output element has one owner (no atomics), so two launches give the
+ * same bits.  No allocation and no synchronisation on the launch path. */
+typedef struct {
+  void* dG;      int64_t dG_stride; int32_t dG_ld; int32_t reserved0;   /* n x n */
+  void* dc;      int64_t dc_stride;                                   /* n */
+  void* dA_eq;   int64_t dA_stride; int32_t dA_ld; int32_t reserved1;   /* k x n */
+  void* db_eq;   int64_t db_stride;                                   /* k */
+  void* dcons_a; void* dcons_b; int64_t dcons_stride;                 /* m each */
+  void* dJ;      int64_t dJ_stride; int32_t dJ_ld; int32_t dJ_layout;   /* m_r x n */
+  void* dr;      int64_t dr_stride;                                   /* m_r */
+  void* dlambda; int64_t dlambda_stride;                              /* 1 */
+} mo_qp_grads;
+int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* u,
+                    int64_t u_stride, const mo_qp_grads* out, void* stream);
 
 #ifdef __cplusplus
 }

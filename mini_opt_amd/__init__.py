@@ -1,7 +1,18 @@
 """mini_opt_amd -- MI355X-native batched interior-point Newton steps behind mini_opt's QP API.
 
 Only what the hot path needs: csrc/ (HIP kernels + C ABI, built into lib/libminiopt_hip.so), qp.py (host mirror of
-mini_opt::QP / QPInteriorPointSolver for batches), synth.py (synthetic workloads), sharding.py (multi-GPU batch shards).
+mini_opt::QP / QPInteriorPointSolver for batches), diff.py (solve_qp: autograd through a solve), synth.py (synthetic workloads),
+sharding.py (multi-GPU batch shards).
 """
 from . import _lib  # noqa: F401
 from ._lib import MiniOptError, build  # noqa: F401
+
+
+_DIFF_EXPORTS = ("solve_qp", "kkt_solve", "qp_gradients", "QPSolveFunction", "adjoint_status")
+
+
+def __getattr__(name):  # the differentiable front end needs torch: imported on first use, like qp
+    if name in _DIFF_EXPORTS:
+        from . import diff
+        return getattr(diff, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

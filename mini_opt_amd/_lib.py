@@ -23,6 +23,7 @@ MO_PLAN_STATIC_ROUNDS_ALWAYS = 8
 # scheme this way).  A knob of THIS mirror: the library itself reads no environment variable.
 EXTRA_PLAN_FLAGS = int(os.environ.get("MO_PLAN_EXTRA_FLAGS", "0"), 0)
 MO_STEP_NO_INEQUALITIES = 1
+MO_KKT_TRANSPOSE = 4
 (MO_STATUS_OK, MO_STATUS_NONPOSITIVE_SLACK, MO_STATUS_FACTORIZATION_FAILED, MO_STATUS_NONFINITE, MO_STATUS_BAD_INDEX,
  MO_STATUS_NOT_POSITIVE_DEFINITE) = range(6)
 MO_KKT_RECORD, MO_IP_RECORD, MO_ITER_RECORD = 4, 6, 14
@@ -33,7 +34,7 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_qp_solve", "mo_fill_qp", "mo_nonlinear_errors", "mo_qp_cost_derivative",
            "mo_default_nls_params", "mo_nls_solve", "mo_nullspace_solve", "mo_residual_eval", "mo_qp_eigenvalue_stats",
            "mo_residual_layout_create", "mo_residual_layout_destroy", "mo_residual_layout_values", "mo_residual_layout_rows",
-           "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks"]
+           "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks", "mo_kkt_solve", "mo_qp_gradients"]
 
 
 class PlanDesc(C.Structure):
@@ -84,6 +85,18 @@ class NlsProblem(C.Structure):
                 ("qp_iterations", C.c_void_p), ("qp_lagrange", C.c_void_p), ("qp_eigenvalues", C.c_void_p)]
 
 
+class QPGrads(C.Structure):
+    """mo_qp_grads: optional device outputs of mo_qp_gradients (a NULL member is neither computed nor written)."""
+    _fields_ = [("dG", C.c_void_p), ("dG_stride", C.c_int64), ("dG_ld", C.c_int32), ("reserved0", C.c_int32),
+                ("dc", C.c_void_p), ("dc_stride", C.c_int64),
+                ("dA_eq", C.c_void_p), ("dA_stride", C.c_int64), ("dA_ld", C.c_int32), ("reserved1", C.c_int32),
+                ("db_eq", C.c_void_p), ("db_stride", C.c_int64),
+                ("dcons_a", C.c_void_p), ("dcons_b", C.c_void_p), ("dcons_stride", C.c_int64),
+                ("dJ", C.c_void_p), ("dJ_stride", C.c_int64), ("dJ_ld", C.c_int32), ("dJ_layout", C.c_int32),
+                ("dr", C.c_void_p), ("dr_stride", C.c_int64),
+                ("dlambda", C.c_void_p), ("dlambda_stride", C.c_int64)]
+
+
 NLS_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
 MO_NLS_EVAL_LINEARIZE, MO_NLS_EVAL_ERRORS, MO_NLS_EVAL_RETRACT, MO_NLS_EVAL_ITERATION_DONE = 0, 1, 2, 3
 MO_RETRACT_EUCLIDEAN, MO_RETRACT_WRAP_PI, MO_RETRACT_CALLBACK = 0, 1, 2
@@ -99,7 +112,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "tools", "isa_lint.py"))   # the build lints its own listings: a changed lint re-runs it
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
-        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (eleven units, the longest 5.7 min)
+        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (thirteen units, the longest 5.7 min)
         subprocess.check_call(["make", "-C", CSRC, f"-j{jobs}"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
@@ -156,6 +169,8 @@ def lib() -> C.CDLL:
     L.mo_linearize_blocks.argtypes = [vp, vp, vp, i64, vp, i64, dbl, vp, i64, i64, vp, i64, i32, vp, i64, vp, vp]
     L.mo_jacobian_blocks.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, i64, i32, i32, vp, vp]
     L.mo_nls_solve_blocks.argtypes = [vp, C.POINTER(NlsProblem), vp, vp, i64, C.POINTER(NlsParams), NLS_EVAL_FN, vp, vp, vp, vp, vp, vp]
+    L.mo_kkt_solve.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, u32, vp, i64, vp, vp]
+    L.mo_qp_gradients.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, C.POINTER(QPGrads), vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what the header declares
     _lib = L

@@ -1,8 +1,8 @@
 // kkt_generic.hip -- shape-generic LDS-resident KKT kernel for gfx950 (one problem per 256-thread workgroup).
 //
 // Handles any (n, k, m, m_r) whose reduced KKT matrix fits the CU's 160 KiB LDS, in f64 or f32, and every
-// mode of the C ABI (linearise / residual / Newton step / Iterate / full Solve).  The fixed-shape fused kernels
-// (kkt_fused.hip) are the fast path for BASELINE.json's configs; this kernel is the general path and the
+// mode of the C ABI (linearise / residual / Newton step / Iterate / full Solve / the KKT solve for a caller's
+// right-hand side).  The fixed-shape fused kernels (kkt_fused.hip) are the fast path for BASELINE.json's configs; this kernel is the general path and the
 // on-device reference they are A/B-tested against.
 //
 // Reference arithmetic reproduced (citations into /root/reference):
@@ -1654,6 +1654,45 @@ __global__ __launch_bounds__(TG * TG, LARGE ? 2 : 1) void kkt_generic_kernel(con
       continue;
     }
 
+    if (MODE == MODE_RHS) {
+      // mo_kkt_solve: SolveForUpdate (qp.cc:318-364) with r_ := the caller's vector, mu = 0, delta_affine_ = 0, behind the factorisation of the
+      // step.  Transposed: K^T u = g is K delta = -[-g_x | -s o g_s | g_y | g_z] with u = [delta_x | delta_s / s | -delta_y | -delta_z].
+      const bool no_ineq = (a.flags & MO_STEP_NO_INEQUALITIES) != 0;
+      const bool transpose = (a.flags & MO_KKT_TRANSPOSE) != 0;
+      const T* gp = (const T*)a.rhs + p * a.rhs_stride;
+      for (int i = tid; i < V; i += kThreads) {
+        const bool in_s = i >= n && i < n + m, in_z = i >= n + m + k;
+        T v = gp[i];
+        if (no_ineq && (in_s || in_z)) v = (T)0;
+        else if (transpose) v = i < n ? -v : (in_s ? -(w.vars[i] * v) : v);
+        w.res[i] = v; w.delta[i] = (T)0; w.daff[i] = (T)0;
+      }
+      __syncthreads();
+      if (st == MO_STATUS_OK) {
+        st = assemble_and_factor<T, TG, R, LARGE>(w, n, k, m, !no_ineq, tid, m_r);
+        if (st == MO_STATUS_OK) solve_for_update<T, LARGE>(w, n, k, m, (T)0, !no_ineq, tid);
+      }
+      if (st == MO_STATUS_OK) {
+        bool bad = false;
+        for (int i = tid; i < V; i += kThreads) {
+          T v = w.delta[i];
+          if (transpose) {
+            if (i >= n + m) v = -v;
+            else if (i >= n && !no_ineq) v = v / w.vars[i];
+          }
+          w.delta[i] = v;
+          bad |= !finiteT(v);
+        }
+        if (bad) w.iflag[3] = 1;
+        __syncthreads();
+        if (w.iflag[3]) st = MO_STATUS_NONFINITE;
+      }
+      T* dp = (T*)a.delta + p * a.delta_stride;
+      for (int i = tid; i < V; i += kThreads) dp[i] = st == MO_STATUS_OK ? w.delta[i] : nanT<T>();
+      if (a.status && tid == 0) a.status[p] = st;
+      continue;
+    }
+
     if (MODE == MODE_STEP || MODE == MODE_ITERATE) {
       T ip[6];
       const bool no_ineq = (a.flags & MO_STEP_NO_INEQUALITIES) != 0;
@@ -2120,6 +2159,7 @@ static hipError_t launch_generic_large(const KernelArgs& a, int dtype, int num_c
     case MODE_STEP: MO_LAUNCH_LARGE(TYPE, MODE_STEP); break;           \
     case MODE_ITERATE: MO_LAUNCH_LARGE(TYPE, MODE_ITERATE); break;     \
     case MODE_SOLVE: MO_LAUNCH_LARGE(TYPE, MODE_SOLVE); break;         \
+    case MODE_RHS: MO_LAUNCH_LARGE(TYPE, MODE_RHS); break;             \
     default: return hipErrorInvalidValue;                             \
   }
 #ifdef MO_GENERIC_LARGE_STEP_ONLY   // development builds: the fp64 step kernel alone (register-pressure probes)
@@ -2187,6 +2227,7 @@ hipError_t launch_generic(const KernelArgs& a, int dtype, int num_cus, hipStream
     case MODE_STEP: MO_LAUNCH_FACTORISING(TYPE, MODE_STEP); break;       \
     case MODE_ITERATE: MO_LAUNCH_FACTORISING(TYPE, MODE_ITERATE); break; \
     case MODE_SOLVE: MO_LAUNCH_FACTORISING(TYPE, MODE_SOLVE); break;     \
+    case MODE_RHS: MO_LAUNCH_FACTORISING(TYPE, MODE_RHS); break;         \
     default: return hipErrorInvalidValue;                               \
   }
   if (dtype == MO_F64) { MO_DISPATCH_MODE(double) } else { MO_DISPATCH_MODE(float) }

@@ -194,7 +194,7 @@ struct NlsScratch {  // one allocation carved into 256-byte aligned pieces
 
 extern "C" {
 
-const char* mo_version_string(void) { return "mini_opt_hip 0.1 (gfx950)"; }
+const char* mo_version_string(void) { return "mini_opt_hip 0.2 (gfx950)"; }
 
 const char* mo_status_string(int32_t status) {
   switch (status) {
@@ -527,6 +527,75 @@ int mo_iterate(mo_plan* plan, const mo_problem* prob, int64_t batch, void* vars,
   a.barrier_strategy = barrier_strategy;
   a.delta = delta; a.delta_stride = delta_stride; a.ip_out = ip_out; a.status = status;
   return launch(plan, a, stream);
+}
+
+int mo_kkt_solve(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* rhs,
+                 int64_t rhs_stride, uint32_t flags, void* out, int64_t out_stride, int32_t* status, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (!vars || !rhs || !out) return fail(MO_ERR_INVALID_ARGUMENT, "vars / rhs / out is NULL");
+  if (flags & ~(MO_STEP_NO_INEQUALITIES | MO_KKT_TRANSPOSE)) return fail(MO_ERR_INVALID_ARGUMENT, "unsupported flags 0x%x for mo_kkt_solve", flags);
+  if (rhs == out || rhs == vars) return fail(MO_ERR_INVALID_ARGUMENT, "rhs may alias neither vars nor out");
+  if (int rc = check_plan(plan)) return rc;
+  mo::KernelArgs a;
+  if (int rc = fill_problem(plan, prob, batch, true, true, &a)) return rc;
+  a.mode = mo::MODE_RHS;
+  a.flags = flags;
+  a.vars = const_cast<void*>(vars); a.vars_stride = vars_stride;
+  a.rhs = rhs; a.rhs_stride = rhs_stride;
+  a.delta = out; a.delta_stride = out_stride; a.status = status;
+  // always the shape-generic kernel: the fused kernels take no caller right-hand side (include/mini_opt_hip.h)
+  return launch_chosen(plan, a, KERNEL_GENERIC, stream);
+}
+
+int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* u,
+                    int64_t u_stride, const mo_qp_grads* out, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (!prob) return fail(MO_ERR_INVALID_ARGUMENT, "Must pass a non-null problem");
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  const bool j_level = prob->J != nullptr;
+  if (j_level && out->dG) return fail(MO_ERR_INVALID_ARGUMENT, "dG asked for with J-level input: ask for dJ / dr / dlambda");
+  if (!j_level && (out->dJ || out->dr || out->dlambda))
+    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr / dlambda asked for with (G, c) input: ask for dG / dc");
+  if (!vars || !u) return fail(MO_ERR_INVALID_ARGUMENT, "vars / u is NULL");
+  if (int rc = check_plan(plan)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  mo::GradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = d.n; a.k = d.k; a.m = d.m; a.batch = batch;
+  a.vars = vars; a.vars_stride = vars_stride; a.u = u; a.u_stride = u_stride;
+  a.out = *out;
+  if (d.k == 0) { a.out.dA_eq = nullptr; a.out.db_eq = nullptr; }
+  if (d.m == 0) { a.out.dcons_a = nullptr; a.out.dcons_b = nullptr; }
+  if (a.out.dJ || a.out.dr) {  // the only outputs that read J
+    if (d.m_r <= 0) return fail(MO_ERR_DIMENSION, "J given but the plan was created with m_r = 0");
+    if (prob->J_layout != MO_ROW_MAJOR && prob->J_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad J_layout");
+    const int min_ld = prob->J_layout == MO_ROW_MAJOR ? d.n : d.m_r;
+    if (prob->J_ld < min_ld) return fail(MO_ERR_DIMENSION, "J_ld %d < %d", prob->J_ld, min_ld);
+    if (!prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "J given without r");
+    a.m_r = d.m_r;
+    a.J = prob->J; a.J_stride = prob->J_stride; a.J_ld = prob->J_ld; a.J_row_major = prob->J_layout == MO_ROW_MAJOR;
+    a.r = prob->r; a.r_stride = prob->r_stride;
+    if (a.out.dJ) {
+      if (a.out.dJ_layout != MO_ROW_MAJOR && a.out.dJ_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad dJ_layout");
+      const int min_dld = a.out.dJ_layout == MO_ROW_MAJOR ? d.n : d.m_r;
+      if (a.out.dJ_ld < min_dld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a.out.dJ_ld, min_dld);
+    }
+  }
+  if (a.out.dG && a.out.dG_ld < d.n) return fail(MO_ERR_DIMENSION, "dG_ld %d < n %d", a.out.dG_ld, d.n);
+  if (a.out.dA_eq && a.out.dA_ld < d.k) return fail(MO_ERR_DIMENSION, "dA_ld %d < k %d", a.out.dA_ld, d.k);
+  if (a.out.dcons_a) {
+    if (!prob->cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a asked for but cons_var is NULL");
+    a.cons_var = prob->cons_var; a.cons_stride = prob->cons_stride;
+  }
+  if (mo::qp_grad_lds_bytes(a, plan->elem) > 64 * 1024)
+    return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, m_r = %d: the vectors of one problem exceed the 64 KiB of LDS the gradient kernel uses", d.n, d.k, d.m, a.m_r);
+  if (batch == 0) return MO_OK;
+  MO_HIP_CHECK(hipSetDevice(d.device));
+  MO_HIP_CHECK(mo::launch_qp_gradients(a, d.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
 }
 
 }  // extern "C"

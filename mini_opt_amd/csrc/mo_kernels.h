@@ -13,6 +13,7 @@ enum Mode : int {
   MODE_STEP = 2,       // qp.cc:391-420, 275-364, 485-507 on the caller's state
   MODE_ITERATE = 3,    // qp.cc:153-201
   MODE_SOLVE = 4,      // qp.cc:100-151
+  MODE_RHS = 5,        // qp.cc:275-364 on the caller's state for the CALLER's right-hand side (mo_kkt_solve): no residual, no alpha
 };
 
 // Everything a kernel needs, passed by value (kernarg segment).
@@ -67,6 +68,9 @@ struct KernelArgs {
   long long H_work_slots;   // workgroup slots behind H_work: the launch clamps its grid to it
   // diagnostics only (tools/phase_timer.hip builds kkt_fused.hip with MO_FUSED_STAMPS); NULL in the product
   unsigned long long* debug;
+  // MODE_RHS (generic kernel only): the caller's right-hand side [batch][V]; the result goes to delta.  Appended behind every older field,
+  // so the kernarg offsets the other modes read are what they were.
+  const void* rhs; long long rhs_stride;
 };
 
 // shape-generic LDS kernel (any n,k,m,m_r that fits LDS), kkt_generic.hip
@@ -190,5 +194,20 @@ struct BlocksArgs {
 };
 hipError_t launch_blocks_linearize(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
 hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
+
+// gradients of a loss through the solution of a QP (mo_qp_gradients), qp_grad.hip: rank-2 updates of the state v = [x | s | y | z] and the
+// adjoint u = K^-T g.  Inputs that are not needed for the outputs asked for may be NULL (J, r only for dJ / dr).
+struct GradArgs {
+  int n, k, m, m_r;
+  long long batch;
+  const void* vars; long long vars_stride;   // [batch][V]
+  const void* u; long long u_stride;         // [batch][V]
+  const void* J; long long J_stride; int J_ld; int J_row_major;
+  const void* r; long long r_stride;
+  const int* cons_var; long long cons_stride;
+  mo_qp_grads out;                           // NULL members are neither computed nor written
+};
+size_t qp_grad_lds_bytes(const GradArgs& a, int elem_size);
+hipError_t launch_qp_gradients(const GradArgs& a, int dtype, int num_cus, hipStream_t stream);
 
 }  // namespace mo

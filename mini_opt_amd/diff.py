@@ -1,0 +1,237 @@
+"""Differentiable batched QP: `.backward()` through QPInteriorPointSolver::Solve.
+
+    kkt_solve       mo_kkt_solve     the KKT system of a state for the caller's right-hand side (direct or transposed)
+    qp_gradients    mo_qp_gradients  gradients of a loss with respect to the QP's data from the state v and the adjoint u = K^-T g
+    solve_qp        the user-facing call: forward = Solve (the kernels of qp.QPInteriorPointSolver, fused where the shape allows),
+                    backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient
+
+The mathematics is in include/mini_opt_hip.h (above mo_kkt_solve) and DESIGN.md section 4.8.  All arithmetic happens in the HIP library;
+torch owns memory, streams and the autograd graph.  Plans are created once per (shape, dtype, device, batch) and cached.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Iterable, Optional
+
+import torch
+
+from . import _lib as L
+from .qp import _DT, BatchedQP, Params, _ptr, _stream
+
+_PLANS: Dict[tuple, C.c_void_p] = {}
+GRADIENTS = ("G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b")
+
+
+def plan_for(problem: BatchedQP, batch: int) -> C.c_void_p:
+    """The cached plan of (shape, dtype, device, batch); created on first use, kept until clear_plan_cache()."""
+    dev = problem.device
+    key = (problem.n, problem.k, problem.m, problem.m_r, problem.dtype, dev.index or 0, int(batch))
+    plan = _PLANS.get(key)
+    if plan is None:
+        desc = L.PlanDesc(problem.n, problem.k, problem.m, problem.m_r, _DT[problem.dtype], dev.index or 0, L.EXTRA_PLAN_FLAGS, 0, int(batch))
+        plan = C.c_void_p()
+        L.check(L.lib().mo_plan_create(C.byref(desc), C.byref(plan)))
+        _PLANS[key] = plan
+    return plan
+
+
+def clear_plan_cache() -> None:
+    for plan in _PLANS.values():
+        L.lib().mo_plan_destroy(plan)
+    _PLANS.clear()
+
+
+def _check_state(problem: BatchedQP, t: torch.Tensor, name: str) -> int:
+    if t.dim() != 2 or int(t.shape[1]) != problem.V or not t.is_contiguous() or t.dtype != problem.dtype or t.device != problem.device:
+        raise ValueError(f"{name}: expected a contiguous [B, {problem.V}] {problem.dtype} tensor on {problem.device}, got {tuple(t.shape)} {t.dtype}")
+    return int(t.shape[0])
+
+
+def kkt_solve(problem: BatchedQP, vars: torch.Tensor, rhs: torch.Tensor, transpose: bool = False, include_inequalities: bool = True):
+    """mo_kkt_solve: factorise the KKT matrix K of every problem at `vars` [B, V] (s > 0 required) and solve for `rhs` [B, V].
+    transpose=False: out = delta with K delta = -rhs (SolveForUpdate with r_ := rhs, mu = 0); transpose=True: out = u with K^T u = rhs.
+    Returns (out [B, V], status [B] int32 MO_STATUS_*); out is NaN for problems whose status is not OK."""
+    B = _check_state(problem, vars, "vars")
+    if _check_state(problem, rhs, "rhs") != B:
+        raise ValueError("vars and rhs must have the same batch")
+    out = torch.empty_like(vars)
+    status = torch.empty(B, dtype=torch.int32, device=vars.device)
+    flags = (L.MO_KKT_TRANSPOSE if transpose else 0) | (0 if include_inequalities else L.MO_STEP_NO_INEQUALITIES)
+    prob = problem.as_struct()
+    L.check(L.lib().mo_kkt_solve(plan_for(problem, B), C.byref(prob), B, _ptr(vars), problem.V, _ptr(rhs), problem.V, flags,
+                                 _ptr(out), problem.V, _ptr(status), _stream()))
+    return out, status
+
+
+def qp_gradients(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor, want: Optional[Iterable[str]] = None) -> Dict[str, torch.Tensor]:
+    """mo_qp_gradients: the gradients named in `want` (default: every one the problem's input level has) from the state `vars` [B, V] and
+    the adjoint `u` [B, V] = kkt_solve(..., transpose=True) of g = dl/dv.  Keys and layouts follow BatchedQP:
+      "c" [B, n]    "G" [B, n, n] (symmetric)    "A_eq" [B, n, k]    "b_eq" [B, k]    "cons_a", "cons_b" [B, m]
+      "J" (the shape and layout of problem.J)    "r" [B, m_r]    "lam" [B]
+    "G" is the gradient with respect to a symmetric G; "G" with J-level input and "J" / "r" / "lam" with (G, c) input raise."""
+    B = _check_state(problem, vars, "vars")
+    if _check_state(problem, u, "u") != B:
+        raise ValueError("vars and u must have the same batch")
+    n, k, m = problem.n, problem.k, problem.m
+    j_level = problem.J is not None
+    if want is None:
+        want = (("J", "r", "lam") if j_level else ("G", "c")) + (("A_eq", "b_eq") if k else ()) + (("cons_a", "cons_b") if m else ())
+    want = tuple(want)
+    for w in want:
+        if w not in GRADIENTS:
+            raise ValueError(f"unknown gradient {w!r}: one of {GRADIENTS}")
+        if (w in ("A_eq", "b_eq") and k == 0) or (w in ("cons_a", "cons_b") and m == 0):
+            raise ValueError(f"gradient {w!r} of a problem without such rows")
+        if (w == "G" and j_level) or (w in ("J", "r", "lam") and not j_level):
+            raise ValueError(f"gradient {w!r} does not belong to this problem's input level ((J, r, lam) or (G, c))")
+    dt, dev = problem.dtype, problem.device
+    new = lambda *shape: torch.empty(*shape, dtype=dt, device=dev)
+    out: Dict[str, torch.Tensor] = {}
+    g = L.QPGrads()
+    if "G" in want:
+        out["G"] = new(B, n, n)
+        g.dG, g.dG_stride, g.dG_ld = _ptr(out["G"]), n * n, n
+    if "c" in want:
+        out["c"] = new(B, n)
+        g.dc, g.dc_stride = _ptr(out["c"]), n
+    if "A_eq" in want:
+        out["A_eq"] = new(B, n, k)
+        g.dA_eq, g.dA_stride, g.dA_ld = _ptr(out["A_eq"]), n * k, k
+    if "b_eq" in want:
+        out["b_eq"] = new(B, k)
+        g.db_eq, g.db_stride = _ptr(out["b_eq"]), k
+    if "cons_a" in want or "cons_b" in want:
+        g.dcons_stride = m
+        if "cons_a" in want:
+            out["cons_a"] = new(B, m)
+            g.dcons_a = _ptr(out["cons_a"])
+        if "cons_b" in want:
+            out["cons_b"] = new(B, m)
+            g.dcons_b = _ptr(out["cons_b"])
+    if "J" in want:
+        rows, ld = int(problem.J.shape[1]), int(problem.J.shape[2])
+        padded = ld > (problem.m_r if problem.J_layout == "col" else n)   # (the padding beyond the matrix is not written: define it)
+        out["J"] = torch.zeros(B, rows, ld, dtype=dt, device=dev) if padded else new(B, rows, ld)
+        g.dJ, g.dJ_stride, g.dJ_ld = _ptr(out["J"]), rows * ld, ld
+        g.dJ_layout = L.MO_COL_MAJOR if problem.J_layout == "col" else L.MO_ROW_MAJOR
+    if "r" in want:
+        out["r"] = new(B, problem.m_r)
+        g.dr, g.dr_stride = _ptr(out["r"]), problem.m_r
+    if "lam" in want:
+        out["lam"] = new(B)
+        g.dlambda, g.dlambda_stride = _ptr(out["lam"]), 1
+    prob = problem.as_struct()
+    L.check(L.lib().mo_qp_gradients(plan_for(problem, B), C.byref(prob), B, _ptr(vars), problem.V, _ptr(u), problem.V, C.byref(g), _stream()))
+    return out
+
+
+class QPSolveFunction(torch.autograd.Function):
+    """v*(theta) = QPInteriorPointSolver::Solve with the adjoint of the KKT conditions as its backward.
+
+    forward(G, c, J, r, lam, A_eq, b_eq, cons_a, cons_b, cons_var, params) -> (v [B, V] = [x | s | y | z], status [B]); tensors in BatchedQP's
+    layouts, full batch, contiguous; `lam` a [B] tensor or None.  The backward solves K(v)^T u = g once and launches mo_qp_gradients once, for
+    the inputs whose needs_input_grad is set.  A problem whose forward status or adjoint status is not MO_STATUS_OK gets ZERO gradients: one
+    infeasible problem must not poison the reduction over a batch with NaN.  The adjoint's status words stay on the node
+    (`adjoint_status`, None before the first backward)."""
+
+    @staticmethod
+    def forward(ctx, G, c, J, r, lam, A_eq, b_eq, cons_a, cons_b, cons_var, params):
+        det = lambda t: None if t is None else t.detach()
+        ref = J if J is not None else G
+        n = int(ref.shape[2])
+        k = 0 if A_eq is None else int(A_eq.shape[2])
+        m = 0 if cons_a is None else int(cons_a.shape[1])
+        problem = BatchedQP(n=n, k=k, m=m, J=det(J), r=det(r), lam=0.0, lam_vec=det(lam), G=det(G), c=det(c), A_eq=det(A_eq), b_eq=det(b_eq),
+                            cons_var=cons_var, cons_a=det(cons_a), cons_b=det(cons_b))
+        B = int(ref.shape[0])
+        dev, dt = ref.device, ref.dtype
+        v = torch.zeros(B, problem.V, dtype=dt, device=dev)
+        term = torch.empty(B, dtype=torch.int32, device=dev)
+        nit = torch.empty(B, dtype=torch.int32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        prob, sp = problem.as_struct(), params.as_struct()
+        L.check(L.lib().mo_qp_solve(plan_for(problem, B), C.byref(prob), B, C.byref(sp), _ptr(v), problem.V, _ptr(term), _ptr(nit), None, None,
+                                    _ptr(status), _stream()))
+        ctx.problem, ctx.v, ctx.status = problem, v, status
+        ctx.adjoint_status = None
+        ctx.termination_state, ctx.num_iterations = term, nit
+        ctx.mark_non_differentiable(status)
+        return v.clone(), status
+
+    @staticmethod
+    def backward(ctx, g, _g_status):
+        problem, v = ctx.problem, ctx.v
+        u, adj = kkt_solve(problem, v, g.contiguous(), transpose=True)
+        ctx.adjoint_status = adj
+        names = ("G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b")
+        want = [nm for nm, need in zip(names, ctx.needs_input_grad[:9]) if need]
+        grads = qp_gradients(problem, v, u, want) if want else {}
+        ok = (ctx.status == L.MO_STATUS_OK) & (adj == L.MO_STATUS_OK)
+        out = []
+        for nm in names:
+            t = grads.get(nm)
+            if t is not None:
+                t = torch.where(ok.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros((), dtype=t.dtype, device=t.device))
+            out.append(t)
+        return (*out, None, None)
+
+
+def adjoint_status(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """The [B] status words of the adjoint solve behind a tensor solve_qp returned (None before the first backward)."""
+    seen, todo = set(), [t.grad_fn]
+    while todo:
+        node = todo.pop()
+        if node is None or node in seen:
+            continue
+        seen.add(node)
+        if hasattr(node, "adjoint_status"):
+            return node.adjoint_status
+        todo.extend(fn for fn, _ in node.next_functions)
+    return None
+
+
+def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons_var=None, cons_a=None, cons_b=None,
+             params: Optional[Params] = None, return_all: bool = False, return_status: bool = False):
+    """Solve a batch of QPs   min 1/2 x^T G x + c^T x   s.t.  A_eq x + b_eq = 0,  cons_a[i] x[cons_var[i]] + cons_b[i] >= 0   on the GPU and
+    keep the result on the autograd graph.  Give EITHER (G [B, n, n] SYMMETRIC, c [B, n]) OR the least-squares form (J [B, m_r, n], r [B, m_r],
+    lam: float or [B] tensor; G = J^T J + lam I, c = J^T r, lam added where > 0).  A_eq [B, k, n] (rows = constraints), b_eq [B, k];
+    cons_var int32 [B, m] (never differentiable), cons_a, cons_b [B, m]; a leading dimension of 1 is broadcast over the batch.
+    Returns x [B, n] (return_all: x, s, y, z), and with return_status also the [B] int32 forward status (MO_STATUS_*).
+
+    Gradients: every floating-point input that requires_grad receives one, nothing else is computed.  G's gradient is the one with respect
+    to a symmetric G, -1/2 (u_x x^T + x u_x^T).  Problems whose forward or adjoint status is not OK receive zero gradients (see
+    QPSolveFunction); adjoint_status(x) returns the adjoint's status words after a backward.  The derivative is that of the KKT conditions
+    at the returned point: it is as accurate as the solve (termination_kkt_tol), and at an active inequality the slack sits at the
+    interior-point floor, so K is ill-conditioned there by construction."""
+    params = params if params is not None else Params()
+    if (J is None) == (G is None):
+        raise ValueError("give either (G, c) or (J, r)")
+    ref = J if J is not None else G
+    if ref.dim() != 3:
+        raise ValueError("G / J must be [B, rows, n]")
+    B = max(int(t.shape[0]) for t in (G, c, J, r, A_eq, b_eq, cons_a, cons_b) if t is not None)
+    full = lambda t: None if t is None else (t.expand(B, *t.shape[1:]) if t.shape[0] != B else t).contiguous()
+    lam_t = None
+    if isinstance(lam, torch.Tensor):
+        if J is None:
+            raise ValueError("lam belongs to the (J, r) form")
+        lam_t = full(lam.reshape(-1))
+    elif float(lam) != 0.0:
+        if J is None:
+            raise ValueError("lam belongs to the (J, r) form")
+        lam_t = torch.full((B,), float(lam), dtype=ref.dtype, device=ref.device)
+    if (cons_var is None) != (cons_a is None) or (cons_a is None) != (cons_b is None):
+        raise ValueError("cons_var, cons_a and cons_b come together")
+    if cons_var is not None and cons_var.dtype != torch.int32:
+        raise ValueError("cons_var must be int32")
+    A_t = None if A_eq is None else full(A_eq).transpose(1, 2).contiguous()   # BatchedQP's layout: memory = k x n column-major
+    v, status = QPSolveFunction.apply(full(G), full(c), full(J), full(r), lam_t, A_t, full(b_eq), full(cons_a), full(cons_b),
+                                      full(cons_var), params)
+    n = int(ref.shape[2])
+    k = 0 if A_eq is None else int(A_eq.shape[1])
+    m = 0 if cons_a is None else int(cons_a.shape[1])
+    x = v[:, :n]
+    res = (x, v[:, n:n + m], v[:, n + m:n + m + k], v[:, n + m + k:]) if return_all else (x,)
+    if return_status:
+        res = res + (status,)
+    return res[0] if len(res) == 1 else res

@@ -1,0 +1,147 @@
+"""The differentiable QP's launches, per launch, event-timed, in one process: mo_kkt_solve (direct and transposed),
+mo_qp_gradients (dc only; dG + dc; the J-level set dJ + dr + dlambda), the forward mo_qp_solve, and -- the yardstick of mo_kkt_solve --
+mo_newton_step on a MO_PLAN_FORCE_GENERIC plan of the same shape.  Prints one JSON line per shape.
+
+  cfg3  n = 64, k = 8, m = 32, m_r = 128 (BASELINE configs[2])        ref8  n = 8, k = 2, m = 4, m_r = 16 (the reference's own size)
+
+mo_kkt_solve does strictly less than the generic Newton step (no residual, no alpha) and reads one more V-vector: kkt_over_step is expected
+at or below 1.1.  backward = the transposed solve + the J-level gradient launch; backward_over_forward is expected above 1 where the forward
+runs on a fused kernel.  mo_qp_gradients is data movement: achieved bytes/s against its algorithmic bytes (the vectors and matrices it must
+read and write once)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+from mini_opt_amd import _lib as L  # noqa: E402
+from mini_opt_amd import qp as Q  # noqa: E402
+from mini_opt_amd import synth  # noqa: E402
+
+SHAPES = {"cfg3": (64, 8, 32, 128), "ref8": (8, 2, 4, 16)}
+HBM = 8.0e12
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / 1e3 / reps
+
+
+def run(shape, dtype, batch, reps, warmup, rounds):
+    n, k, m, m_r = SHAPES[shape]
+    dev = torch.device("cuda:0")
+    elem = 8 if dtype == torch.float64 else 4
+    qp, v, mu = synth.make_batch_torch(n, k, m, m_r, batch, dev, dtype)
+    V = qp.V
+    lib = L.lib()
+    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    s = Q._stream()
+
+    def plan_of(flags):
+        desc = L.PlanDesc(n, k, m, m_r, Q._DT[dtype], 0, flags, 0, batch)
+        plan = C.c_void_p()
+        L.check(lib.mo_plan_create(C.byref(desc), C.byref(plan)))
+        return plan
+
+    plan, plan_generic = plan_of(0), plan_of(L.MO_PLAN_FORCE_GENERIC)
+    pj = qp.as_struct()
+    # the (G, c) twin of the same problems
+    G = torch.empty(batch, n, n, dtype=dtype, device=dev)
+    c = torch.empty(batch, n, dtype=dtype, device=dev)
+    L.check(lib.mo_linearize(plan, C.byref(pj), batch, P(G), n * n, n, P(c), n, None, s))
+    qg = Q.BatchedQP(n=n, k=k, m=m, G=G, c=c, A_eq=qp.A_eq, b_eq=qp.b_eq, cons_var=qp.cons_var, cons_a=qp.cons_a, cons_b=qp.cons_b)
+    pg = qg.as_struct()
+    rhs = torch.randn(batch, V, dtype=dtype, device=dev)
+    out = torch.empty_like(rhs)
+    u = torch.empty_like(rhs)
+    delta = torch.empty_like(rhs)
+    alpha = torch.empty(batch, 2, dtype=dtype, device=dev)
+    status = torch.empty(batch, dtype=torch.int32, device=dev)
+    dG = torch.empty(batch, n, n, dtype=dtype, device=dev)
+    dc = torch.empty(batch, n, dtype=dtype, device=dev)
+    dJ = torch.empty(batch, m_r, n, dtype=dtype, device=dev)
+    dr = torch.empty(batch, m_r, dtype=dtype, device=dev)
+    dlam = torch.empty(batch, dtype=dtype, device=dev)
+    g_c, g_G, g_J = L.QPGrads(), L.QPGrads(), L.QPGrads()
+    g_c.dc, g_c.dc_stride = dc.data_ptr(), n
+    g_G.dc, g_G.dc_stride, g_G.dG, g_G.dG_stride, g_G.dG_ld = dc.data_ptr(), n, dG.data_ptr(), n * n, n
+    g_J.dJ, g_J.dJ_stride, g_J.dJ_ld, g_J.dJ_layout = dJ.data_ptr(), m_r * n, n, L.MO_ROW_MAJOR
+    g_J.dr, g_J.dr_stride, g_J.dlambda, g_J.dlambda_stride = dr.data_ptr(), m_r, dlam.data_ptr(), 1
+    prm = Q.Params(max_iterations=10)
+    solver = Q.QPInteriorPointSolver(qp)
+
+    calls = {
+        "kkt_solve": lambda: L.check(lib.mo_kkt_solve(plan, C.byref(pj), batch, P(v), V, P(rhs), V, 0, P(out), V, P(status), s)),
+        "kkt_solve_transposed": lambda: L.check(lib.mo_kkt_solve(plan, C.byref(pj), batch, P(v), V, P(rhs), V, L.MO_KKT_TRANSPOSE, P(u), V,
+                                                                 P(status), s)),
+        "newton_step_generic": lambda: L.check(lib.mo_newton_step(plan_generic, C.byref(pj), batch, P(v), V, P(mu), 1, 0.995, 0, P(delta), V,
+                                                                  P(alpha), P(status), s)),
+        "newton_step_plan_default": lambda: L.check(lib.mo_newton_step(plan, C.byref(pj), batch, P(v), V, P(mu), 1, 0.995, 0, P(delta), V,
+                                                                       P(alpha), P(status), s)),
+        "kkt_solve_transposed_qp_level": lambda: L.check(lib.mo_kkt_solve(plan, C.byref(pg), batch, P(v), V, P(rhs), V, L.MO_KKT_TRANSPOSE,
+                                                                          P(out), V, P(status), s)),
+        "gradients_c": lambda: L.check(lib.mo_qp_gradients(plan, C.byref(pg), batch, P(v), V, P(u), V, C.byref(g_c), s)),
+        "gradients_G": lambda: L.check(lib.mo_qp_gradients(plan, C.byref(pg), batch, P(v), V, P(u), V, C.byref(g_G), s)),
+        "gradients_J": lambda: L.check(lib.mo_qp_gradients(plan, C.byref(pj), batch, P(v), V, P(u), V, C.byref(g_J), s)),
+        "forward_solve": lambda: solver.Solve(prm, record_iterations=False),
+    }
+    for fn in calls.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    best = {key: float("inf") for key in calls}
+    for _ in range(rounds):  # alternating rounds, best of
+        for key, fn in calls.items():
+            best[key] = min(best[key], timed(fn, reps if key != "forward_solve" else max(1, reps // 4)))
+    algo = {"gradients_c": elem * 2 * n, "gradients_G": elem * (2 * n + n * n + n),
+            "gradients_J": elem * (m_r * n + m_r + 2 * n + m_r * n + m_r + 1)}
+    res = {"shape": shape, "n": n, "k": k, "m": m, "m_r": m_r, "dtype": str(dtype).split(".")[-1], "batch": batch,
+           "step_kernel_plan_default": lib.mo_plan_step_kernel(plan, C.byref(pj)).decode(), "solve_kernel": solver.solve_kernel()}
+    res.update({key + "_s": t for key, t in best.items()})
+    res["kkt_over_step"] = best["kkt_solve"] / best["newton_step_generic"]
+    res["kkt_transposed_over_step"] = best["kkt_solve_transposed"] / best["newton_step_generic"]
+    res["backward_s"] = best["kkt_solve_transposed"] + best["gradients_J"]
+    res["backward_over_forward"] = res["backward_s"] / best["forward_solve"]
+    for key, b in algo.items():
+        res[key + "_bytes_per_problem"] = b
+        res[key + "_TBps"] = b * batch / best[key] / 1e12
+        res[key + "_frac_8TBps"] = b * batch / best[key] / HBM
+    for pl in (plan, plan_generic):
+        lib.mo_plan_destroy(pl)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="cfg3,ref8")
+    ap.add_argument("--dtype", default="f64")
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    L.build()
+    lines = []
+    for sh in a.shapes.split(","):
+        res = run(sh, torch.float64 if a.dtype == "f64" else torch.float32, a.batch, a.reps, a.warmup, a.rounds)
+        print(json.dumps(res), flush=True)
+        lines.append(res)
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            for res in lines:
+                fh.write(json.dumps(res) + "\n")
+
+
+if __name__ == "__main__":
+    main()

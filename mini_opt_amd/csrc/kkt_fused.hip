@@ -30,7 +30,7 @@
 
 #include <type_traits>
 
-#include "mo_kernels.h"
+#include "mo_fused_select.h"
 
 namespace mo {
 namespace {
@@ -66,12 +66,6 @@ __device__ inline double readlane_f64(double v, int lane) {
 __device__ inline double bpermute_f64(int byte_addr, double v) {
   int lo = __builtin_amdgcn_ds_bpermute(byte_addr, __double2loint(v));
   int hi = __builtin_amdgcn_ds_bpermute(byte_addr, __double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-template <int LANE_IN_ROW> __device__ inline double row_bcast(double v) {  // every lane of a 16-lane row <- lane LANE_IN_ROW
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, 0x150 + LANE_IN_ROW, 0xf, 0xf, false);  // all lanes written: no "old" value to set up
-  hi = __builtin_amdgcn_mov_dpp(hi, 0x150 + LANE_IN_ROW, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
 }
 typedef unsigned u2v __attribute__((ext_vector_type(2)));
@@ -377,32 +371,10 @@ __device__ inline void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "me
 // Symmetric sweep of pivots 0..NPIV-1 of a symmetric 16x16 tile held in the C/D layout.  Afterwards the swept block holds
 // -T11^-1, the swept x unswept block T11^-1 T12 (the solution for an augmented right-hand-side column) and the unswept
 // block the Schur complement.  Returns false if a pivot is zero or not finite.
-// Broadcast flavours (SW): the f64 MFMA and the VALU share one datapath on gfx950 (tools/coissue.hip: beside back-to-back
-// f64 MFMAs a second wave issues only ~1.5 v_fma_f64 per MFMA), so VALU instructions are as precious as MFMAs, while the
-// LDS crossbar (ds_bpermute) is idle but has ~100+ cycles of latency.  0: both broadcasts through ds_bpermute (fewest
-// VALU instructions; wants >= 3-4 waves per SIMD), 1: row k through ds_bpermute, column k through DPP, 2: VALU only.
-template <int K, int SW>
-__device__ inline void sweep_step(d4& T, bool& ok, int g, int j) {
-  constexpr int src_g = K & 3, src_t = K >> 2;
-  const double rowreg = T[src_t];  // every broadcast below is taken before any register of T is modified
-  const double d = readlane_f64(rowreg, 16 * src_g + K);
-  ok = ok && (fabs(d) > 0.0) && (fabs(d) < INFINITY);
-  const double inv = rcp_f64(d);
-  // T(k, j) for this lane's column j, in every row
-  const double rowk = SW == 2 ? bcast_from_row<src_g>(rowreg) : bpermute_f64((16 * src_g + j) * 4, rowreg);
-  const double rk = (j == K) ? -inv : rowk * inv;
-  double f[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)  // T(g + 4t, k): column k of this lane's own rows ( = T(k, g + 4t) by symmetry)
-    f[t] = SW == 0 ? bpermute_f64((16 * src_g + g + 4 * t) * 4, rowreg) : row_bcast<K>(T[t]);
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const double a0 = (j == K) ? 0.0 : T[t];
-    double nv = fma(-f[t], rk, a0);
-    if (t == src_t) nv = (g == src_g) ? rk : nv;
-    T[t] = nv;
-  }
-}
+// The f64 MFMA and the VALU share one datapath on gfx950 (tools/coissue.hip: beside back-to-back f64 MFMAs a second wave issues only
+// ~1.5 v_fma_f64 per MFMA), so VALU instructions are as precious as MFMAs, while the LDS crossbar (ds_bpermute) is idle but has ~100+
+// cycles of latency: the lean sweep takes row k over the crossbar and column k through DPP.  (The other broadcast mixes and a fused
+// v_fmac_f64_dpp form were measured and rejected)
 // Pad behind an EXEC-masked VALU write inside an asm block.  What the next instruction may need: a DPP read of the VGPR just written
 // (2 wait states: the s_mov_b64 that restores EXEC is one, `s_nop 0` the other).  The 5 wait states of "EXEC written -> DPP" apply to
 // VALU writes of EXEC (v_cmpx) only; an s_mov to EXEC is interlocked by the hardware (hipcc itself puts DPP ops right behind
@@ -412,7 +384,7 @@ __device__ inline void sweep_step(d4& T, bool& ok, int g, int j) {
 #else
 #define MO_MASKED_PAD "0"
 #endif
-// 64-bit helpers for the lean sweep (SW == 3): one v_mov_b64_dpp instead of two 32-bit DPP movs, and EXEC-masked v_mov_b64
+// 64-bit helpers for the lean sweep: one v_mov_b64_dpp instead of two 32-bit DPP movs, and EXEC-masked v_mov_b64
 // instead of v_cndmask_b32 pairs.  The asm blocks restore EXEC and end with the wait states a following DPP op needs.
 template <int LANE_IN_ROW> __device__ inline double row_bcast64(double v) {
   return __longlong_as_double(__builtin_amdgcn_mov_dpp(__double_as_longlong(v), 0x150 + LANE_IN_ROW, 0xf, 0xf, false));
@@ -446,7 +418,7 @@ template <unsigned long long MASK> __device__ inline void masked_zero4(d4& T) { 
 // `bad` accumulates 0 * (1/d): it turns NaN at a zero (or NaN) pivot and stays 0.0 otherwise -- one FMA per pivot instead
 // of a compare whose sixteen scalar results hipcc parks in spill lanes.  (An infinite pivot is not flagged here; it makes the
 // tile NaN and surfaces as MO_STATUS_NONFINITE.)
-template <int K, bool BPF>
+template <int K>
 __device__ inline void sweep_step_lean(d4& T, double& bad, int g, int j) {
   constexpr int src_g = K & 3, src_t = K >> 2;
   constexpr unsigned long long mcol = 0x0001000100010001ull << K;           // the four lanes of tile column k (j == K)
@@ -464,8 +436,7 @@ __device__ inline void sweep_step_lean(d4& T, double& bad, int g, int j) {
   masked_set_neg<mcol>(rk, inv);
   double f[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t)  // T(g + 4t, k): column k of this lane's own rows ( = T(k, g + 4t) by symmetry when BPF)
-    f[t] = BPF ? bpermute_f64(4 * g + (64 * src_g + 16 * t), rowreg) : row_bcast64<K>(T[t]);
+  for (int t = 0; t < 4; ++t) f[t] = row_bcast64<K>(T[t]);  // T(g + 4t, k): column k of this lane's own rows
   masked_zero4<mcol>(T);
 #pragma unroll
   for (int t = 0; t < 4; ++t) T[t] = fma(-f[t], rk, T[t]);
@@ -473,100 +444,19 @@ __device__ inline void sweep_step_lean(d4& T, double& bad, int g, int j) {
   masked_set<mrow>(rowk_new, rk);
   T[src_t] = rowk_new;
 }
-// ---- the fused-broadcast sweep (SW == 5) --------------------------------------------------------------------------------------
-// v_fmac_f64 has a DPP form on gfx950 (VOP2), and row_newbcast may read the destination register itself (tools/dpp_fmac.hip checks it
-// bit for bit):  T[t] <- T[t] - T[t](row lane K) * rk  is ONE instruction where the lean sweep spends a v_mov_b64_dpp and a v_fma_f64.
-// The pivot column cannot ride along (its lanes ARE the broadcast source): rk is zeroed there for the fused update and the column is
-// scaled by 1/d afterwards under an EXEC mask.  The pivot check moves to the scalar unit: d passes through SGPRs anyway (v_readlane), so
-// "zero" and "not finite" are integer tests on its bits, accumulated as a running min / max -- no VALU instruction at all.
-template <unsigned long long MASK> __device__ inline void masked_zero1(double& v) {  // v = 0 in the lanes of MASK
-  unsigned long long save;
-  asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\tv_mov_b64 %[d], 0\n\t"
-               "s_mov_b64 exec, %[sv]\n\ts_nop " MO_MASKED_PAD
-               : [d] "+v"(v), [sv] "=&s"(save)
-               : [lo] "i"((unsigned)(MASK & 0xffffffffull)), [hi] "i"((unsigned)(MASK >> 32)));
-}
-template <unsigned long long MASK> __device__ inline void masked_mul4(d4& T, double f) {  // T[0..3] *= f in the lanes of MASK
-  unsigned long long save;
-  double t0 = T[0], t1 = T[1], t2 = T[2], t3 = T[3];
-  asm volatile(
-      "s_mov_b64 %[sv], exec\n\ts_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\tv_mul_f64 %[a], %[a], %[f]\n\tv_mul_f64 %[b], %[b], %[f]\n\t"
-      "v_mul_f64 %[c], %[c], %[f]\n\tv_mul_f64 %[d], %[d], %[f]\n\ts_mov_b64 exec, %[sv]\n\ts_nop " MO_MASKED_PAD
-      : [a] "+v"(t0), [b] "+v"(t1), [c] "+v"(t2), [d] "+v"(t3), [sv] "=&s"(save)
-      : [f] "v"(f), [lo] "i"((unsigned)(MASK & 0xffffffffull)), [hi] "i"((unsigned)(MASK >> 32)));
-  T[0] = t0; T[1] = t1; T[2] = t2; T[3] = t3;
-}
-template <int K> __device__ inline void fmac_bcast4(d4& T, double rk0) {  // T[t] -= T[t](lane K of the row) * rk0, t = 0..3
-  double t0 = T[0], t1 = T[1], t2 = T[2], t3 = T[3];
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_fmac_f64_dpp %[a], -%[a], %[r] row_newbcast:%[k] row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %[b], -%[b], %[r] row_newbcast:%[k] row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %[c], -%[c], %[r] row_newbcast:%[k] row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %[d], -%[d], %[r] row_newbcast:%[k] row_mask:0xf bank_mask:0xf"
-      : [a] "+v"(t0), [b] "+v"(t1), [c] "+v"(t2), [d] "+v"(t3)
-      : [r] "v"(rk0), [k] "i"(K));
-  T[0] = t0; T[1] = t1; T[2] = t2; T[3] = t3;
-}
-struct PivotBits { unsigned min_mag, max_hi; };  // running min of the pivots' magnitude bits / max of their high words (scalar registers)
-template <int K>
-__device__ inline void sweep_step_fmac(d4& T, PivotBits& pb, int g, int j) {
-  constexpr int src_g = K & 3, src_t = K >> 2;
-  constexpr unsigned long long mcol = 0x0001000100010001ull << K;           // the four lanes of tile column k (j == K)
-  constexpr unsigned long long mrow = 0xFFFFull << (16 * src_g);            // the 16 lanes of the row group that holds row k
-  const double rowreg = T[src_t];  // every broadcast below is taken before any register of T is modified
-  const unsigned dlo = (unsigned)__builtin_amdgcn_readlane(__double2loint(rowreg), 16 * src_g + K);
-  const unsigned dhi = (unsigned)__builtin_amdgcn_readlane(__double2hiint(rowreg), 16 * src_g + K);
-  const double d = __hiloint2double((int)dhi, (int)dlo);
-  {  // scalar unit: |d| == 0  <=>  mag == 0;  d not finite  <=>  (hi & 0x7fffffff) >= 0x7ff00000
-    const unsigned ahi = dhi & 0x7fffffffu;
-    const unsigned mag = ahi | (dlo >> 1) | (dlo & 1u);
-    pb.min_mag = mag < pb.min_mag ? mag : pb.min_mag;
-    pb.max_hi = ahi > pb.max_hi ? ahi : pb.max_hi;
-  }
-  double inv = __builtin_amdgcn_rcp(d);
-  inv = fma(inv, fma(-d, inv, 1.0), inv);  // one Newton step: |inv d - 1| < 2e-15 (tools/microbench.hip)
-  double rk = bpermute_f64((16 * src_g + j) * 4, rowreg) * inv;  // T(k, j) / d for this lane's column j, in every row
-  double rk0 = rk;
-  masked_zero1<mcol>(rk0);           // the pivot column sits the fused update out
-  fmac_bcast4<K>(T, rk0);            // T(i, j) -= T(i, k) T(k, j) / d   (j != k)
-  masked_mul4<mcol>(T, inv);         // T(i, k) <- T(i, k) / d
-  masked_set_neg<mcol>(rk, inv);     // T(k, k) <- -1 / d
-  double rowk_new = T[src_t];
-  masked_set<mrow>(rowk_new, rk);    // row k <- T(k, j) / d
-  T[src_t] = rowk_new;
-}
-template <int K, int KEND> struct SweepLoopFmac {
-  static __device__ inline void run(d4& T, PivotBits& pb, int npiv, int g, int j) {
-    if (K < npiv) sweep_step_fmac<K>(T, pb, g, j);  // wave-uniform
-    SweepLoopFmac<K + 1, KEND>::run(T, pb, npiv, g, j);
+template <int K, int KEND> struct SweepLoop {
+  static __device__ inline void run(d4& T, double& bad, int npiv, int g, int j) {
+    if (K < npiv) sweep_step_lean<K>(T, bad, g, j);  // wave-uniform
+    SweepLoop<K + 1, KEND>::run(T, bad, npiv, g, j);
   }
 };
-template <int KEND> struct SweepLoopFmac<KEND, KEND> {
-  static __device__ inline void run(d4&, PivotBits&, int, int, int) {}
+template <int KEND> struct SweepLoop<KEND, KEND> {
+  static __device__ inline void run(d4&, double&, int, int, int) {}
 };
-template <int K, int KEND, int SW> struct SweepLoop {
-  static __device__ inline void run(d4& T, bool& ok, double& bad, int npiv, int g, int j) {
-    if (K < npiv) {  // wave-uniform
-      if (SW >= 3) sweep_step_lean<K, SW == 4>(T, bad, g, j);
-      else sweep_step<K, SW>(T, ok, g, j);
-    }
-    SweepLoop<K + 1, KEND, SW>::run(T, ok, bad, npiv, g, j);
-  }
-};
-template <int KEND, int SW> struct SweepLoop<KEND, KEND, SW> {
-  static __device__ inline void run(d4&, bool&, double&, int, int, int) {}
-};
-template <int SW> __device__ inline bool sweep_tile(d4& T, int npiv, int g, int j) {
-  if (SW == 5) {
-    PivotBits pb{0xffffffffu, 0u};
-    SweepLoopFmac<0, 16>::run(T, pb, npiv, g, j);
-    return pb.min_mag != 0u && pb.max_hi < 0x7ff00000u;
-  }
-  bool ok = true;
+__device__ inline bool sweep_tile(d4& T, int npiv, int g, int j) {
   double bad = 0.0;
-  SweepLoop<0, 16, SW>::run(T, ok, bad, npiv, g, j);
-  return ok && (bad == 0.0);
+  SweepLoop<0, 16>::run(T, bad, npiv, g, j);
+  return bad == 0.0;
 }
 
 // ---- reusable components ----------------------------------------------------------------------------------------
@@ -581,7 +471,6 @@ template <int SW> __device__ inline bool sweep_tile(d4& T, int npiv, int g, int 
 // fetches its own operands J(4s+g, col) as two dwords each through per-lane LDS-DMA addresses (wave-uniform part of the address on the
 // scalar unit: base + column part; one VGPR holds the lane part g * row_stride + 2j * column_stride).  2 NT + 1 DMAs per group, operand c
 // at dwords [2c][lane] and [2c+1][lane] of the slot.  The memory system sees 4-byte pieces: this is the flexible path, not the fast one.
-constexpr int JMODE_VECTOR = 0, JMODE_FLAT = 1, JMODE_GATHER = 2;
 template <int NT, int D, int JMODE = JMODE_VECTOR, int NY = 1, bool ROW0 = true>
 struct JStream {
   static constexpr bool FLAT = JMODE == JMODE_FLAT, GATHER = JMODE == JMODE_GATHER;
@@ -798,13 +687,13 @@ struct JStream {
 // [A_eq^T | rhs]).  Afterwards the diagonal tiles hold -T^-1, the off-diagonal tiles their forward-eliminated values.
 // Pivots of diagonal tile pa: 16 for the x tiles and for every y tile but the last, which holds the remaining k - 16 (NY - 1) equality rows.
 template <int NT, int NY> __device__ inline int tile_pivots(int pa, int k) { return pa < NT + NY - 1 ? 16 : k - 16 * (NY - 1); }
-template <int NT, int SW, int NY = 1>
+template <int NT, int NY = 1>
 __device__ inline bool block_eliminate(d4 (&U)[(NT + NY) * (NT + NY)], int k, int g, int j) {
   constexpr int NB = NT + NY;
   bool ok = true;
 #pragma unroll
   for (int pa = 0; pa < NB; ++pa) {
-    ok = sweep_tile<SW>(U[pa * NB + pa], tile_pivots<NT, NY>(pa, k), g, j) && ok;
+    ok = sweep_tile(U[pa * NB + pa], tile_pivots<NT, NY>(pa, k), g, j) && ok;
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int pc = pa + 1; pc < NB; ++pc) {
@@ -818,9 +707,9 @@ __device__ inline bool block_eliminate(d4 (&U)[(NT + NY) * (NT + NY)], int k, in
 }
 
 #ifndef MO_LA_MIN_NT
-#define MO_LA_MIN_NT 6   // smallest tile grid (NT = n / 16) whose step kernel eliminates with look-ahead (A/B knob; 99 = only where SW == 6 asks)
+#define MO_LA_MIN_NT 6   // smallest tile grid (NT = n / 16) whose step kernel eliminates with look-ahead (A/B knob)
 #endif
-// ---- look-ahead elimination (SW == 6) ------------------------------------------------------------------------------------------
+// ---- look-ahead elimination ---------------------------------------------------------------------------------------------------
 // The diagonal sweeps are dependent VALU chains, the trailing updates independent MFMA chains; in program order "sweep, then all updates"
 // a wave alternates between a phase that can only wait on itself and a phase that only feeds the matrix pipe.  Here the update of block
 // step pa is split: the column of tile (pa+1, pa+1) first, then the sweep of that tile INTERLEAVED, pivot by pivot, with the remaining
@@ -933,7 +822,7 @@ template <int NT, int PA> struct LookAheadSteps {
 };
 template <int NT>
 __device__ inline bool block_eliminate_lookahead(d4 (&U)[(NT + 1) * (NT + 1)], int k, int g, int j) {
-  const bool ok0 = sweep_tile<3>(U[0], 16, g, j);
+  const bool ok0 = sweep_tile(U[0], 16, g, j);
   __builtin_amdgcn_sched_barrier(0);
   double bad = 0.0;
   LookAheadSteps<NT, 0>::run(U, bad, k, g, j);
@@ -1062,7 +951,7 @@ template <int NT, int WPS, int MC = 1, int NY = 1> struct FusedCfg {
 
 // One workgroup of 4*WPS independent waves per CU (so that exactly WPS waves sit on every SIMD).  The waves never
 // synchronise with each other; each owns its slice of the workgroup's LDS.
-template <int NT, int WPS, int SW, bool QPL, int MC = 1, int JMODE = JMODE_VECTOR, int NY = 1>
+template <int NT, int WPS, bool QPL, int MC = 1, int JMODE = JMODE_VECTOR, int NY = 1>
 __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const KernelArgs a) {
   using C = FusedCfg<NT, WPS, MC, NY>;
   constexpr int MCAP = C::MCAP;
@@ -1306,13 +1195,13 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
     // whatever is left): +0.4 % on two boxes; priority on the J stream instead: -0.8 %.
     if (a.chain_prio) __builtin_amdgcn_s_setprio(1);
     bool ok = true;
-    constexpr bool kLookAhead = SW == 6 || (NT >= MO_LA_MIN_NT && NY == 1);   // the large grids run one or two waves per SIMD: little else hides the sweeps there
+    constexpr bool kLookAhead = NT >= MO_LA_MIN_NT && NY == 1;   // the large grids run one or two waves per SIMD: little else hides the sweeps there
     if constexpr (kLookAhead) {
       ok = block_eliminate_lookahead<NT>(U, k, g, j);
     } else {
 #pragma unroll
     for (int pa = 0; pa < NB; ++pa) {
-      ok = sweep_tile<SW>(U[pa * NB + pa], tile_pivots<NT, NY>(pa, k), g, j) && ok;
+      ok = sweep_tile(U[pa * NB + pa], tile_pivots<NT, NY>(pa, k), g, j) && ok;
       __builtin_amdgcn_sched_barrier(0);
       MO_STAMP(3);
 #pragma unroll
@@ -1617,7 +1506,7 @@ template <int NT, int WPS, int MC = 1, int NY = 1> struct SolveCfg {
 
 __device__ inline double wave_sum_f64(double v) { return cross_row_sum(row_sum(v)); }
 
-template <int NT, int WPS, int SW, bool QPL, int MC = 1, int JMODE = JMODE_VECTOR, int NY = 1, bool PCK = true>
+template <int NT, int WPS, bool QPL, int MC = 1, int JMODE = JMODE_VECTOR, int NY = 1, bool PCK = true>
 __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_solve_kernel(const KernelArgs a) {
   using C = SolveCfg<NT, WPS, MC, NY>;
   constexpr int N = C::N, NB = NT + NY, LT = NB - 1, SLOT = C::SLOT, D = C::D;  // LT: the tile column that carries the right-hand side
@@ -2205,10 +2094,10 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_solve_kernel(const K
       // section 8), but the Solve kernel runs two and its cached passes are chains: 9.38 -> 9.55 M solves/s, 11.86 -> 12.03 M predictor-corrector
       bool elim_ok;
       if constexpr (NY == 1 && (NT == 4 || NT >= MO_LA_MIN_NT)) elim_ok = block_eliminate_lookahead<NT>(U, k, g, j);
-      else elim_ok = block_eliminate<NT, SW, NY>(U, k, g, j);
+      else elim_ok = block_eliminate<NT, NY>(U, k, g, j);
       if (!__all(elim_ok)) { st = MO_STATUS_FACTORIZATION_FAILED; break; }   // (__all: a scalar branch, see the decision point)
 #else
-      if (!__all(block_eliminate<NT, SW, NY>(U, k, g, j))) { st = MO_STATUS_FACTORIZATION_FAILED; break; }
+      if (!__all(block_eliminate<NT, NY>(U, k, g, j))) { st = MO_STATUS_FACTORIZATION_FAILED; break; }
 #endif
       double xb[NB];
       back_substitute<NT, NY>(U, k, j, xb);  // xb[c] = dx (permuted), xb[NT + q] = -dy
@@ -2429,275 +2318,112 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_solve_kernel(const K
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// ---- the instantiations as data -----------------------------------------------------------------------------------
+// Every translation unit of the fused fp64 kernels is one table of rows {key, kernel}; MO_FUSED_ROW is the only place where a key turns
+// into template arguments.  A key whose unused fields are not the normalised ones (mo_fused_select.h) has no FusedKernelOf; a row in the
+// table of a unit that fused_unit() does not name for its key fails the static_assert.
+template <int F, int NT, int WPS, bool QPL, int MC, int JMODE, int NY, bool PCK> struct FusedKernelOf;
+template <int NT, int WPS, bool QPL, int MC, int JMODE, int NY> struct FusedKernelOf<FUSED_STEP, NT, WPS, QPL, MC, JMODE, NY, true> {
+  static constexpr FusedKernel kernel = kkt_fused_f64_kernel<NT, WPS, QPL, MC, JMODE, NY>;
+};
+template <int NT, int WPS, bool QPL, int MC, int JMODE, int NY, bool PCK> struct FusedKernelOf<FUSED_SOLVE, NT, WPS, QPL, MC, JMODE, NY, PCK> {
+  static constexpr FusedKernel kernel = kkt_fused_solve_kernel<NT, WPS, QPL, MC, JMODE, NY, PCK>;
+};
+template <int NT, int WPS, int JMODE> struct FusedKernelOf<FUSED_LINEARIZE, NT, WPS, false, 1, JMODE, 1, true> {
+  static constexpr FusedKernel kernel = kkt_fused_linearize_kernel<NT, WPS, JMODE>;
+};
+template <int UNIT, int F, int NT, int WPS, bool QPL, int MC, int JMODE, int NY, bool PCK> struct FusedRowOf {
+  static constexpr FusedKey key{F, NT, WPS, QPL, MC, JMODE, NY, PCK};
+  static_assert(fused_unit(key) == UNIT, "this row belongs to the table of another translation unit");
+  static FusedRow row() { return FusedRow{key, FusedKernelOf<F, NT, WPS, QPL, MC, JMODE, NY, PCK>::kernel}; }
+};
+// (family, NT, WPS, QPL, MC, JMODE, NY, PCK) in the table of unit kUnit
+#define MO_FUSED_ROW(...) FusedRowOf<kUnit, __VA_ARGS__>::row()
+#define MO_FUSED_TABLE_SIZE(rows) (int)(sizeof(rows) / sizeof(rows[0]))
 
 }  // namespace
 
-#ifndef MO_FUSED_IMPL_ONLY  // kkt_fused_gather.hip includes this file for the templates only
-// J-level input whose layout the 16-byte / flat streams cannot take: column-major, a leading dimension beyond n, rows that are not 16-byte
-// aligned (even n), odd n beyond the flat stream's 64 -- served by the per-lane gather stream (JMODE_GATHER, kkt_fused_gather.hip).
-bool fused_needs_gather(const KernelArgs& a) {
-  if (!a.J) return false;
-  if (!a.J_row_major || a.J_ld != a.n) return true;
-  if (a.n & 1) return a.n > 64 || a.m > 64;
-  return !aligned16(a.J) || (a.J_stride & 1);
-}
-
-bool fused_supported(const KernelArgs& a, int dtype) {
-  if (dtype != MO_F64) return false;
-  if (a.flags & ~MO_STEP_NO_INEQUALITIES) return false;
-  if (a.flags && a.mode != MODE_STEP && a.mode != MODE_RESIDUAL) return false;
-  if (a.mode == MODE_LINEARIZE) {  // standalone J^T J: J-level fp64; packed J on the 16-byte stream, every other layout (odd n included) on the gather stream
-    return a.J && a.ticket && a.G_out && a.c_out && a.n >= 2 && a.n <= 128 && a.m_r > 0 && a.J_ld >= (a.J_row_major ? a.n : a.m_r) && a.G_out_ld >= a.n;
-  }
-  if (a.mode != MODE_SOLVE && a.mode != MODE_ITERATE && a.mode != MODE_STEP && a.mode != MODE_RESIDUAL) return false;
-  if (a.mode == MODE_RESIDUAL && !a.r_out) return false;
-  if (a.n < 2 || a.n > 128) return false;  // padded to 32 / 64 / 96 / 128 variables inside the kernel
-  if (a.m < 0) return false;
-  if (a.k > 31) {  // one y tile up to k = 15, two (kkt_fused_ny2.hip) up to 31, three / four (kkt_fused_ny34.hip) up to 47 / 63 on the 32 / 64 grids,
-                   // and since round 4 three / four on the 96 grid (45 / 55 live tiles) and three on the 128 grid (66: it spills, and is still 2 x the generic kernel)
-    if (a.k > 63) return false;                  // (m <= 256 as everywhere since round 4: four constraint slots per lane beyond 128)
-    if (a.n > 96 && a.k > 47) return false;      // (the 128 grid with four y tiles would be 78 live tiles)
-    if (a.mode == MODE_LINEARIZE) return false;
-    // (every layout of J since round 4: the gather instantiations of kkt_fused_ny34.hip, one constraint slot per lane -- m <= 64 below)
-    if (a.J && (a.n & 1) && a.m > 64) return false;
-  }
-  // up to four constraint slots per lane: m <= 256 (beyond 128, and beyond 64 for Solve / Iterate on the 96 / 128 grids: kkt_fused_mc4.hip)
-  if (a.m > 256) return false;
-  if (a.m > 128 && a.J && (a.n & 1)) return false;  // the flat-stream kernels carry one slot
-  // (round 4: the two-y-tile kernels carry up to four slots on every grid, Solve / Iterate included -- a box on each of 128 variables
-  // beside 16 .. 31 equalities used to fall to the generic kernel)
-  if (!a.ticket || !a.vars) return false;
-  if (a.mode == MODE_STEP && !a.delta) return false;
-  if (a.J) {  // J-level: 16-byte pieces of a packed row-major J (even n), the flat-group stream (odd n <= 64), or the gather stream
-    if (a.m_r <= 0) return false;  // m_r % 4 rows are handled after the ring stream
-    if (a.J_ld < (a.J_row_major ? a.n : a.m_r)) return false;
-    if (fused_needs_gather(a) && a.m > 64) return false;  // the gather instantiations carry one constraint slot per lane
-  } else {    // QP-level: G, c given; no alignment requirements
-    if (!a.G || !a.c || a.G_ld < a.n) return false;
-  }
-  return true;
-}
-
-const char* fused_name(const KernelArgs& a, int) {
-#if !defined(MO_FUSED_STAMPS) && !defined(MO_GENERIC_STAMPS)
-  if (fused_tiny_supported(a)) {  // the whole KKT system in one tile (kkt_fused_tiny.hip)
-    const bool solve = a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL;
-    if (!a.J) return solve ? "fused_solve_qp_tiny_f64" : "fused_qp_tiny_f64";
-    return solve ? "fused_solve_tiny_f64" : "fused_tiny_f64";
-  }
+#ifndef MO_FUSED_IMPL_ONLY  // the other units include this file for the templates only
+namespace {
+constexpr int kUnit = UNIT_MAIN;
+// one y tile, k <= 15; packed J, the flat stream or (G, c); one or two constraint slots (Solve with two: the 32 / 64 grids)
+const FusedRow kRows[] = {
+    MO_FUSED_ROW(FUSED_LINEARIZE, 2, 3, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_LINEARIZE, 4, 3, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_LINEARIZE, 6, 2, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_LINEARIZE, 8, 1, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 2, 4, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 2, 4, true, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 2, 3, false, 1, JMODE_FLAT, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 2, 3, false, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 2, 3, true, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 3, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 3, true, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 3, false, 1, JMODE_FLAT, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 2, false, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 2, true, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 6, 2, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 6, 2, true, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 6, 2, false, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 6, 2, true, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 8, 1, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 8, 1, true, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 8, 1, false, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 8, 1, true, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 2, 3, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 2, 3, true, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 2, 3, false, 1, JMODE_FLAT, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 2, 3, false, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 2, 3, true, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, true, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, false, 1, JMODE_FLAT, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, false, 2, JMODE_VECTOR, 1, false),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, false, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, true, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 6, 1, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 6, 1, true, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 8, 1, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 8, 1, true, 1, JMODE_VECTOR, 1, true),
+#ifdef MO_TUNING   // MO_FUSED_WPS: the plain step kernel with one wave per SIMD less
+    MO_FUSED_ROW(FUSED_STEP, 2, 3, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 2, 3, true, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 2, false, 1, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 2, true, 1, JMODE_VECTOR, 1, true),
 #endif
-  if (a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL) {
-    if (!a.J) return a.n > 96 ? "fused_solve_qp_f64_n128" : a.n > 64 ? "fused_solve_qp_f64_n96" : a.n > 32 ? "fused_solve_qp_f64_n64" : "fused_solve_qp_f64_n32";
-    return a.n > 96 ? "fused_solve_mfma_f64_n128" : a.n > 64 ? "fused_solve_mfma_f64_n96" : a.n > 32 ? "fused_solve_mfma_f64_n64" : "fused_solve_mfma_f64_n32";
+};
+}  // namespace
+FusedTable fused_table_main() { return {kRows, MO_FUSED_TABLE_SIZE(kRows)}; }
+
+FusedTable fused_table(int unit) {
+  switch (unit) {
+    case UNIT_MAIN: return fused_table_main();
+#ifndef MO_FUSED_SINGLE_UNIT
+    case UNIT_GATHER: return fused_table_gather();
+    case UNIT_NY2: return fused_table_ny2();
+    case UNIT_NY34: return fused_table_ny34();
+    case UNIT_MC4: return fused_table_mc4();
+    case UNIT_TINY: return fused_table_tiny();
+#endif
+    default: return {nullptr, 0};
   }
-  // the tile grid the problem is padded to
-  if (!a.J) return a.n > 96 ? "fused_qp_f64_n128" : a.n > 64 ? "fused_qp_f64_n96" : a.n > 32 ? "fused_qp_f64_n64" : "fused_qp_f64_n32";
-  return a.n > 96 ? "fused_mfma_f64_n128" : a.n > 64 ? "fused_mfma_f64_n96" : a.n > 32 ? "fused_mfma_f64_n64" : "fused_mfma_f64_n32";
 }
 
 hipError_t launch_fused(const KernelArgs& a_in, int, int num_cus, hipStream_t stream) {
+  const FusedLaunch L = fused_select(a_in, num_cus);
+  const FusedTable table = fused_table(fused_unit(L.key));
+  FusedKernel kernel = nullptr;
+  for (int i = 0; i < table.count && !kernel; ++i)
+    if (table.rows[i].key == L.key) kernel = table.rows[i].kernel;
+  if (!kernel) return hipErrorInvalidDeviceFunction;   // a key without a row is an internal error: there is no fallback kernel
   KernelArgs a = a_in;
-  // static rounds up to this many problems per wave (mo_kernels.h; measured): equal-cost work (step, Iterate, residual,
-  // linearisation) splits statically further than a Solve, whose problems need different numbers of passes
-  if (a.static_rounds < 0) a.static_rounds = a.mode == MODE_SOLVE ? (a.n > 32 ? 2 : 6) : (a.n > 32 ? 8 : 32);
-#ifdef MO_TUNING   // (A/B builds only: the product library reads no environment variable)
-  static const int env_stagger = [] { const char* e = getenv("MO_FUSED_STAGGER"); return e ? atoi(e) : -1; }();
-  static const int env_wps = [] { const char* e = getenv("MO_FUSED_WPS"); return e ? atoi(e) : 0; }();
-  static const int env_sw = [] { const char* e = getenv("MO_FUSED_SWEEP"); return e ? atoi(e) : -1; }();
-#else
-  constexpr int env_stagger = -1, env_wps = 0, env_sw = -1;
-#endif
-  // the 64-variable grid of the step kernel with J-level input (the BASELINE configs[2] / [4] shape); measured neutral elsewhere
-  const bool headline_shape = a.mode == MODE_STEP && a.J && a.n > 32 && a.n <= 64;
-  a.stagger = env_stagger >= 0 ? (env_stagger & 0xff) : (headline_shape ? 4 : 0);
-  a.chain_prio = env_stagger >= 0 ? ((env_stagger >> 8) & 1) : (headline_shape ? 1 : 0);   // MO_FUSED_STAGGER = units + 256 * priority
-  // Waves per SIMD the kernel is register-budgeted for (defaults picked from measurements; MO_FUSED_WPS in -DMO_TUNING builds).
-  // 64 grid: 3 (A/B in DESIGN.md).  32 grid: FOUR since round 4 (the kernel needs 100 VGPRs).  Round 3 had measured a fourth wave 10 % slower at
-  // BASELINE configs[1] (0.136 vs 0.123 ms) -- when launches still took a ticket per problem; with static rounds it is faster at every batch
-  // size: configs[1] 86.4 / 87.1 -> 94.9 / 96.4 M steps/s (4 096 problems are ONE round of 4 096 waves), batch 65 536: 140.6 -> 152.9 M.
-  const int wps = a.n > 32 ? (env_wps == 2 ? 2 : 3) : (env_wps == 3 ? 3 : 4);
-  const int sw = (env_sw >= 0 && env_sw <= 6) ? env_sw : 3;
-  long long grid = num_cus;  // one workgroup of 4*wps waves per CU; problems are pulled from the ticket counter
-  const long long blocks_needed = (a.batch + 3) / 4;
-  if (grid > blocks_needed) grid = blocks_needed;
-  if (grid < 1) grid = 1;
-  // The work counter is zeroed on the stream in front of the kernel -- unless the launch is certain to run in static rounds, which never touch
-  // it: every kernel below has at least 4 waves per workgroup and min(CUs, ceil(batch / 4)) workgroups, so batch <= rounds x 4 x workgroups
-  // is static whatever the instantiation (the kernels test batch <= rounds x waves).  One enqueued operation less per small launch.
-  {
-    long long wgs = (a.batch + 3) / 4;
-    if (wgs > num_cus) wgs = num_cus;
-#if !defined(MO_FUSED_STAMPS) && !defined(MO_GENERIC_STAMPS)
-    const bool tickets_always = fused_tiny_supported(a);   // the one-tile kernel hands out tickets of up to 64 problems whatever the size
-#else
-    const bool tickets_always = false;
-#endif
-    const bool surely_static = !tickets_always && a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * 4 * wgs;
-    if (!surely_static) {
-      hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), stream);
-      if (e != hipSuccess) return e;
-    }
+  a.stagger = L.stagger; a.chain_prio = L.chain_prio; a.static_rounds = L.static_rounds;
+  if (L.zero_ticket) {
+    hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return e;
   }
-#if !defined(MO_FUSED_STAMPS) && !defined(MO_GENERIC_STAMPS)  // (the diagnostic builds of tools/phase_timer*.hip link this file alone)
-  if (fused_tiny_supported(a)) return launch_fused_tiny(a, num_cus, stream);
-  if (a.mode != MODE_LINEARIZE && a.k <= 15 && !fused_needs_gather(a) && !(a.J && (a.n & 1)) &&
-      (a.m > 128 || (a.m > 64 && a.n > 64 && a.mode != MODE_STEP)))
-    return launch_fused_mc4(a, num_cus, stream);
-  if (a.mode != MODE_LINEARIZE && a.k > 31) return launch_fused_ny34(a, num_cus, stream);
-  if (a.mode != MODE_LINEARIZE && a.k > 15) return launch_fused_ny2(a, num_cus, stream);
-  if (fused_needs_gather(a) || (a.mode == MODE_LINEARIZE && (a.n & 1))) return launch_fused_gather(a, num_cus, stream);
-#endif
-  if (a.mode == MODE_LINEARIZE) {
-    const int wl = a.n > 96 ? 1 : (a.n > 64 ? 2 : 3);
-    long long lgrid = num_cus;
-    const long long lneed = (a.batch + 3) / 4;
-    if (lgrid > lneed) lgrid = lneed;
-    if (lgrid < 1) lgrid = 1;
-    const dim3 lgd((unsigned)lgrid), lbd(256 * wl);
-    if (a.n > 96) hipLaunchKernelGGL((kkt_fused_linearize_kernel<8, 1>), lgd, lbd, 0, stream, a);
-    else if (a.n > 64) hipLaunchKernelGGL((kkt_fused_linearize_kernel<6, 2>), lgd, lbd, 0, stream, a);
-    else if (a.n > 32) hipLaunchKernelGGL((kkt_fused_linearize_kernel<4, 3>), lgd, lbd, 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_linearize_kernel<2, 3>), lgd, lbd, 0, stream, a);
-    return hipGetLastError();
-  }
-  if (a.J && (a.n & 1)) {  // odd n: flat-group J stream
-    const bool solve = a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL;
-    const int wf = (a.n > 32 && solve) ? 2 : 3;
-    long long fgrid = num_cus;
-    const long long fneed = (a.batch + 3) / 4;
-    if (fgrid > fneed) fgrid = fneed;
-    if (fgrid < 1) fgrid = 1;
-    const dim3 fgd((unsigned)fgrid), fbd(256 * wf);
-    if (solve) {
-      if (a.n > 32) hipLaunchKernelGGL((kkt_fused_solve_kernel<4, 2, 3, false, 1, true>), fgd, fbd, 0, stream, a);
-      else hipLaunchKernelGGL((kkt_fused_solve_kernel<2, 3, 3, false, 1, true>), fgd, fbd, 0, stream, a);
-    } else {
-      if (a.n > 32) hipLaunchKernelGGL((kkt_fused_f64_kernel<4, 3, 3, false, 1, true>), fgd, fbd, 0, stream, a);
-      else hipLaunchKernelGGL((kkt_fused_f64_kernel<2, 3, 3, false, 1, true>), fgd, fbd, 0, stream, a);
-    }
-    return hipGetLastError();
-  }
-  if (a.mode == MODE_STEP && a.m > 64) {  // two constraint slots per lane (a box on every one of 64 variables is m = 128)
-    const int wq = a.n > 96 ? 1 : (a.n > 32 ? 2 : 3);
-    long long qgrid = num_cus;
-    const long long qneed = (a.batch + 3) / 4;
-    if (qgrid > qneed) qgrid = qneed;
-    if (qgrid < 1) qgrid = 1;
-    const dim3 qgd((unsigned)qgrid), qbd(256 * wq);
-#define MO_FUSED_MC2(NT_, WPS_)                                                                                      \
-  do {                                                                                                               \
-    if (a.J) hipLaunchKernelGGL((kkt_fused_f64_kernel<NT_, WPS_, 3, false, 2>), qgd, qbd, 0, stream, a);             \
-    else hipLaunchKernelGGL((kkt_fused_f64_kernel<NT_, WPS_, 3, true, 2>), qgd, qbd, 0, stream, a);                  \
-  } while (0)
-    if (a.n > 96) MO_FUSED_MC2(8, 1);
-    else if (a.n > 64) MO_FUSED_MC2(6, 2);
-    else if (a.n > 32) MO_FUSED_MC2(4, 2);
-    else MO_FUSED_MC2(2, 3);
-#undef MO_FUSED_MC2
-    return hipGetLastError();
-  }
-  if (a.m > 64) {  // Solve / Iterate with two constraint slots per lane (n <= 64, checked by fused_supported)
-    const int wq = a.n > 32 ? 2 : 3;
-    long long qgrid = num_cus;
-    const long long qneed = (a.batch + 3) / 4;
-    if (qgrid > qneed) qgrid = qneed;
-    if (qgrid < 1) qgrid = 1;
-    const dim3 qgd((unsigned)qgrid), qbd(256 * wq);
-    // (J-level on the 64 grid: the instantiation with the corrector's code needs 20 B of scratch, the one without none -- picked by strategy)
-    const bool pc = (a.mode == MODE_SOLVE ? a.sp.barrier_strategy : a.barrier_strategy) == MO_PREDICTOR_CORRECTOR && a.mode != MODE_RESIDUAL;
-    if (a.n > 32) {
-      if (a.J && !pc) hipLaunchKernelGGL((kkt_fused_solve_kernel<4, 2, 3, false, 2, JMODE_VECTOR, 1, false>), qgd, qbd, 0, stream, a);
-      else if (a.J) hipLaunchKernelGGL((kkt_fused_solve_kernel<4, 2, 3, false, 2>), qgd, qbd, 0, stream, a);
-      else hipLaunchKernelGGL((kkt_fused_solve_kernel<4, 2, 3, true, 2>), qgd, qbd, 0, stream, a);
-    } else {
-      if (a.J) hipLaunchKernelGGL((kkt_fused_solve_kernel<2, 3, 3, false, 2>), qgd, qbd, 0, stream, a);
-      else hipLaunchKernelGGL((kkt_fused_solve_kernel<2, 3, 3, true, 2>), qgd, qbd, 0, stream, a);
-    }
-    return hipGetLastError();
-  }
-  if (a.n > 64) {  // 96 / 128-variable tile grids: correctness-first instantiations (the 128 one spills), one or two waves per SIMD
-    const bool big = a.n > 96, solve = a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL;
-    const int bw = (!big && !solve) ? 2 : 1;
-    long long bgrid = num_cus;
-    const long long bneed = (a.batch + 3) / 4;
-    if (bgrid > bneed) bgrid = bneed;
-    if (bgrid < 1) bgrid = 1;
-    const dim3 bgd((unsigned)bgrid), bbd(256 * bw);
-    if (solve) {
-      if (big) { if (a.J) hipLaunchKernelGGL((kkt_fused_solve_kernel<8, 1, 3, false>), bgd, bbd, 0, stream, a); else hipLaunchKernelGGL((kkt_fused_solve_kernel<8, 1, 3, true>), bgd, bbd, 0, stream, a); }
-      else { if (a.J) hipLaunchKernelGGL((kkt_fused_solve_kernel<6, 1, 3, false>), bgd, bbd, 0, stream, a); else hipLaunchKernelGGL((kkt_fused_solve_kernel<6, 1, 3, true>), bgd, bbd, 0, stream, a); }
-    } else {
-      if (big) { if (a.J) hipLaunchKernelGGL((kkt_fused_f64_kernel<8, 1, 3, false>), bgd, bbd, 0, stream, a); else hipLaunchKernelGGL((kkt_fused_f64_kernel<8, 1, 3, true>), bgd, bbd, 0, stream, a); }
-      else { if (a.J) hipLaunchKernelGGL((kkt_fused_f64_kernel<6, 2, 3, false>), bgd, bbd, 0, stream, a); else hipLaunchKernelGGL((kkt_fused_f64_kernel<6, 2, 3, true>), bgd, bbd, 0, stream, a); }
-    }
-    return hipGetLastError();
-  }
-  if (a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL) {  // register budget of the Solve kernel: 2 waves per SIMD at n = 64, 3 at n = 32
-    const int swps = a.n > 32 ? 2 : 3;
-    long long sgrid = num_cus;
-    const long long need = (a.batch + 3) / 4;
-    if (sgrid > need) sgrid = need;
-    if (sgrid < 1) sgrid = 1;
-    const dim3 sgd((unsigned)sgrid), sbd(256 * swps);
-    if (a.n > 32) {
-      if (a.J) hipLaunchKernelGGL((kkt_fused_solve_kernel<4, 2, 3, false>), sgd, sbd, 0, stream, a);
-      else hipLaunchKernelGGL((kkt_fused_solve_kernel<4, 2, 3, true>), sgd, sbd, 0, stream, a);
-    } else {
-      if (a.J) hipLaunchKernelGGL((kkt_fused_solve_kernel<2, 3, 3, false>), sgd, sbd, 0, stream, a);
-      else hipLaunchKernelGGL((kkt_fused_solve_kernel<2, 3, 3, true>), sgd, sbd, 0, stream, a);
-    }
-    return hipGetLastError();
-  }
-  const dim3 gd((unsigned)grid), bd(256 * wps);
-#ifndef MO_TUNING
-  // The product build carries ONE instantiation per tile grid and input level: three waves per SIMD (four on the 32 grid), the lean sweep (SW = 3).  The other
-  // waves-per-SIMD / sweep flavours DESIGN.md section 8 measured and rejected are instantiated in -DMO_TUNING builds only.
-  (void)sw;
-  if (a.n > 32) {
-    if (a.J) hipLaunchKernelGGL((kkt_fused_f64_kernel<4, 3, 3, false>), gd, bd, 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f64_kernel<4, 3, 3, true>), gd, bd, 0, stream, a);
-  } else {
-    if (a.J) hipLaunchKernelGGL((kkt_fused_f64_kernel<2, 4, 3, false>), gd, bd, 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f64_kernel<2, 4, 3, true>), gd, bd, 0, stream, a);
-  }
+  hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(L.block), 0, stream, a);
   return hipGetLastError();
-#else
-  if (!a.J) {  // QP-level input: default flavour only
-    if (a.n > 32) {
-      if (wps == 3) hipLaunchKernelGGL((kkt_fused_f64_kernel<4, 3, 3, true>), gd, bd, 0, stream, a);
-      else hipLaunchKernelGGL((kkt_fused_f64_kernel<4, 2, 3, true>), gd, bd, 0, stream, a);
-    } else {
-      if (wps == 3) hipLaunchKernelGGL((kkt_fused_f64_kernel<2, 3, 3, true>), gd, bd, 0, stream, a);
-      else hipLaunchKernelGGL((kkt_fused_f64_kernel<2, 4, 3, true>), gd, bd, 0, stream, a);
-    }
-    return hipGetLastError();
-  }
-#define MO_FUSED_LAUNCH(NT_, WPS_, SW_) hipLaunchKernelGGL((kkt_fused_f64_kernel<NT_, WPS_, SW_, false>), gd, bd, 0, stream, a)
-// MO_FUSED_SWEEP = 5 (fused-broadcast sweep) / 6 (look-ahead elimination): measured and rejected; they are only
-// instantiated in builds with -DMO_FUSED_EXPERIMENTS (A/B runs), the product build carries neither.
-#ifdef MO_FUSED_EXPERIMENTS
-#define MO_FUSED_EXPERIMENTAL(NT_, WPS_)              \
-    else if (sw == 5) MO_FUSED_LAUNCH(NT_, WPS_, 5);  \
-    else if (sw == 6) MO_FUSED_LAUNCH(NT_, WPS_, 6);
-#else
-#define MO_FUSED_EXPERIMENTAL(NT_, WPS_)
-#endif
-#define MO_FUSED_BY_SW(NT_, WPS_)                     \
-  do {                                                \
-    if (sw == 1) MO_FUSED_LAUNCH(NT_, WPS_, 1);       \
-    MO_FUSED_EXPERIMENTAL(NT_, WPS_)                  \
-    else MO_FUSED_LAUNCH(NT_, WPS_, 3);               \
-  } while (0)
-  if (a.n > 32) {
-    if (wps == 3) MO_FUSED_BY_SW(4, 3); else MO_FUSED_BY_SW(4, 2);
-  } else {
-    if (wps == 3) MO_FUSED_BY_SW(2, 3); else MO_FUSED_BY_SW(2, 4);
-  }
-#undef MO_FUSED_BY_SW
-#undef MO_FUSED_LAUNCH
-  return hipGetLastError();
-#endif  // MO_TUNING
 }
 
 #endif  // MO_FUSED_IMPL_ONLY

@@ -111,14 +111,8 @@ __device__ inline void lds_fence32() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "
 #else
 #define MO_F32_PAD "0"
 #endif
-#ifndef MO_F32_LOOKAHEAD
-#define MO_F32_LOOKAHEAD 0   // A/B knob: 1 = look-ahead elimination (measured: -2.2 % at BASELINE configs[3])
-#endif
 #ifndef MO_F32_RHS_VECTOR   // A/B knob (step kernel): 0 = the right-hand side in tile column NT + 1, as in rounds 1 - 3
-#define MO_F32_RHS_VECTOR (!MO_F32_LOOKAHEAD)   // round 4: a vector (registers + two LDS hops per block step): -180 MFMAs at NT = 8, +1.0 %
-#endif
-#if MO_F32_RHS_VECTOR && MO_F32_LOOKAHEAD
-#error "the look-ahead elimination schedules the MFMAs of tile column NT + 1: build it with -DMO_F32_RHS_VECTOR=0"
+#define MO_F32_RHS_VECTOR 1   // round 4: a vector (registers + two LDS hops per block step): -180 MFMAs at NT = 8, +1.0 %
 #endif
 template <unsigned long long MASK> __device__ inline void masked_set_f32(float& dst, float src) {
   unsigned long long save;
@@ -180,127 +174,6 @@ template <int KEND> struct SweepLoop32<KEND, KEND> {
 __device__ inline bool sweep_tile_f32(f4& T, int npiv, int j) {
   float bad = 0.0f;
   SweepLoop32<0, 16>::run(T, bad, npiv, j);
-  return bad == 0.0f;
-}
-
-// ---- look-ahead elimination of the step kernel ----------------------------------------------------------------------------------
-// Program order "sweep tile (pa, pa), then every update of block step pa" makes a wave alternate between a dependent VALU chain that
-// leaves the matrix pipe idle (16 pivots of ~150 cycles each) and a run of MFMAs that leaves the VALU idle -- and the fp32 MFMA, unlike
-// the fp64 one, does not share the VALU's datapath, so the two can run side by side inside ONE wave.  The update of block step pa is
-// split: the column of tile (pa+1, pa+1) first, then the sweep of that tile interleaved pivot by pivot with the remaining tile products
-// of step pa (they touch neither that tile nor its operands).  Work items (one item = one 16x16x16 tile product = four MFMAs) stay in
-// program order -- all four MFMAs of an item before the next one: the updates of a panel need its finished -Z, the next panel product
-// overwrites it -- so every tile sees the same operations in the same order as in the plain loop: bit-identical results.
-// Tile columns: x blocks 0 .. NT-1, y block NT, right-hand side NR = NT + 1 (NB = NT + 2); rows pb <= NT.
-template <int NT> constexpr int la32_rows(int pa, int pc) { return (pc < NT ? pc : NT) - pa; }   // tiles (pa+1 .. min(pc, NT), pc) updated at step pa
-template <int NT> constexpr int la32_count(int pa) { int c = 0; for (int pc = pa + 2; pc < NT + 2; ++pc) c += 1 + la32_rows<NT>(pa, pc); return c; }
-template <int NT> constexpr int la32_pc(int pa, int idx) {
-  for (int pc = pa + 2; pc < NT + 2; ++pc) { const int n = 1 + la32_rows<NT>(pa, pc); if (idx < n) return pc; idx -= n; }
-  return -1;
-}
-template <int NT> constexpr int la32_sub(int pa, int idx) {  // 0: the panel product -Z = (-T^-1) U_ac;  s >= 1: update of tile (pa + s, pc)
-  for (int pc = pa + 2; pc < NT + 2; ++pc) { const int n = 1 + la32_rows<NT>(pa, pc); if (idx < n) return idx; idx -= n; }
-  return -1;
-}
-template <int NT> constexpr int la32_per_pivot(int pa) { return (la32_count<NT>(pa) + 15) / 16; }
-// the Q-th of the four MFMAs of work item IDX of block step PA
-template <int NT, int PA, int IDX, int Q> __device__ inline void la32_mfma(f4 (&U)[(NT + 2) * (NT + 2)], f4& negZ) {
-  constexpr int NB = NT + 2;
-  if constexpr (IDX < la32_count<NT>(PA)) {
-    constexpr int pc = la32_pc<NT>(PA, IDX), sub = la32_sub<NT>(PA, IDX);
-    if constexpr (sub == 0) {
-      if constexpr (Q == 0) negZ = f4{0.0f, 0.0f, 0.0f, 0.0f};
-      negZ = __builtin_amdgcn_mfma_f32_16x16x4f32(U[PA * NB + PA][Q], U[PA * NB + pc][Q], negZ, 0, 0, 0);
-    } else {
-      U[(PA + sub) * NB + pc] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[PA * NB + (PA + sub)][Q], negZ[Q], U[(PA + sub) * NB + pc], 0, 0, 0);
-    }
-  }
-}
-// What goes to wait point P (0 .. 3) of pivot K's chain: with one item per pivot its P-th MFMA; with M > 1 items per pivot (pivot K owns
-// items K M .. K M + M - 1) whole items, spread over the points in order.
-template <int NT, int PA, int K, int P> __device__ inline void la32_point(f4 (&U)[(NT + 2) * (NT + 2)], f4& negZ) {
-  constexpr int M = la32_per_pivot<NT>(PA);
-  static_assert(M <= 4, "work items per pivot");
-  if constexpr (M <= 1) {
-    la32_mfma<NT, PA, K, P>(U, negZ);
-  } else {
-    constexpr int slot = M == 2 ? (P == 0 ? 0 : (P == 2 ? 1 : -1)) : (P < M ? P : -1);
-    if constexpr (slot >= 0) {
-      la32_mfma<NT, PA, K * M + slot, 0>(U, negZ); la32_mfma<NT, PA, K * M + slot, 1>(U, negZ);
-      la32_mfma<NT, PA, K * M + slot, 2>(U, negZ); la32_mfma<NT, PA, K * M + slot, 3>(U, negZ);
-    }
-  }
-}
-template <int NT, int PA, int K>
-__device__ inline void sweep_step_work_f32(f4 (&U)[(NT + 2) * (NT + 2)], f4& negZ, float& bad, bool active, int j) {
-  constexpr int NB = NT + 2;
-  constexpr int src_g = K >> 2, src_t = K & 3;
-  constexpr unsigned long long mcol = 0x0001000100010001ull << K;
-  constexpr unsigned long long mrow = 0xFFFFull << (16 * src_g);
-  f4& T = U[(PA + 1) * NB + (PA + 1)];
-  if (!active) {  // wave-uniform: pivots beyond the y tile's k rows -- only the work
-    la32_point<NT, PA, K, 0>(U, negZ); la32_point<NT, PA, K, 1>(U, negZ); la32_point<NT, PA, K, 2>(U, negZ); la32_point<NT, PA, K, 3>(U, negZ);
-    return;
-  }
-  const float rowreg = T[src_t];
-  const float d = readlane_f32(rowreg, 16 * src_g + K);
-  float inv = __builtin_amdgcn_rcpf(d);
-  const float rowk = bpermute_f32((16 * src_g + j) * 4, rowreg);
-  __builtin_amdgcn_sched_barrier(0);
-  la32_point<NT, PA, K, 0>(U, negZ);                       // covers v_rcp_f32 and the LDS round trip of the row broadcast
-  __builtin_amdgcn_sched_barrier(0);
-  inv = fmaf(inv, fmaf(-d, inv, 1.0f), inv);
-  asm volatile("v_fma_f32 %0, %1, 0, %0" : "+v"(bad) : "v"(inv));
-  float f[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) f[t] = row_bcast_f32<K>(T[t]);
-  __builtin_amdgcn_sched_barrier(0);
-  la32_point<NT, PA, K, 1>(U, negZ);
-  __builtin_amdgcn_sched_barrier(0);
-  float rk = rowk * inv;
-  masked_set_neg_f32<mcol>(rk, inv);
-  masked_zero4_f32<mcol>(T);
-  __builtin_amdgcn_sched_barrier(0);
-  la32_point<NT, PA, K, 2>(U, negZ);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int t = 0; t < 4; ++t) T[t] = fmaf(-f[t], rk, T[t]);
-  float rowk_new = T[src_t];
-  masked_set_f32<mrow>(rowk_new, rk);
-  T[src_t] = rowk_new;
-  __builtin_amdgcn_sched_barrier(0);
-  la32_point<NT, PA, K, 3>(U, negZ);
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int NT, int PA, int K> struct SweepWithWork32 {
-  static __device__ inline void run(f4 (&U)[(NT + 2) * (NT + 2)], f4& negZ, float& bad, int npiv, int j) {
-    sweep_step_work_f32<NT, PA, K>(U, negZ, bad, K < npiv, j);
-    SweepWithWork32<NT, PA, K + 1>::run(U, negZ, bad, npiv, j);
-  }
-};
-template <int NT, int PA> struct SweepWithWork32<NT, PA, 16> {
-  static __device__ inline void run(f4 (&)[(NT + 2) * (NT + 2)], f4&, float&, int, int) {
-    static_assert(la32_count<NT>(PA) <= 16 * la32_per_pivot<NT>(PA), "work items per pivot");
-  }
-};
-template <int NT, int PA> struct LookAheadSteps32 {
-  static __device__ inline void run(f4 (&U)[(NT + 2) * (NT + 2)], float& bad, int k, int j) {
-    constexpr int NB = NT + 2;
-    // the column of the next diagonal tile first
-    f4 negZ = mfma4_f32(U[PA * NB + PA], U[PA * NB + PA + 1], f4{0.0f, 0.0f, 0.0f, 0.0f});
-    U[(PA + 1) * NB + PA + 1] = mfma4_f32(U[PA * NB + PA + 1], negZ, U[(PA + 1) * NB + PA + 1]);
-    __builtin_amdgcn_sched_barrier(0);
-    SweepWithWork32<NT, PA, 0>::run(U, negZ, bad, PA + 1 < NT ? 16 : k, j);
-    if constexpr (PA + 1 < NT) LookAheadSteps32<NT, PA + 1>::run(U, bad, k, j);
-  }
-};
-// (block step NT -- the y tile -- has no update left: the back-substitution applies its swept tile itself)
-template <int NT>
-__device__ inline bool block_eliminate_lookahead_f32(f4 (&U)[(NT + 2) * (NT + 2)], int k, int j) {
-  float bad = 0.0f;
-  SweepLoop32<0, 16>::run(U[0], bad, 16, j);
-  __builtin_amdgcn_sched_barrier(0);
-  LookAheadSteps32<NT, 0>::run(U, bad, k, j);
   return bad == 0.0f;
 }
 
@@ -611,9 +484,6 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
     __builtin_amdgcn_sched_barrier(0);
     MO_STAMP32(2);
     bool ok = true;
-#if MO_F32_LOOKAHEAD
-    ok = block_eliminate_lookahead_f32<NT>(U, k, j);
-#else
 #pragma unroll
     for (int pa = 0; pa <= NT; ++pa) {
 #if MO_F32_RHS_VECTOR
@@ -657,7 +527,6 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
 #endif
       MO_STAMP32(4);
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     MO_STAMP32(4);
 
@@ -1704,62 +1573,38 @@ hipError_t launch_fused_f32(const KernelArgs& a_in, int num_cus, hipStream_t str
   // The work counter is zeroed on the stream in front of the kernel -- unless the launch is certain to run in static rounds, which never touch
   // it: every kernel below has at least 4 waves per workgroup and min(CUs, ceil(batch / 4)) workgroups, so batch <= rounds x 4 x workgroups
   // is static whatever the instantiation (the kernels test batch <= rounds x waves).  One enqueued operation less per small launch.
-  {
-    long long wgs = (a.batch + 3) / 4;
-    if (wgs > num_cus) wgs = num_cus;
-    const bool surely_static = a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * 4 * wgs;
-    if (!surely_static) {
-      hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), stream);
-      if (e != hipSuccess) return e;
-    }
+  if (!(a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * 4 * fused_grid(a.batch, num_cus))) {
+    hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return e;
   }
-  if (a.mode == MODE_LINEARIZE) {
-    long long grid = num_cus;   // (two waves per SIMD at n = 128, three at n = 64)
-    const long long need = (a.batch + 3) / 4;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    if (a.n > 64) hipLaunchKernelGGL((kkt_fused_f32_linearize_kernel<8, 2>), dim3((unsigned)grid), dim3(512), 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f32_linearize_kernel<4, 3>), dim3((unsigned)grid), dim3(768), 0, stream, a);
+  const dim3 grid(fused_grid(a.batch, num_cus));
+  if (a.mode == MODE_LINEARIZE) {  // (two waves per SIMD at n = 128, three at n = 64)
+    if (a.n > 64) hipLaunchKernelGGL((kkt_fused_f32_linearize_kernel<8, 2>), grid, dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL((kkt_fused_f32_linearize_kernel<4, 3>), grid, dim3(768), 0, stream, a);
     return hipGetLastError();
   }
   if (a.mode != MODE_STEP) {  // Solve / Iterate / KKT residual: one wave per SIMD at n = 128 (216 tile registers + the state), three at n = 64
-    long long grid = num_cus;
-    const long long need = (a.batch + 3) / 4;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    if (a.n > 64) { if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<8, 1, false>), dim3((unsigned)grid), dim3(256), 0, stream, a); else hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<8, 1, true>), dim3((unsigned)grid), dim3(256), 0, stream, a); }
-    else { if (a.n == 64) hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<4, 3, false>), dim3((unsigned)grid), dim3(768), 0, stream, a); else hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<4, 3, true>), dim3((unsigned)grid), dim3(768), 0, stream, a); }
+    if (a.n > 64) { if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<8, 1, false>), grid, dim3(256), 0, stream, a); else hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<8, 1, true>), grid, dim3(256), 0, stream, a); }
+    else { if (a.n == 64) hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<4, 3, false>), grid, dim3(768), 0, stream, a); else hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<4, 3, true>), grid, dim3(768), 0, stream, a); }
     return hipGetLastError();
   }
 #ifdef MO_TUNING
   if (a.n > 64 && env_wps == 1) {
     constexpr int WPS = 1;
-    long long grid = num_cus;
-    const long long need = (a.batch + 3) / 4;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, false>), dim3((unsigned)grid), dim3(256 * WPS), 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, true>), dim3((unsigned)grid), dim3(256 * WPS), 0, stream, a);
+    if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, false>), grid, dim3(256 * WPS), 0, stream, a);
+    else hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, true>), grid, dim3(256 * WPS), 0, stream, a);
   } else
 #else
   (void)env_wps;
 #endif
   if (a.n > 64) {
     constexpr int WPS = 2;  // 255 VGPRs, no scratch: the 216 accumulator registers + operands just fit two waves per SIMD
-    long long grid = num_cus;
-    const long long need = (a.batch + 3) / 4;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, false>), dim3((unsigned)grid), dim3(256 * WPS), 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, true>), dim3((unsigned)grid), dim3(256 * WPS), 0, stream, a);
+    if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, false>), grid, dim3(256 * WPS), 0, stream, a);
+    else hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, true>), grid, dim3(256 * WPS), 0, stream, a);
   } else {
     constexpr int WPS = 3;
-    long long grid = num_cus;
-    const long long need = (a.batch + 3) / 4;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    if (a.n == 64) hipLaunchKernelGGL((kkt_fused_f32_kernel<4, WPS, false>), dim3((unsigned)grid), dim3(256 * WPS), 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f32_kernel<4, WPS, true>), dim3((unsigned)grid), dim3(256 * WPS), 0, stream, a);
+    if (a.n == 64) hipLaunchKernelGGL((kkt_fused_f32_kernel<4, WPS, false>), grid, dim3(256 * WPS), 0, stream, a);
+    else hipLaunchKernelGGL((kkt_fused_f32_kernel<4, WPS, true>), grid, dim3(256 * WPS), 0, stream, a);
   }
   return hipGetLastError();
 }

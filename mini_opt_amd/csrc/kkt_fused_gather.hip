@@ -5,44 +5,24 @@
 #include "kkt_fused.hip"
 
 namespace mo {
-
-hipError_t launch_fused_gather(const KernelArgs& a, int num_cus, hipStream_t stream) {  // the work counter has been zeroed by launch_fused
-  const bool solve = a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL;
-  const int grid_tile = a.n > 96 ? 8 : a.n > 64 ? 6 : a.n > 32 ? 4 : 2;
-  // waves per SIMD: the register budgets of the fast-path instantiations
-  // (the 32 grid's step kernel runs four waves per SIMD since round 4, as its packed sibling does: 105 VGPRs)
-  const bool step32 = !solve && a.mode != MODE_LINEARIZE && grid_tile == 2;
-  const int wps = solve ? (grid_tile == 2 ? 3 : grid_tile == 4 ? 2 : 1) : (step32 ? 4 : grid_tile == 2 || grid_tile == 4 ? 3 : grid_tile == 6 ? 2 : 1);
-  long long grid = num_cus;
-  const long long need = (a.batch + 3) / 4;
-  if (grid > need) grid = need;
-  if (grid < 1) grid = 1;
-  const dim3 gd((unsigned)grid), bd(256 * wps);
-  if (a.mode == MODE_LINEARIZE) {  // mo_linearize / mo_fill_qp with column-major, strided, unaligned J or odd n
-    switch (grid_tile) {
-      case 2: hipLaunchKernelGGL((kkt_fused_linearize_kernel<2, 3, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      case 4: hipLaunchKernelGGL((kkt_fused_linearize_kernel<4, 3, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      case 6: hipLaunchKernelGGL((kkt_fused_linearize_kernel<6, 2, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      default: hipLaunchKernelGGL((kkt_fused_linearize_kernel<8, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-    }
-    return hipGetLastError();
-  }
-  if (solve) {
-    switch (grid_tile) {
-      case 2: hipLaunchKernelGGL((kkt_fused_solve_kernel<2, 3, 3, false, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      case 4: hipLaunchKernelGGL((kkt_fused_solve_kernel<4, 2, 3, false, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      case 6: hipLaunchKernelGGL((kkt_fused_solve_kernel<6, 1, 3, false, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      default: hipLaunchKernelGGL((kkt_fused_solve_kernel<8, 1, 3, false, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-    }
-  } else {
-    switch (grid_tile) {
-      case 2: hipLaunchKernelGGL((kkt_fused_f64_kernel<2, 4, 3, false, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      case 4: hipLaunchKernelGGL((kkt_fused_f64_kernel<4, 3, 3, false, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      case 6: hipLaunchKernelGGL((kkt_fused_f64_kernel<6, 2, 3, false, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-      default: hipLaunchKernelGGL((kkt_fused_f64_kernel<8, 1, 3, false, 1, JMODE_GATHER>), gd, bd, 0, stream, a); break;
-    }
-  }
-  return hipGetLastError();
-}
+namespace {
+constexpr int kUnit = UNIT_GATHER;
+// waves per SIMD: the register budgets of the fast-path instantiations (fused_wps); one constraint slot per lane
+const FusedRow kRows[] = {
+    MO_FUSED_ROW(FUSED_LINEARIZE, 2, 3, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_LINEARIZE, 4, 3, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_LINEARIZE, 6, 2, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_LINEARIZE, 8, 1, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 2, 4, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 3, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 6, 2, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 8, 1, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 2, 3, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 6, 1, false, 1, JMODE_GATHER, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 8, 1, false, 1, JMODE_GATHER, 1, true),
+};
+}  // namespace
+FusedTable fused_table_gather() { return {kRows, MO_FUSED_TABLE_SIZE(kRows)}; }
 
 }  // namespace mo

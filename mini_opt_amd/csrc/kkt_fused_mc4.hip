@@ -7,38 +7,32 @@
 #include "kkt_fused.hip"
 
 namespace mo {
-
-hipError_t launch_fused_mc4(const KernelArgs& a, int num_cus, hipStream_t stream) {  // the work counter has been zeroed by launch_fused
-  const bool solve = a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL;
-  const int grid_tile = a.n > 96 ? 8 : a.n > 64 ? 6 : a.n > 32 ? 4 : 2;
-  const int wps = grid_tile == 2 ? 3 : grid_tile == 4 ? 2 : 1;
-  long long grid = num_cus;
-  const long long need = (a.batch + 3) / 4;
-  if (grid > need) grid = need;
-  if (grid < 1) grid = 1;
-  const dim3 gd((unsigned)grid), bd(256 * wps);
-#define MO_MC(KERNEL, NT_, WPS_, MC_)                                                                  \
-  do {                                                                                                 \
-    if (a.J) hipLaunchKernelGGL((KERNEL<NT_, WPS_, 3, false, MC_>), gd, bd, 0, stream, a);             \
-    else hipLaunchKernelGGL((KERNEL<NT_, WPS_, 3, true, MC_>), gd, bd, 0, stream, a);                  \
-  } while (0)
-  if (solve) {
-    switch (grid_tile) {
-      case 2: MO_MC(kkt_fused_solve_kernel, 2, 3, 4); break;
-      case 4: MO_MC(kkt_fused_solve_kernel, 4, 2, 4); break;
-      case 6: if (a.m > 128) MO_MC(kkt_fused_solve_kernel, 6, 1, 4); else MO_MC(kkt_fused_solve_kernel, 6, 1, 2); break;
-      default: if (a.m > 128) MO_MC(kkt_fused_solve_kernel, 8, 1, 4); else MO_MC(kkt_fused_solve_kernel, 8, 1, 2); break;
-    }
-  } else {
-    switch (grid_tile) {
-      case 2: MO_MC(kkt_fused_f64_kernel, 2, 3, 4); break;
-      case 4: MO_MC(kkt_fused_f64_kernel, 4, 2, 4); break;
-      case 6: MO_MC(kkt_fused_f64_kernel, 6, 1, 4); break;
-      default: MO_MC(kkt_fused_f64_kernel, 8, 1, 4); break;
-    }
-  }
-#undef MO_MC
-  return hipGetLastError();
-}
+namespace {
+constexpr int kUnit = UNIT_MC4;
+// four slots on every grid; the Solve kernel with two on the 96 / 128 grids
+const FusedRow kRows[] = {
+    MO_FUSED_ROW(FUSED_STEP, 2, 3, false, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 2, 3, true, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 2, false, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 4, 2, true, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 6, 1, false, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 6, 1, true, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 8, 1, false, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_STEP, 8, 1, true, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 2, 3, false, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 2, 3, true, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, false, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 4, 2, true, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 6, 1, false, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 6, 1, true, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 6, 1, false, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 6, 1, true, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 8, 1, false, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 8, 1, true, 2, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 8, 1, false, 4, JMODE_VECTOR, 1, true),
+    MO_FUSED_ROW(FUSED_SOLVE, 8, 1, true, 4, JMODE_VECTOR, 1, true),
+};
+}  // namespace
+FusedTable fused_table_mc4() { return {kRows, MO_FUSED_TABLE_SIZE(kRows)}; }
 
 }  // namespace mo

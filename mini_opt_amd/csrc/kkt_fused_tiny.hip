@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_tiny_kernel(const KernelAr
       }
       lds_fence();
       __builtin_amdgcn_sched_barrier(0);
-      if (!sweep_tile<3>(T, P, g, j)) { st = MO_STATUS_FACTORIZATION_FAILED; break; }
+      if (!sweep_tile(T, P, g, j)) { st = MO_STATUS_FACTORIZATION_FAILED; break; }
       {  // the solution sits in column 15 of the swept tile: element (q, 15) at lane (q & 3, 15), register q >> 2
         double v = 0.0;
         const int src = (16 * (j & 3) + kRC) * 4;
@@ -450,23 +450,17 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_tiny_kernel(const KernelAr
   }
 }
 
+template <int WPS> struct FusedKernelOf<FUSED_TINY, 1, WPS, false, 1, JMODE_VECTOR, 1, true> {
+  static constexpr FusedKernel kernel = kkt_tiny_kernel<WPS>;
+};
+constexpr int kUnit = UNIT_TINY;
+// one workgroup of 12 waves per CU (145 VGPRs: three waves per SIMD; four would spill)
+const FusedRow kRows[] = {
+    MO_FUSED_ROW(FUSED_TINY, 1, 3, false, 1, JMODE_VECTOR, 1, true),
+};
+
 }  // namespace
 
-bool fused_tiny_supported(const KernelArgs& a) {  // the caller has run fused_supported() on the same arguments
-  if (a.mode == MODE_LINEARIZE || a.no_tiny) return false;
-  if (a.n + a.k > 15 || a.m > 64) return false;
-  if (a.J && a.m_r > 64) return false;  // larger stacks: the 32-variable grid streams J through the matrix cores
-  return true;
-}
-
-hipError_t launch_fused_tiny(const KernelArgs& a, int num_cus, hipStream_t stream) {  // the work counter has been zeroed by launch_fused
-  constexpr int WPS = 3;
-  long long grid = num_cus;        // one workgroup of 12 waves per CU (145 VGPRs: three waves per SIMD; four would spill)
-  const long long need = (a.batch + 4 * WPS - 1) / (4 * WPS);
-  if (grid > need) grid = need;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((kkt_tiny_kernel<WPS>), dim3((unsigned)grid), dim3(256 * WPS), 0, stream, a);
-  return hipGetLastError();
-}
+FusedTable fused_table_tiny() { return {kRows, MO_FUSED_TABLE_SIZE(kRows)}; }
 
 }  // namespace mo

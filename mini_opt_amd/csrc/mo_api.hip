@@ -10,6 +10,7 @@
 #include <new>
 #include <vector>
 
+#include "mo_fused_select.h"
 #include "mo_kernels.h"
 
 namespace {

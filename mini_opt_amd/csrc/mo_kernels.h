@@ -55,7 +55,7 @@ struct KernelArgs {
   long long skip_active;  // how many of them are still active (host-side count from the previous outer iteration; -1: unknown)
   // fused kernel: device work counter (plan-owned, zeroed on the launch stream before every launch)
   unsigned long long* ticket;
-  int stagger;     // fused step kernel: start offset between the waves that share a SIMD, in units of 127 x 64 cycles (set by launch_fused)
+  int stagger;     // fused step kernel: start offset between the waves that share a SIMD, in units of 127 x 64 cycles (set by launch_fused from fused_select)
   int chain_prio;  // fused step kernel: s_setprio 1 while a wave is in the elimination / substitution chains
   int static_rounds;  // fused kernels: launches of at most this many problems per wave are split statically, round by round, with no ticket
                       // (mo_api.hip hands over -1 = "the launcher decides" or MO_FUSED_STATIC_ROUNDS; 0 = tickets always).  The grids are
@@ -94,18 +94,17 @@ int eig_grid(int n, int num_cus);
 hipError_t launch_qp_eig(const KernelArgs& a, int dtype, int num_cus, void* out, long long out_stride, void* work, size_t work_slot_bytes,
                          long long work_slots, hipStream_t stream);
 
-// fused single-wave MFMA kernels for fixed shapes, kkt_fused.hip.  Returns false if (shape, layout) is unsupported.
-bool fused_supported(const KernelArgs& a, int dtype);
-const char* fused_name(const KernelArgs& a, int dtype);
-hipError_t launch_fused(const KernelArgs& a, int dtype, int num_cus, hipStream_t stream);
-bool fused_needs_gather(const KernelArgs& a);  // J-level input in a layout only the per-lane gather stream takes
-hipError_t launch_fused_gather(const KernelArgs& a, int num_cus, hipStream_t stream);  // kkt_fused_gather.hip
-hipError_t launch_fused_ny2(const KernelArgs& a, int num_cus, hipStream_t stream);     // kkt_fused_ny2.hip: 16 <= k <= 31
-hipError_t launch_fused_ny34(const KernelArgs& a, int num_cus, hipStream_t stream);    // kkt_fused_ny34.hip: 32 <= k <= 63 on the 32 / 64 grids
-hipError_t launch_fused_mc4(const KernelArgs& a, int num_cus, hipStream_t stream);     // kkt_fused_mc4.hip: 128 < m <= 256; Solve with m > 64 on the 96 / 128 grids
-bool fused_tiny_supported(const KernelArgs& a);                                          // kkt_fused_tiny.hip: n + k <= 15, m <= 64 (a subset of fused_supported)
-hipError_t launch_fused_tiny(const KernelArgs& a, int num_cus, hipStream_t stream);
+// min(CUs, ceil(batch / problems_per_wg)) workgroups of a persistent grid, so that a small batch spreads one wave per SIMD over the CUs
+// before any SIMD gets a second wave (static_rounds above).  The one formula of every fused launcher, fp32 included.
+inline unsigned fused_grid(long long batch, int num_cus, int problems_per_wg = 4) {
+  long long grid = num_cus;
+  const long long need = (batch + problems_per_wg - 1) / problems_per_wg;
+  if (grid > need) grid = need;
+  if (grid < 1) grid = 1;
+  return (unsigned)grid;
+}
 
+// fused single-wave MFMA kernels for fixed tile grids (fp64): mo_fused_select.h
 
 // fused single-wave fp32 step kernel for n = 64 / 128 (J-level input), kkt_fused_f32.hip
 bool fused_f32_supported(const KernelArgs& a, int dtype);

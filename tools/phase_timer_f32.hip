@@ -1,6 +1,6 @@
 // phase_timer_f32.hip -- DIAGNOSTIC build of the fp32 fused step kernel with s_memtime stamps at the phase boundaries (never shipped: the
 // product library is built without MO_F32_STAMPS).  Prints the share of wave time per phase at BASELINE configs[3] (n = 128 / 16 / 64, m_r = 256).
-// build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -mllvm -amdgpu-function-calls=false -DMO_F32_STAMPS -DMO_F32_LOOKAHEAD=0 \
+// build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -mllvm -amdgpu-function-calls=false -DMO_F32_STAMPS \
 //        tools/phase_timer_f32.hip -o tools/phase_timer_f32        usage: tools/phase_timer_f32 [batch] [waves per SIMD: 1 | 2]
 #include "../mini_opt_amd/csrc/kkt_fused_f32.hip"
 

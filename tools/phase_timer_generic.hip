@@ -1,6 +1,6 @@
 // phase_timer_generic.hip [n batch k m m_r] -- DIAGNOSTIC build of the generic kernel (LDS-resident and LARGE) with s_memtime stamps at phase boundaries (never shipped:
-// the product library is built without MO_FUSED_STAMPS).  Prints the share of wave time per phase.
-// build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -DMO_FUSED_STAMPS tools/phase_timer.hip -o tools/phase_timer
+// the product library is built without MO_GENERIC_STAMPS).  Prints the share of wave time per phase.
+// build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -DMO_GENERIC_STAMPS tools/phase_timer_generic.hip -o tools/phase_timer_generic
 #include "../mini_opt_amd/csrc/kkt_fused.hip"
 #include "../mini_opt_amd/csrc/kkt_generic.hip"
 

@@ -151,6 +151,9 @@ int mo_plan_destroy(mo_plan* plan);
 const char* mo_plan_step_kernel(const mo_plan* plan, const mo_problem* prob);
 /* The same for mo_qp_solve / mo_iterate / mo_kkt_residual ("generic", "fused_solve_mfma_f64_n64", "fused_solve_mfma_f32_n128", ...). */
 const char* mo_plan_solve_kernel(const mo_plan* plan, const mo_problem* prob);
+/* The same for mo_kkt_solve: "generic", or the right-hand-side twin of the fused fp64 step kernel, "fused_rhs_mfma_f64_n32|64|96|128" for
+ * J-level and "fused_rhs_qp_f64_n32|64|96|128" for (G, c) input (the coverage rule stands above mo_kkt_solve). */
+const char* mo_plan_kkt_solve_kernel(const mo_plan* plan, const mo_problem* prob);
 
 /* Replaces LinearizeAndFillQP's cost part (nonlinear.cc:182-189; Residual::Model::UpdateHessian, residual.hpp:186-226):
  * G_out (n x n col-major, leading dim G_ld; lower triangle written, strict upper written as 0) = J^T J + lambda I,
@@ -416,9 +419,14 @@ int mo_nls_solve_blocks(mo_plan* plan, const mo_nls_problem* np, const mo_residu
  *   MO_KKT_TRANSPOSE          out = u with K^T u = rhs: the kernel solves K delta = -[-g_x | -s o g_s | g_y | g_z] and returns
  *                             [delta_x | delta_s / s | -delta_y | -delta_z], so the adjoint shares the factorisation code of the step.
  *   MO_STEP_NO_INEQUALITIES   as in the Newton step: the system of [x | y] alone; the s and z blocks of rhs are ignored and written as 0.
- * rhs, out: [batch][V]; rhs may alias neither vars nor out.  J-level and (G, c) input are both accepted.  The call always runs the
- * shape-generic kernel, whatever the plan would pick for a step: the fused kernels take no right-hand side (a run-time branch there would
- * cost registers in every one of their instantiations).  No allocation and no synchronisation on the launch path. */
+ * rhs, out: [batch][V], 8-byte aligned; rhs may alias neither vars nor out.  J-level and (G, c) input are both accepted.
+ * Which kernel runs (mo_plan_kkt_solve_kernel tells): the right-hand-side twin of the fused fp64 step kernel -- the step's template
+ * instantiated with a compile-time right-hand-side mode, in a translation unit of its own, so that no step or Solve instantiation pays a
+ * register for it -- where ALL of these hold: fp64; 2 <= n <= 128; k <= 31; m <= 128; input (G, c), or a J the 16-byte vector stream
+ * takes (packed row-major with J_ld = n, even n, 16-byte aligned, even stride); not a shape whose step runs the one-tile kernel (n + k <= 15,
+ * m <= 64, J-level: m_r <= 64; none with MO_PLAN_NO_TINY); no MO_PLAN_FORCE_GENERIC.  Every other call runs the shape-generic kernel.  The two kernels agree to
+ * rounding (same reduced system, different elimination order); only on the generic kernel is the flags = 0 result bit for bit the Newton
+ * direction of that kernel's step.  No allocation and no synchronisation on the launch path: at most an 8-byte memset and one kernel. */
 int mo_kkt_solve(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* rhs,
                  int64_t rhs_stride, uint32_t flags, void* out, int64_t out_stride, int32_t* status, void* stream);
 

@@ -334,6 +334,7 @@ class BatchedQPInteriorPointSolver {
     detail::check(mo_qp_solve(plan_, &prob, batch, &params, vars, vars_stride, termination, num_iterations, iterations, lagrange, status, stream));
   }
   const char* StepKernel(const mo_problem& prob) const { return mo_plan_step_kernel(plan_, &prob); }
+  const char* KktSolveKernel(const mo_problem& prob) const { return mo_plan_kkt_solve_kernel(plan_, &prob); }
   mo_plan* plan() const { return plan_; }
  private:
   mo_plan* plan_{nullptr};

@@ -935,13 +935,14 @@ __device__ inline void solve_second_rhs(const d4 (&U)[(NT + NY) * (NT + NY)], in
 // NT = n / 16 (2 or 4), WPS = waves per SIMD the register budget is sized for.  k <= 15 (index 15 of the y tile carries the right-hand side), m <= 64 MC are
 // checked by fused_supported().
 // MC = constraint slots per lane (m <= 64 MC).
-template <int NT, int WPS, int MC = 1, int NY = 1> struct FusedCfg {
+template <int NT, int WPS, int MC = 1, int NY = 1, bool RHS = false> struct FusedCfg {
   static constexpr int N = 16 * NT;
   static constexpr int NH = NT / 2;                 // 16-byte J loads per lane per 4-row group
   static constexpr int DPS = NH + 1;                // LDS-DMA instructions per 4-row group (J pieces + 32 B of r)
   static constexpr int SLOT = NH * 1024 + 64;       // ring slot: 4 rows of J (lane-linear) + r[4s..4s+3]
   static constexpr int MCAP = 64 * MC;
-  static constexpr int VEC = (3 * N + 4 * MCAP + MCAP / 2 + 32 * NY) * 8;  // xs, diagS|rp, rhsS|dxs, cons a/b/s/z, cons var (int), y[16 NY], b_eq[16 NY]
+  // xs, diagS|rp, rhsS|dxs, cons a/b/s/z, cons var (int), y[16 NY], b_eq[16 NY]; the right-hand-side mode: one more constraint vector (rho_pi)
+  static constexpr int VEC = (3 * N + 4 * MCAP + MCAP / 2 + 32 * NY + (RHS ? MCAP : 0)) * 8;
   static constexpr int D_FIT = ((160 * 1024) / (4 * WPS) - VEC) / SLOT;  // what the 160 KiB of a CU leave per wave
   static constexpr int D_TUNED = NT > 4 ? 4 : (NT == 4 ? (WPS >= 3 ? 4 : 7) : (WPS >= 4 ? 4 : 8));
   static constexpr int D = MC == 1 ? D_TUNED : (D_FIT > 8 ? 8 : D_FIT);  // ring depth (4-row groups in flight per wave), LDS-limited
@@ -951,9 +952,18 @@ template <int NT, int WPS, int MC = 1, int NY = 1> struct FusedCfg {
 
 // One workgroup of 4*WPS independent waves per CU (so that exactly WPS waves sit on every SIMD).  The waves never
 // synchronise with each other; each owns its slice of the workgroup's LDS.
-template <int NT, int WPS, bool QPL, int MC = 1, int JMODE = JMODE_VECTOR, int NY = 1>
+//
+// RHS = true (kkt_fused_rhs.hip; mo_kkt_solve): the same matrix for the CALLER's right-hand side rho = [rho_d(n) | rho_comp(m) | rho_pe(k) |
+// rho_pi(m)] (a.rhs) instead of the KKT residual -- qp.cc:318-364 with r_ := rho, mu = 0.  P0 .. P6 are the step's; rho rides in the LDS slots
+// of the vectors this mode does not need (rho_d: x, rho_comp: cons_b, rho_pe: b_eq; rho_pi has a slot of its own), J^T r is not formed, and
+//   rhs_x[v] = -rho_d[v] - sum_{i on v} a_i (rho_comp_i + z_i rho_pi_i) / s_i,   equality rows -rho_pe,
+// so that the solution is [delta_x; -delta_y] itself; ds_i = a_i dx[var_i] + rho_pi_i, dz_i = -(rho_comp_i + z_i ds_i) / s_i, no alpha.
+// MO_KKT_TRANSPOSE: K^T u = g is K delta = -rho with rho = [-g_x | -s o g_s | g_y | g_z] and u = [dx | ds / s | -dy | -dz] (kkt_generic.hip MODE_RHS).
+// A compile-time mode: with RHS = false the kernel is instruction for instruction what it was before the parameter existed.
+template <int NT, int WPS, bool QPL, int MC = 1, int JMODE = JMODE_VECTOR, int NY = 1, bool RHS = false>
 __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const KernelArgs a) {
-  using C = FusedCfg<NT, WPS, MC, NY>;
+  static_assert(!RHS || JMODE == JMODE_VECTOR, "the right-hand-side mode exists on the 16-byte stream and for (G, c) only");
+  using C = FusedCfg<NT, WPS, MC, NY, RHS>;
   constexpr int MCAP = C::MCAP;
   constexpr int N = C::N, NB = NT + NY, LT = NB - 1, SLOT = C::SLOT, D = C::D;  // LT: the tile column that carries the right-hand side
   constexpr int WAVES = 4 * WPS;
@@ -974,6 +984,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
   int* const cV = reinterpret_cast<int*>(cZ + MCAP);
   double* const yb = cZ + MCAP + MCAP / 2;
   double* const bb = yb + 16 * NY;
+  double* const cP = bb + 16 * NY;                                // RHS: rho_pi per constraint
   const unsigned ring_base = (unsigned)(uintptr_t)smem;           // LDS byte address of the ring (low 32 bits of the flat address)
   const unsigned vec_base = ring_base + D * SLOT;                 // LDS byte address of xs
 
@@ -983,6 +994,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
   const bool no_ineq = (a.flags & MO_STEP_NO_INEQUALITIES) != 0;
   const int k = a.k, m = no_ineq ? 0 : a.m, m_r = a.m_r;
   const int nn = a.n;  // actual number of variables <= N; the system is padded to whole tiles (unit diagonal, zero solution)
+  const bool transpose = RHS && (a.flags & MO_KKT_TRANSPOSE) != 0;
   // Once per wave: the ring (lanes whose J piece lies beyond the row never receive DMA data and must read zeros) and x's padding.
   for (int i = (int)(threadIdx.x & 63); i < D * SLOT / 8; i += 64) reinterpret_cast<double*>(smem)[i] = 0.0;
   for (int i = (int)(threadIdx.x & 63); i < N; i += 64) xs[i] = 0.0;
@@ -1051,11 +1063,13 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
     const int g = lane >> 4, j = lane & 15;
 
     const double* Jp = QPL ? nullptr : (const double*)a.J + p * a.J_stride;
-    const double* rg = QPL ? nullptr : (const double*)a.r + p * a.r_stride;
+    // (RHS: J^T r is not formed; the stream's 32 bytes of "r" per 4-row group are taken from the head of J itself and feed nothing)
+    const double* rg = QPL ? nullptr : RHS ? Jp : (const double*)a.r + p * a.r_stride;
     // Everything but the J stream's own operands is re-read from the kernarg segment where it is used (scalar loads, K$
     // hits): held in SGPRs for the whole kernel they overflow the SGPR file and come back as v_readlane VALU work.
     KArgs ka = fresh_args();
     const double* vp = (const double*)ka->vars + p * ka->vars_stride;
+    const double* gp = RHS ? (const double*)ka->rhs + p * ka->rhs_stride : nullptr;   // rho (or g), laid out as the state
 
     // The ring is filled FIRST: the J stream's memory latency then overlaps the address arithmetic and the small loads of P0.
     JStream<NT, D, JMODE, NY> stream;
@@ -1070,7 +1084,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
     d4 U[NB * NB];
 #pragma unroll
     for (int q = 0; q < NB * NB; ++q) U[q] = d4{0.0, 0.0, 0.0, 0.0};
-    dma_doubles(vp, vec_base, nn, lane);                                                    // x -> xs
+    dma_doubles(RHS ? gp : vp, vec_base, nn, lane);                                         // x (RHS: rho_d) -> xs
     if (m > 0) {
       const long long coff = p * ka->cons_stride;
       if (lane < m) dma4_s(ka->cons_var + coff, 4u * (unsigned)lane, vec_base + (3 * N + 4 * MCAP) * 8);
@@ -1078,13 +1092,18 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
       for (int ci = 1; ci < MC; ++ci)
         if (lane + 64 * ci < m) dma4_s(ka->cons_var + coff + 64 * ci, 4u * (unsigned)lane, vec_base + (3 * N + 4 * MCAP) * 8 + 256 * ci);
       dma_doubles((const double*)ka->cons_a + coff, vec_base + (3 * N) * 8, m, lane);
-      dma_doubles((const double*)ka->cons_b + coff, vec_base + (3 * N + MCAP) * 8, m, lane);
+      if (RHS) {
+        dma_doubles(gp + nn, vec_base + (3 * N + MCAP) * 8, m, lane);                                           // rho_comp -> cB
+        dma_doubles(gp + nn + m + k, vec_base + (3 * N + 4 * MCAP + MCAP / 2 + 32 * NY) * 8, m, lane);          // rho_pi -> cP
+      } else {
+        dma_doubles((const double*)ka->cons_b + coff, vec_base + (3 * N + MCAP) * 8, m, lane);
+      }
       dma_doubles(vp + nn, vec_base + (3 * N + 2 * MCAP) * 8, m, lane);                      // s
       dma_doubles(vp + nn + m + k, vec_base + (3 * N + 3 * MCAP) * 8, m, lane);              // z
     }
     if (k > 0) {
-      dma_doubles(vp + nn + m_lay, vec_base + (3 * N + 4 * MCAP + MCAP / 2) * 8, k, lane);   // y
-      dma_doubles((const double*)ka->b + p * ka->b_stride, vec_base + (3 * N + 4 * MCAP + MCAP / 2 + 16 * NY) * 8, k, lane);  // b_eq
+      if (!RHS) dma_doubles(vp + nn + m_lay, vec_base + (3 * N + 4 * MCAP + MCAP / 2) * 8, k, lane);   // y
+      dma_doubles(RHS ? gp + nn + m_lay : (const double*)ka->b + p * ka->b_stride, vec_base + (3 * N + 4 * MCAP + MCAP / 2 + 16 * NY) * 8, k, lane);  // b_eq (RHS: rho_pe)
     }
     MO_STAMP(14);   // (diagnostic build) tile registers zeroed, small-vector DMAs issued
     // tile column NT = [A_eq^T | rhs] (rhs is merged in after P3); y diagonal tile = [0, -b_eq; -b_eq^T, 0]
@@ -1120,12 +1139,17 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
       rhsS[2 * lane] = 0.0; rhsS[2 * lane + 1] = 0.0;
     }
     int cvar[MC]; double ca[MC], cb[MC], cs[MC], cz[MC], cs_inv[MC];  // constraint lane + 64 ci
+    double cp[MC];                                                    // RHS: rho_pi (and cb: rho_comp)
     bool bad_index[MC];
 #pragma unroll
     for (int ci = 0; ci < MC; ++ci) {
       const int ix = lane + 64 * ci;
-      cvar[ci] = 0; ca[ci] = 1.0; cb[ci] = 0.0; cs[ci] = 1.0; cz[ci] = 0.0;
+      cvar[ci] = 0; ca[ci] = 1.0; cb[ci] = 0.0; cs[ci] = 1.0; cz[ci] = 0.0; cp[ci] = 0.0;
       if (ix < m) { cvar[ci] = cV[ix]; ca[ci] = cA[ix]; cb[ci] = cB[ix]; cs[ci] = cS[ix]; cz[ci] = cZ[ix]; }
+      if (RHS && ix < m) {
+        cp[ci] = cP[ix];
+        if (transpose) { cb[ci] = -(cs[ci] * cb[ci]); cB[ix] = cb[ci]; }   // rho_comp = -s o g_s, kept for P7
+      }
     }
     lds_fence();  // diagS / rhsS initialised
     bool lane_bad_slack = false, lane_bad_index = false;
@@ -1140,7 +1164,8 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
       if (ix < m) {
         const double zs = cz[ci] * cs_inv[ci];
         atomicAdd(&diagS[cvar[ci]], ca[ci] * zs * ca[ci]);                                  // qp.cc:296
-        atomicAdd(&rhsS[cvar[ci]], ca[ci] * (cz[ci] * (cs[ci] - cb[ci]) + mu) * cs_inv[ci]);  // x+ form of qp.cc:340-341
+        if (RHS) atomicAdd(&rhsS[cvar[ci]], -(ca[ci] * (cb[ci] + cz[ci] * cp[ci]) * cs_inv[ci]));  // qp.cc:340-341 with r_ := rho, mu = 0
+        else atomicAdd(&rhsS[cvar[ci]], ca[ci] * (cz[ci] * (cs[ci] - cb[ci]) + mu) * cs_inv[ci]);  // x+ form of qp.cc:340-341
       }
     }
     const bool slack_bad = __any(lane_bad_slack);
@@ -1155,6 +1180,12 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
     double dS[NT], rS[NT];
     ldv<NT, QPL>(diagS, j, dS);
     ldv<NT, QPL>(rhsS, j, rS);
+    if (RHS) {   // -rho_d in the place of -c (transposed: rho_d = -g_x)
+      double rd[NT];
+      ldv<NT, QPL>(xs, j, rd);
+#pragma unroll
+      for (int c = 0; c < NT; ++c) cvec[c] = transpose ? -rd[c] : rd[c];
+    }
     if (g == 0) {
 #pragma unroll
       for (int c = 0; c < NT; ++c) rp[16 * c + j] = rS[c] - cvec[c];
@@ -1226,9 +1257,9 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
     double dxv[NT];
     {
       double xn[NT];
-      ldv<NT, QPL>(xs, j, xn);
+      if (!RHS) ldv<NT, QPL>(xs, j, xn);
 #pragma unroll
-      for (int c = 0; c < NT; ++c) dxv[c] = xb[c] - xn[c];
+      for (int c = 0; c < NT; ++c) dxv[c] = RHS ? xb[c] : xb[c] - xn[c];   // RHS: the solution is the direction itself
     }
     bool finite = true;
 #pragma unroll
@@ -1244,6 +1275,13 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
         const double ca2 = cA[ix], cb2 = cB[ix], cs2 = cS[ix], cz2 = cZ[ix];       // re-read: not kept live across P5
         const int cvar2 = bad_index[ci] ? 0 : cV[ix];
         const double csi = MC == 1 ? cs_inv[ci] : rcp_f64(cs2);                     // one slot: kept in a register; more: recomputed
+        if (RHS) {                                                                  // cb2: rho_comp
+          dsv[ci] = ca2 * dxs[cvar2] + cP[ix];                                      // qp.cc:361 with r_pi := rho_pi
+          dzv[ci] = -(cb2 + cz2 * dsv[ci]) * csi;                                   // qp.cc:362 with r_comp := rho_comp, mu = 0
+          finite = finite && (fabs(dsv[ci]) < INFINITY) && (fabs(dzv[ci]) < INFINITY);
+          if (transpose) { dsv[ci] *= csi; dzv[ci] = -dzv[ci]; }                    // u = [dx | ds / s | -dy | -dz]
+          continue;
+        }
         const double r_pi = ca2 * xs[cvar2] + cb2 - cs2;                            // qp.cc:416
         dsv[ci] = ca2 * dxs[cvar2] + r_pi;                                          // qp.cc:361
         dzv[ci] = -(cz2 * csi) * dsv[ci] - csi * (cs2 * cz2 - mu);                  // qp.cc:362
@@ -1253,12 +1291,15 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
         finite = finite && (fabs(dsv[ci]) < INFINITY) && (fabs(dzv[ci]) < INFINITY);
       }
     }
-    ap = cross_row_min(row_min(ap));
-    ad = cross_row_min(row_min(ad));
-    double dyv[NY];                                                                 // y+ - y, equality row 16 q + j
+    if (!RHS) {
+      ap = cross_row_min(row_min(ap));
+      ad = cross_row_min(row_min(ad));
+    }
+    double dyv[NY];                                                                 // y+ - y, equality row 16 q + j (RHS: dy; transposed -dy)
 #pragma unroll
     for (int q = 0; q < NY; ++q) {
-      dyv[q] = (16 * q + j < k) ? (-xb[NT + q] - yb[16 * q + j]) : 0.0;
+      if (RHS) dyv[q] = (16 * q + j < k) ? (transpose ? xb[NT + q] : -xb[NT + q]) : 0.0;
+      else dyv[q] = (16 * q + j < k) ? (-xb[NT + q] - yb[16 * q + j]) : 0.0;
       finite = finite && (fabs(dyv[q]) < INFINITY);
     }
     int st = MO_STATUS_OK;
@@ -1289,7 +1330,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
       }
     }
     if (lane == 0) {
-      if (ka->alpha) {
+      if (!RHS && ka->alpha) {
         ((double*)ka->alpha)[2 * p] = st == MO_STATUS_OK ? ap : nanv;
         ((double*)ka->alpha)[2 * p + 1] = st == MO_STATUS_OK ? ad : nanv;
       }

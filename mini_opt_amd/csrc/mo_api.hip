@@ -110,7 +110,7 @@ int fill_problem(const mo_plan* plan, const mo_problem* prob, int64_t batch, boo
 // Which kernel serves a call is decided ONCE, here, from the plan flags, the process-wide MO_FORCE_GENERIC knob (read a single
 // time: the scratch a call prepares and the kernel that consumes it must come from the same decision) and the kernels' own
 // shape predicates.
-enum KernelChoice { KERNEL_FUSED_F64, KERNEL_FUSED_F32, KERNEL_GENERIC };
+enum KernelChoice { KERNEL_FUSED_F64, KERNEL_FUSED_F32, KERNEL_GENERIC, KERNEL_FUSED_RHS_F64 };
 
 // The product library reads NO environment variable (the reference has none): kernel selection and scheduling follow the
 // plan flags of include/mini_opt_hip.h only.  The getenv knobs of the A/B scripts exist in builds with -DMO_TUNING (tools/ab_build.sh).
@@ -135,6 +135,8 @@ int fused_static_rounds(const mo_plan* plan) {
 }
 
 KernelChoice choose_kernel(const mo_plan* plan, const mo::KernelArgs& a) {
+  if (a.mode == mo::MODE_RHS)   // mo_kkt_solve: the step kernel's right-hand-side twin where one exists, the generic kernel everywhere else
+    return !generic_forced(plan) && mo::fused_rhs_supported(a, plan->desc.dtype) ? KERNEL_FUSED_RHS_F64 : KERNEL_GENERIC;
   if (!generic_forced(plan)) {
     if (mo::fused_supported(a, plan->desc.dtype)) return KERNEL_FUSED_F64;
     if (mo::fused_f32_supported(a, plan->desc.dtype)) return KERNEL_FUSED_F32;
@@ -152,6 +154,8 @@ int launch_chosen(const mo_plan* plan, const mo::KernelArgs& a_in, KernelChoice 
     MO_HIP_CHECK(mo::launch_fused(a, plan->desc.dtype, plan->num_cus, s));
   } else if (choice == KERNEL_FUSED_F32) {
     MO_HIP_CHECK(mo::launch_fused_f32(a, plan->num_cus, s));
+  } else if (choice == KERNEL_FUSED_RHS_F64) {
+    MO_HIP_CHECK(mo::launch_fused_rhs(a, plan->desc.dtype, plan->num_cus, s));
   } else {
     if (mo::generic_needs_large(a, plan->elem)) {  // H in a global workspace per workgroup: plan-owned, allocated by mo_plan_create
       const size_t need = mo::generic_large_lds_bytes(a, plan->elem);
@@ -364,6 +368,19 @@ const char* mo_plan_solve_kernel(const mo_plan* plan, const mo_problem* prob) {
   }
 }
 
+const char* mo_plan_kkt_solve_kernel(const mo_plan* plan, const mo_problem* prob) {
+  if (!plan || !prob) return "invalid";
+  mo::KernelArgs a;
+  if (fill_problem(plan, prob, 1, true, true, &a) != MO_OK) return "invalid";
+  a.mode = mo::MODE_RHS;
+  a.vars = a.delta = reinterpret_cast<void*>(16);  // layout query only: the state, right-hand side and output have no alignment rule
+  a.rhs = reinterpret_cast<const void*>(32);
+  a.vars_stride = a.delta_stride = a.rhs_stride = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
+  a.ticket = plan->ticket; a.static_rounds = fused_static_rounds(plan); a.no_tiny = (plan->desc.flags & MO_PLAN_NO_TINY) != 0;
+  if (choose_kernel(plan, a) == KERNEL_FUSED_RHS_F64) return mo::fused_rhs_name(mo::fused_rhs_select(a, 1).key);
+  return "generic";
+}
+
 int mo_linearize(mo_plan* plan, const mo_problem* prob, int64_t batch, void* G_out, int64_t G_stride, int32_t G_ld,
                  void* c_out, int64_t c_stride, void* half_sq_out, void* stream) {
   g_err[0] = 0;
@@ -545,8 +562,8 @@ int mo_kkt_solve(mo_plan* plan, const mo_problem* prob, int64_t batch, const voi
   a.vars = const_cast<void*>(vars); a.vars_stride = vars_stride;
   a.rhs = rhs; a.rhs_stride = rhs_stride;
   a.delta = out; a.delta_stride = out_stride; a.status = status;
-  // always the shape-generic kernel: the fused kernels take no caller right-hand side (include/mini_opt_hip.h)
-  return launch_chosen(plan, a, KERNEL_GENERIC, stream);
+  // one decision per call (choose_kernel): the step kernel's right-hand-side twin on the shapes fused_rhs_supported names, else the generic kernel
+  return launch(plan, a, stream);
 }
 
 int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* u,

@@ -241,4 +241,39 @@ static inline const char* fused_name(const KernelArgs& a, int) {
 
 hipError_t launch_fused(const KernelArgs& a, int dtype, int num_cus, hipStream_t stream);   // kkt_fused.hip
 
+// ---- the right-hand-side mode of the step kernel (mo_kkt_solve, MODE_RHS; kkt_fused_rhs.hip) ------------------------------------------
+// The RHS kernel of a shape is the twin of that shape's step kernel -- kkt_fused_f64_kernel<..., RHS = true> with the step's template
+// arguments, grid, block and scheduling values -- so everything here derives from fused_select of the same arguments in MODE_STEP.
+// The arguments a MODE_RHS call would hand to the step (MO_KKT_TRANSPOSE is the RHS kernel's own flag).
+inline KernelArgs fused_rhs_as_step(const KernelArgs& a) {
+  KernelArgs s = a;
+  s.mode = MODE_STEP;
+  s.flags = a.flags & ~(unsigned)MO_KKT_TRANSPOSE;
+  return s;
+}
+// Coverage: fp64 shapes whose step runs kkt_fused_f64_kernel (not the one-tile kernel) with one or two y tiles (k <= 31), one or two
+// constraint slots (m <= 128) and (G, c) or the 16-byte vector stream (packed row-major J, even n, 16-byte aligned, even stride).
+// Everything else -- flat and gather streams, k > 31, m > 128, one-tile shapes, fp32 -- stays on the generic kernel.
+inline bool fused_rhs_supported(const KernelArgs& a, int dtype) {
+  if (a.mode != MODE_RHS || !a.rhs) return false;
+  if (a.flags & ~(unsigned)(MO_STEP_NO_INEQUALITIES | MO_KKT_TRANSPOSE)) return false;
+  const KernelArgs s = fused_rhs_as_step(a);
+  if (!fused_supported(s, dtype)) return false;
+  if (a.k > 31 || a.m > 128) return false;
+  const FusedKey key = fused_select(s, 1).key;
+  return key.family == FUSED_STEP && key.jmode == JMODE_VECTOR && key.ny <= 2 && key.mc <= 2;
+}
+// The launch of supported arguments: the step's launch description, field for field.
+static inline FusedLaunch fused_rhs_select(const KernelArgs& a, int num_cus) { return fused_select(fused_rhs_as_step(a), num_cus); }
+// The kernel name the plan reports (mo_plan_kkt_solve_kernel).
+inline const char* fused_rhs_name(const FusedKey& k) {
+  static const char* const names[2][4] = {{"fused_rhs_mfma_f64_n32", "fused_rhs_mfma_f64_n64", "fused_rhs_mfma_f64_n96", "fused_rhs_mfma_f64_n128"},
+                                          {"fused_rhs_qp_f64_n32", "fused_rhs_qp_f64_n64", "fused_rhs_qp_f64_n96", "fused_rhs_qp_f64_n128"}};
+  return names[k.qpl][k.nt / 2 - 1];
+}
+// Rows {the STEP kernel's key, kkt_fused_f64_kernel<..., RHS = true>}.  Not one of the FUSED_UNITS tables: it is reached through this
+// function only, and a supported key without a row is an error (launch_fused_rhs), never another kernel.
+FusedTable fused_rhs_table();                                                                    // kkt_fused_rhs.hip
+hipError_t launch_fused_rhs(const KernelArgs& a, int dtype, int num_cus, hipStream_t stream);   // kkt_fused_rhs.hip
+
 }  // namespace mo

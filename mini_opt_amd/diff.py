@@ -63,6 +63,13 @@ def kkt_solve(problem: BatchedQP, vars: torch.Tensor, rhs: torch.Tensor, transpo
     return out, status
 
 
+def kkt_solve_kernel(problem: BatchedQP, batch: int) -> str:
+    """mo_plan_kkt_solve_kernel: the kernel kkt_solve (and the backward of solve_qp) launches for this problem's shape and layout on the cached
+    plan of `batch` problems: "generic", or the fused step kernel's right-hand-side twin ("fused_rhs_mfma_f64_n64", "fused_rhs_qp_f64_n32", ...)."""
+    prob = problem.as_struct()
+    return L.lib().mo_plan_kkt_solve_kernel(plan_for(problem, int(batch)), C.byref(prob)).decode()
+
+
 def qp_gradients(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor, want: Optional[Iterable[str]] = None) -> Dict[str, torch.Tensor]:
     """mo_qp_gradients: the gradients named in `want` (default: every one the problem's input level has) from the state `vars` [B, V] and
     the adjoint `u` [B, V] = kkt_solve(..., transpose=True) of g = dl/dv.  Keys and layouts follow BatchedQP:

@@ -1,12 +1,14 @@
-"""The differentiable QP's launches, per launch, event-timed, in one process: mo_kkt_solve (direct and transposed),
-mo_qp_gradients (dc only; dG + dc; the J-level set dJ + dr + dlambda), the forward mo_qp_solve, and -- the yardstick of mo_kkt_solve --
-mo_newton_step on a MO_PLAN_FORCE_GENERIC plan of the same shape.  Prints one JSON line per shape.
+"""The differentiable QP's launches, per launch, event-timed, in one process: mo_kkt_solve (direct and transposed,
+J-level and (G, c) input) on the plan's own kernel -- the fused step kernel's right-hand-side twin where the shape is covered -- and on a
+MO_PLAN_FORCE_GENERIC plan, mo_qp_gradients (dc only; dG + dc; the J-level set dJ + dr + dlambda), the forward mo_qp_solve, and the two
+yardsticks of mo_kkt_solve: mo_newton_step on the plan's own kernel and on the generic one.  Prints one JSON line per shape.
 
   cfg3  n = 64, k = 8, m = 32, m_r = 128 (BASELINE configs[2])        ref8  n = 8, k = 2, m = 4, m_r = 16 (the reference's own size)
+  n128  n = 128, k = 14, m = 64, m_r = 256 (the 128 tile grid)
 
-mo_kkt_solve does strictly less than the generic Newton step (no residual, no alpha) and reads one more V-vector: kkt_over_step is expected
-at or below 1.1.  backward = the transposed solve + the J-level gradient launch; backward_over_forward is expected above 1 where the forward
-runs on a fused kernel.  mo_qp_gradients is data movement: achieved bytes/s against its algorithmic bytes (the vectors and matrices it must
+mo_kkt_solve does strictly less than the Newton step of the same kernel family (no residual, no alpha) and reads one more V-vector:
+kkt_over_step (generic pair) and kkt_over_fused_step (the plan's own pair) are expected at or below 1.1.  backward = the transposed solve +
+the gradient launch of the input level; backward_over_forward is that over the ten-iteration forward Solve.  mo_qp_gradients is data movement: achieved bytes/s against its algorithmic bytes (the vectors and matrices it must
 read and write once)."""
 import argparse
 import ctypes as C
@@ -21,7 +23,7 @@ from mini_opt_amd import _lib as L  # noqa: E402
 from mini_opt_amd import qp as Q  # noqa: E402
 from mini_opt_amd import synth  # noqa: E402
 
-SHAPES = {"cfg3": (64, 8, 32, 128), "ref8": (8, 2, 4, 16)}
+SHAPES = {"cfg3": (64, 8, 32, 128), "ref8": (8, 2, 4, 16), "n128": (128, 14, 64, 256)}
 HBM = 8.0e12
 
 
@@ -77,21 +79,25 @@ def run(shape, dtype, batch, reps, warmup, rounds):
     g_J.dr, g_J.dr_stride, g_J.dlambda, g_J.dlambda_stride = dr.data_ptr(), m_r, dlam.data_ptr(), 1
     prm = Q.Params(max_iterations=10)
     solver = Q.QPInteriorPointSolver(qp)
+    solver_qp_level = Q.QPInteriorPointSolver(qg)
+    kkt = lambda pl, ps, flags, dst: (lambda: L.check(lib.mo_kkt_solve(pl, C.byref(ps), batch, P(v), V, P(rhs), V, flags, P(dst), V, P(status), s)))  # noqa: E731
+    step = lambda pl, ps: (lambda: L.check(lib.mo_newton_step(pl, C.byref(ps), batch, P(v), V, P(mu), 1, 0.995, 0, P(delta), V, P(alpha), P(status), s)))  # noqa: E731
 
     calls = {
-        "kkt_solve": lambda: L.check(lib.mo_kkt_solve(plan, C.byref(pj), batch, P(v), V, P(rhs), V, 0, P(out), V, P(status), s)),
-        "kkt_solve_transposed": lambda: L.check(lib.mo_kkt_solve(plan, C.byref(pj), batch, P(v), V, P(rhs), V, L.MO_KKT_TRANSPOSE, P(u), V,
-                                                                 P(status), s)),
-        "newton_step_generic": lambda: L.check(lib.mo_newton_step(plan_generic, C.byref(pj), batch, P(v), V, P(mu), 1, 0.995, 0, P(delta), V,
-                                                                  P(alpha), P(status), s)),
-        "newton_step_plan_default": lambda: L.check(lib.mo_newton_step(plan, C.byref(pj), batch, P(v), V, P(mu), 1, 0.995, 0, P(delta), V,
-                                                                       P(alpha), P(status), s)),
-        "kkt_solve_transposed_qp_level": lambda: L.check(lib.mo_kkt_solve(plan, C.byref(pg), batch, P(v), V, P(rhs), V, L.MO_KKT_TRANSPOSE,
-                                                                          P(out), V, P(status), s)),
+        "kkt_solve": kkt(plan, pj, 0, out),
+        "kkt_solve_transposed": kkt(plan, pj, L.MO_KKT_TRANSPOSE, u),
+        "kkt_solve_generic": kkt(plan_generic, pj, 0, out),
+        "kkt_solve_transposed_generic": kkt(plan_generic, pj, L.MO_KKT_TRANSPOSE, out),
+        "newton_step_generic": step(plan_generic, pj),
+        "newton_step_plan_default": step(plan, pj),
+        "kkt_solve_qp_level": kkt(plan, pg, 0, out),
+        "kkt_solve_transposed_qp_level": kkt(plan, pg, L.MO_KKT_TRANSPOSE, out),
+        "newton_step_plan_default_qp_level": step(plan, pg),
         "gradients_c": lambda: L.check(lib.mo_qp_gradients(plan, C.byref(pg), batch, P(v), V, P(u), V, C.byref(g_c), s)),
         "gradients_G": lambda: L.check(lib.mo_qp_gradients(plan, C.byref(pg), batch, P(v), V, P(u), V, C.byref(g_G), s)),
         "gradients_J": lambda: L.check(lib.mo_qp_gradients(plan, C.byref(pj), batch, P(v), V, P(u), V, C.byref(g_J), s)),
         "forward_solve": lambda: solver.Solve(prm, record_iterations=False),
+        "forward_solve_qp_level": lambda: solver_qp_level.Solve(prm, record_iterations=False),
     }
     for fn in calls.values():
         for _ in range(warmup):
@@ -100,16 +106,27 @@ def run(shape, dtype, batch, reps, warmup, rounds):
     best = {key: float("inf") for key in calls}
     for _ in range(rounds):  # alternating rounds, best of
         for key, fn in calls.items():
-            best[key] = min(best[key], timed(fn, reps if key != "forward_solve" else max(1, reps // 4)))
+            best[key] = min(best[key], timed(fn, reps if not key.startswith("forward_solve") else max(1, reps // 4)))
     algo = {"gradients_c": elem * 2 * n, "gradients_G": elem * (2 * n + n * n + n),
             "gradients_J": elem * (m_r * n + m_r + 2 * n + m_r * n + m_r + 1)}
     res = {"shape": shape, "n": n, "k": k, "m": m, "m_r": m_r, "dtype": str(dtype).split(".")[-1], "batch": batch,
-           "step_kernel_plan_default": lib.mo_plan_step_kernel(plan, C.byref(pj)).decode(), "solve_kernel": solver.solve_kernel()}
+           "step_kernel_plan_default": lib.mo_plan_step_kernel(plan, C.byref(pj)).decode(), "solve_kernel": solver.solve_kernel(),
+           "kkt_solve_kernel": lib.mo_plan_kkt_solve_kernel(plan, C.byref(pj)).decode(),
+           "kkt_solve_kernel_qp_level": lib.mo_plan_kkt_solve_kernel(plan, C.byref(pg)).decode()}
     res.update({key + "_s": t for key, t in best.items()})
-    res["kkt_over_step"] = best["kkt_solve"] / best["newton_step_generic"]
-    res["kkt_transposed_over_step"] = best["kkt_solve_transposed"] / best["newton_step_generic"]
+    # the generic pair (the yardstick of the first version of mo_kkt_solve), then the plan's own pair
+    res["kkt_over_step"] = best["kkt_solve_generic"] / best["newton_step_generic"]
+    res["kkt_transposed_over_step"] = best["kkt_solve_transposed_generic"] / best["newton_step_generic"]
+    res["kkt_over_fused_step"] = best["kkt_solve"] / best["newton_step_plan_default"]
+    res["kkt_transposed_over_fused_step"] = best["kkt_solve_transposed"] / best["newton_step_plan_default"]
+    res["kkt_over_fused_step_qp_level"] = best["kkt_solve_qp_level"] / best["newton_step_plan_default_qp_level"]
+    res["kkt_transposed_over_fused_step_qp_level"] = best["kkt_solve_transposed_qp_level"] / best["newton_step_plan_default_qp_level"]
     res["backward_s"] = best["kkt_solve_transposed"] + best["gradients_J"]
     res["backward_over_forward"] = res["backward_s"] / best["forward_solve"]
+    res["backward_generic_s"] = best["kkt_solve_transposed_generic"] + best["gradients_J"]
+    res["backward_generic_over_forward"] = res["backward_generic_s"] / best["forward_solve"]
+    res["backward_qp_level_s"] = best["kkt_solve_transposed_qp_level"] + best["gradients_G"]
+    res["backward_over_forward_qp_level"] = res["backward_qp_level_s"] / best["forward_solve_qp_level"]
     for key, b in algo.items():
         res[key + "_bytes_per_problem"] = b
         res[key + "_TBps"] = b * batch / best[key] / 1e12

@@ -2380,7 +2380,6 @@ template <int UNIT, int F, int NT, int WPS, bool QPL, int MC, int JMODE, int NY,
 };
 // (family, NT, WPS, QPL, MC, JMODE, NY, PCK) in the table of unit kUnit
 #define MO_FUSED_ROW(...) FusedRowOf<kUnit, __VA_ARGS__>::row()
-#define MO_FUSED_TABLE_SIZE(rows) (int)(sizeof(rows) / sizeof(rows[0]))
 
 }  // namespace
 
@@ -2450,21 +2449,9 @@ FusedTable fused_table(int unit) {
   }
 }
 
-hipError_t launch_fused(const KernelArgs& a_in, int, int num_cus, hipStream_t stream) {
-  const FusedLaunch L = fused_select(a_in, num_cus);
-  const FusedTable table = fused_table(fused_unit(L.key));
-  FusedKernel kernel = nullptr;
-  for (int i = 0; i < table.count && !kernel; ++i)
-    if (table.rows[i].key == L.key) kernel = table.rows[i].kernel;
-  if (!kernel) return hipErrorInvalidDeviceFunction;   // a key without a row is an internal error: there is no fallback kernel
-  KernelArgs a = a_in;
-  a.stagger = L.stagger; a.chain_prio = L.chain_prio; a.static_rounds = L.static_rounds;
-  if (L.zero_ticket) {
-    hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), stream);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(L.block), 0, stream, a);
-  return hipGetLastError();
+hipError_t launch_fused(const KernelArgs& a, int, int num_cus, hipStream_t stream) {
+  const FusedLaunch L = fused_select(a, num_cus);
+  return fused_launch(fused_table(fused_unit(L.key)), L, a, stream);
 }
 
 #endif  // MO_FUSED_IMPL_ONLY

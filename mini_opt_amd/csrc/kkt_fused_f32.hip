@@ -9,9 +9,8 @@
 //     instead of column 15 of the [A_eq^T | rhs] tiles: (NT+1)(NT+2)/2 + NT + 1 tiles of 4 VGPRs (216 VGPRs at n = 128).
 // Reference lines: residual.hpp:206-224 + nonlinear.cc:187-189 (J^T J, J^T r, lambda), qp.cc:281-298 (assembly),
 // qp.cc:302-311 + 318-364 (factorisation and solve; no explicit inverse of H here), qp.cc:485-507 (alpha).
-#include <stdlib.h>
-
-#include "mo_kernels.h"
+// Which instantiation serves a launch: fused_f32_supported / fused_f32_select (mo_fused_select.h) and the table at the end of this file.
+#include "mo_fused_select.h"
 
 namespace mo {
 namespace {
@@ -1520,93 +1519,34 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
   }
 }
 
-bool aligned16_f32(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// ---- the instantiations as data: one table of rows {key, kernel}, as in the fp64 units (kkt_fused.hip) -----------------------------------
+// An fp32 key is (family, NT, WPS, PAD) with every other field at its default; a family without an fp32 kernel, or a linearisation with
+// PAD, has no F32KernelOf and does not compile.
+template <int F, int NT, int WPS, bool PAD> struct F32KernelOf;
+template <int NT, int WPS, bool PAD> struct F32KernelOf<FUSED_STEP, NT, WPS, PAD> { static constexpr FusedKernel kernel = kkt_fused_f32_kernel<NT, WPS, PAD>; };
+template <int NT, int WPS, bool PAD> struct F32KernelOf<FUSED_SOLVE, NT, WPS, PAD> { static constexpr FusedKernel kernel = kkt_fused_f32_solve_kernel<NT, WPS, PAD>; };
+template <int NT, int WPS> struct F32KernelOf<FUSED_LINEARIZE, NT, WPS, false> { static constexpr FusedKernel kernel = kkt_fused_f32_linearize_kernel<NT, WPS>; };
+template <int F, int NT, int WPS, bool PAD> FusedRow f32_row() {
+  constexpr FusedKey key{F, NT, WPS, 0, 1, JMODE_VECTOR, 1, 1, /* f32 */ 1, PAD};
+  static_assert(fused_unit(key) == UNIT_F32, "this row belongs to the table of another translation unit");
+  return FusedRow{key, F32KernelOf<F, NT, WPS, PAD>::kernel};
+}
+// (family, NT, WPS, PAD) as fused_f32_select names them
+const FusedRow kRows[] = {
+    f32_row<FUSED_LINEARIZE, 8, 2, false>(), f32_row<FUSED_LINEARIZE, 4, 3, false>(),
+    f32_row<FUSED_SOLVE, 8, 1, false>(), f32_row<FUSED_SOLVE, 8, 1, true>(), f32_row<FUSED_SOLVE, 4, 3, false>(), f32_row<FUSED_SOLVE, 4, 3, true>(),
+#ifdef MO_TUNING   // MO_FUSED_F32_WPS=1: the step on the 128 grid at one wave per SIMD
+    f32_row<FUSED_STEP, 8, 1, false>(), f32_row<FUSED_STEP, 8, 1, true>(),
+#endif
+    f32_row<FUSED_STEP, 8, 2, false>(), f32_row<FUSED_STEP, 8, 2, true>(), f32_row<FUSED_STEP, 4, 3, false>(), f32_row<FUSED_STEP, 4, 3, true>(),
+};
 
 }  // namespace
 
-bool fused_f32_supported(const KernelArgs& a, int dtype) {
-  if (dtype != MO_F32) return false;
-  if (a.mode == MODE_LINEARIZE && a.n != 128 && a.n != 64) return false;
-  if (a.n < 4 || a.n > 128 || (a.n & 3)) return false;   // step / Solve / Iterate / residual: any multiple of 4, padded inside the kernels to the 64 / 128 grid
-  if (a.mode == MODE_LINEARIZE) {  // kkt_fused_f32_linearize_kernel: packed row-major J, rows in whole 4-row groups
-    return a.J && a.ticket && a.G_out && a.c_out && a.J_row_major && a.J_ld == a.n && a.m_r > 0 && !(a.m_r & 3) && aligned16_f32(a.J) &&
-           !(a.J_stride & 3) && aligned16_f32(a.r) && !(a.r_stride & 3) && a.G_out_ld >= a.n;
-  }
-  if (a.k > 16 || a.m > 64 || a.m < 0) return false;
-  if (!a.ticket || !a.vars) return false;
-  if (a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL) {  // kkt_fused_f32_solve_kernel
-    if (a.mode == MODE_RESIDUAL ? ((a.flags & ~MO_STEP_NO_INEQUALITIES) != 0 || !a.r_out) : a.flags != 0) return false;
-    if (a.J) {
-      if (!a.J_row_major || a.J_ld != a.n || a.m_r <= 0) return false;
-      if (!aligned16_f32(a.J) || (a.J_stride & 3)) return false;
-    } else if (!a.G || !a.c || a.G_ld < a.n) {
-      return false;
-    }
-    return true;
-  }
-  if ((a.flags & ~MO_STEP_NO_INEQUALITIES) != 0 || a.mode != MODE_STEP) return false;
-  if (!a.delta || !a.J) return false;
-  if (!a.J_row_major || a.J_ld != a.n || a.m_r <= 0) return false;
-  if (!aligned16_f32(a.J) || (a.J_stride & 3)) return false;
-  return true;
-}
+FusedTable fused_f32_table() { return {kRows, MO_FUSED_TABLE_SIZE(kRows)}; }
 
-const char* fused_f32_name(const KernelArgs& a) {
-  if (a.mode == MODE_LINEARIZE) return a.n > 64 ? "fused_linearize_f32_n128" : "fused_linearize_f32_n64";
-  if (a.mode == MODE_STEP) return a.n > 64 ? "fused_mfma_f32_n128" : "fused_mfma_f32_n64";
-  if (!a.J) return a.n > 64 ? "fused_solve_qp_f32_n128" : "fused_solve_qp_f32_n64";
-  return a.n > 64 ? "fused_solve_mfma_f32_n128" : "fused_solve_mfma_f32_n64";
-}
-
-hipError_t launch_fused_f32(const KernelArgs& a_in, int num_cus, hipStream_t stream) {
-  KernelArgs a = a_in;
-  // static rounds up to this many problems per wave (mo_kernels.h; measured): equal-cost work (step, Iterate, residual,
-  // linearisation) splits statically further than a Solve, whose problems need different numbers of passes
-  if (a.static_rounds < 0) a.static_rounds = a.mode == MODE_SOLVE ? (a.n > 32 ? 2 : 6) : (a.n > 32 ? 8 : 32);
-#ifdef MO_TUNING   // (A/B builds only: the product library reads no environment variable)
-  static const int env_stagger = [] { const char* e = getenv("MO_FUSED_F32_STAGGER"); return e ? atoi(e) : -1; }();
-  static const int env_wps = [] { const char* e = getenv("MO_FUSED_F32_WPS"); return e ? atoi(e) : 0; }();
-#else
-  constexpr int env_stagger = -1, env_wps = 0;
-#endif
-  a.stagger = env_stagger >= 0 ? env_stagger : 0;
-  // The work counter is zeroed on the stream in front of the kernel -- unless the launch is certain to run in static rounds, which never touch
-  // it: every kernel below has at least 4 waves per workgroup and min(CUs, ceil(batch / 4)) workgroups, so batch <= rounds x 4 x workgroups
-  // is static whatever the instantiation (the kernels test batch <= rounds x waves).  One enqueued operation less per small launch.
-  if (!(a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * 4 * fused_grid(a.batch, num_cus))) {
-    hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), stream);
-    if (e != hipSuccess) return e;
-  }
-  const dim3 grid(fused_grid(a.batch, num_cus));
-  if (a.mode == MODE_LINEARIZE) {  // (two waves per SIMD at n = 128, three at n = 64)
-    if (a.n > 64) hipLaunchKernelGGL((kkt_fused_f32_linearize_kernel<8, 2>), grid, dim3(512), 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f32_linearize_kernel<4, 3>), grid, dim3(768), 0, stream, a);
-    return hipGetLastError();
-  }
-  if (a.mode != MODE_STEP) {  // Solve / Iterate / KKT residual: one wave per SIMD at n = 128 (216 tile registers + the state), three at n = 64
-    if (a.n > 64) { if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<8, 1, false>), grid, dim3(256), 0, stream, a); else hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<8, 1, true>), grid, dim3(256), 0, stream, a); }
-    else { if (a.n == 64) hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<4, 3, false>), grid, dim3(768), 0, stream, a); else hipLaunchKernelGGL((kkt_fused_f32_solve_kernel<4, 3, true>), grid, dim3(768), 0, stream, a); }
-    return hipGetLastError();
-  }
-#ifdef MO_TUNING
-  if (a.n > 64 && env_wps == 1) {
-    constexpr int WPS = 1;
-    if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, false>), grid, dim3(256 * WPS), 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, true>), grid, dim3(256 * WPS), 0, stream, a);
-  } else
-#else
-  (void)env_wps;
-#endif
-  if (a.n > 64) {
-    constexpr int WPS = 2;  // 255 VGPRs, no scratch: the 216 accumulator registers + operands just fit two waves per SIMD
-    if (a.n == 128) hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, false>), grid, dim3(256 * WPS), 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f32_kernel<8, WPS, true>), grid, dim3(256 * WPS), 0, stream, a);
-  } else {
-    constexpr int WPS = 3;
-    if (a.n == 64) hipLaunchKernelGGL((kkt_fused_f32_kernel<4, WPS, false>), grid, dim3(256 * WPS), 0, stream, a);
-    else hipLaunchKernelGGL((kkt_fused_f32_kernel<4, WPS, true>), grid, dim3(256 * WPS), 0, stream, a);
-  }
-  return hipGetLastError();
+hipError_t launch_fused_f32(const KernelArgs& a, int num_cus, hipStream_t stream) {
+  return fused_launch(fused_f32_table(), fused_f32_select(a, num_cus), a, stream);
 }
 
 }  // namespace mo

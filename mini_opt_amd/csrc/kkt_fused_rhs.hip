@@ -27,21 +27,8 @@ const FusedRow kRows[] = {
 }  // namespace
 FusedTable fused_rhs_table() { return {kRows, MO_FUSED_TABLE_SIZE(kRows)}; }
 
-hipError_t launch_fused_rhs(const KernelArgs& a_in, int, int num_cus, hipStream_t stream) {
-  const FusedLaunch L = fused_rhs_select(a_in, num_cus);
-  const FusedTable table = fused_rhs_table();
-  FusedKernel kernel = nullptr;
-  for (int i = 0; i < table.count && !kernel; ++i)
-    if (table.rows[i].key == L.key) kernel = table.rows[i].kernel;
-  if (!kernel) return hipErrorInvalidDeviceFunction;   // a supported key without a row is an internal error: there is no fallback kernel
-  KernelArgs a = a_in;
-  a.stagger = L.stagger; a.chain_prio = L.chain_prio; a.static_rounds = L.static_rounds;
-  if (L.zero_ticket) {
-    hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), stream);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(L.block), 0, stream, a);
-  return hipGetLastError();
+hipError_t launch_fused_rhs(const KernelArgs& a, int, int num_cus, hipStream_t stream) {
+  return fused_launch(fused_rhs_table(), fused_rhs_select(a, num_cus), a, stream);   // a supported key without a row is an error, never another kernel
 }
 
 }  // namespace mo

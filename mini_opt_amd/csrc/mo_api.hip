@@ -1,6 +1,6 @@
 // mo_api.hip -- implementation of the C ABI declared in include/mini_opt_hip.h.
 // Validation mirrors QPInteriorPointSolver::Setup (qp.cc:20-73) and CheckParams (qp.cc:76-82); everything numeric
-// happens in the gfx950 kernels (kkt_generic.hip, kkt_fused.hip).  There is NO CPU fallback: without a usable HIP
+// happens in the gfx950 kernels (kkt_generic.hip, kkt_fused*.hip; which one serves a call: mo::decide_kernel, mo_fused_select.h).  There is NO CPU fallback: without a usable HIP
 // device every entry point fails with MO_ERR_NO_DEVICE / MO_ERR_HIP.
 #include <stdarg.h>
 #include <stdio.h>
@@ -66,15 +66,44 @@ int check_plan(const mo_plan* plan) {
   return MO_OK;
 }
 
-// Dimension / pointer checks shared by every batched entry point (the F_ASSERTs of qp.cc:21-34).
+// The product library reads NO environment variable (the reference has none, SURVEY.md section 5): kernel selection and scheduling follow the
+// plan flags of include/mini_opt_hip.h only.  The getenv knobs of the A/B scripts exist in builds with -DMO_TUNING (tools/ab_build.sh).
+bool generic_forced(const mo_plan* plan) {
+#ifdef MO_TUNING
+  static const bool env_force_generic = getenv("MO_FORCE_GENERIC") != nullptr;  // A/B and bisection knob
+  if (env_force_generic) return true;
+#endif
+  return (plan->desc.flags & MO_PLAN_FORCE_GENERIC) != 0;
+}
+
+// Launches of at most this many problems per wave of the persistent grid are split statically (KernelArgs::static_rounds): -1 = the selector's
+// own choice per kernel family (mo_fused_select.h); MO_PLAN_TICKETS_ALWAYS -> 0, MO_PLAN_STATIC_ROUNDS_ALWAYS -> every launch
+int fused_static_rounds(const mo_plan* plan) {
+#ifdef MO_TUNING
+  static const int v = [] { const char* e = getenv("MO_FUSED_STATIC_ROUNDS"); return e ? atoi(e) : -1; }();
+  if (v >= 0) return v;
+#endif
+  if (plan->desc.flags & MO_PLAN_TICKETS_ALWAYS) return 0;
+  if (plan->desc.flags & MO_PLAN_STATIC_ROUNDS_ALWAYS) return 1 << 30;
+  return -1;
+}
+
+// The equality and inequality rows of the system a call works on, where that is not the plan's own: the cost alone (mo_linearize, the
+// eigenvalue statistics) or the problem without its inequalities (the null-space solver).  -1: the plan's.
+struct Dims { int k = -1, m = -1; };
+
+// Every KernelArgs starts here: the dimension / pointer checks shared by every batched entry point (the F_ASSERTs of qp.cc:21-34) and the
+// plan-scoped fields of the fused kernels.
 int fill_problem(const mo_plan* plan, const mo_problem* prob, int64_t batch, bool need_cost, bool need_constraints,
-                 mo::KernelArgs* a) {
+                 mo::KernelArgs* a, Dims dims = Dims()) {
   if (!prob) return fail(MO_ERR_INVALID_ARGUMENT, "Must pass a non-null problem");
   if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
   const mo_plan_desc& d = plan->desc;
+  const int k = dims.k >= 0 ? dims.k : d.k, m = dims.m >= 0 ? dims.m : d.m;
   memset(a, 0, sizeof(*a));
-  a->n = d.n; a->k = d.k; a->m = d.m; a->m_r = 0;
+  a->n = d.n; a->k = k; a->m = m; a->m_r = 0;
   a->batch = batch;
+  a->ticket = plan->ticket; a->static_rounds = fused_static_rounds(plan); a->no_tiny = (d.flags & MO_PLAN_NO_TINY) != 0;
   if (need_cost) {
     if (prob->J) {
       if (d.m_r <= 0) return fail(MO_ERR_DIMENSION, "J given but the plan was created with m_r = 0");
@@ -93,73 +122,40 @@ int fill_problem(const mo_plan* plan, const mo_problem* prob, int64_t batch, boo
       a->c = prob->c; a->c_stride = prob->c_stride;
     }
   }
-  if (d.k > 0) {
-    if (!prob->A_eq || !prob->b_eq) return fail(MO_ERR_DIMENSION, "Rows of A_e and b_e must match (k = %d but NULL given)", d.k);
-    if (prob->A_ld < d.k) return fail(MO_ERR_DIMENSION, "A_ld %d < k %d", prob->A_ld, d.k);
+  if (k > 0) {
+    if (!prob->A_eq || !prob->b_eq) return fail(MO_ERR_DIMENSION, "Rows of A_e and b_e must match (k = %d but NULL given)", k);
+    if (prob->A_ld < k) return fail(MO_ERR_DIMENSION, "A_ld %d < k %d", prob->A_ld, k);
     a->A = prob->A_eq; a->A_stride = prob->A_stride; a->A_ld = prob->A_ld;
     a->b = prob->b_eq; a->b_stride = prob->b_stride;
   }
-  if (d.m > 0 && need_constraints) {
+  if (m > 0 && need_constraints) {
     if (!prob->cons_var || !prob->cons_a || !prob->cons_b)
-      return fail(MO_ERR_INVALID_ARGUMENT, "m = %d but constraint arrays are NULL", d.m);
+      return fail(MO_ERR_INVALID_ARGUMENT, "m = %d but constraint arrays are NULL", m);
     a->cons_var = prob->cons_var; a->cons_a = prob->cons_a; a->cons_b = prob->cons_b; a->cons_stride = prob->cons_stride;
   }
   return MO_OK;
 }
 
-// Which kernel serves a call is decided ONCE, here, from the plan flags, the process-wide MO_FORCE_GENERIC knob (read a single
-// time: the scratch a call prepares and the kernel that consumes it must come from the same decision) and the kernels' own
-// shape predicates.
-enum KernelChoice { KERNEL_FUSED_F64, KERNEL_FUSED_F32, KERNEL_GENERIC, KERNEL_FUSED_RHS_F64 };
-
-// The product library reads NO environment variable (the reference has none, SURVEY.md section 5): kernel selection and scheduling follow the
-// plan flags of include/mini_opt_hip.h only.  The getenv knobs of the A/B scripts exist in builds with -DMO_TUNING (tools/ab_build.sh).
-bool generic_forced(const mo_plan* plan) {
-#ifdef MO_TUNING
-  static const bool env_force_generic = getenv("MO_FORCE_GENERIC") != nullptr;  // A/B and bisection knob
-  if (env_force_generic) return true;
-#endif
-  return (plan->desc.flags & MO_PLAN_FORCE_GENERIC) != 0;
+// Which kernel serves a call is decided ONCE, by mo::decide_kernel (mo_fused_select.h) from the arguments, the plan's dtype and the
+// force-generic flag (read a single time: the scratch a call prepares and the kernel that consumes it must come from the same decision).
+mo::KernelDecision decide(const mo_plan* plan, const mo::KernelArgs& a) {
+  return mo::decide_kernel(a, plan->desc.dtype, generic_forced(plan), plan->num_cus);
 }
 
-// Launches of at most this many problems per wave of the persistent grid are split statically (KernelArgs::static_rounds): -1 = the launcher's
-// own choice per kernel family (launch_fused / launch_fused_f32); MO_PLAN_TICKETS_ALWAYS -> 0, MO_PLAN_STATIC_ROUNDS_ALWAYS -> every launch
-int fused_static_rounds(const mo_plan* plan) {
-#ifdef MO_TUNING
-  static const int v = [] { const char* e = getenv("MO_FUSED_STATIC_ROUNDS"); return e ? atoi(e) : -1; }();
-  if (v >= 0) return v;
-#endif
-  if (plan->desc.flags & MO_PLAN_TICKETS_ALWAYS) return 0;
-  if (plan->desc.flags & MO_PLAN_STATIC_ROUNDS_ALWAYS) return 1 << 30;
-  return -1;
-}
-
-KernelChoice choose_kernel(const mo_plan* plan, const mo::KernelArgs& a) {
-  if (a.mode == mo::MODE_RHS)   // mo_kkt_solve: the step kernel's right-hand-side twin where one exists, the generic kernel everywhere else
-    return !generic_forced(plan) && mo::fused_rhs_supported(a, plan->desc.dtype) ? KERNEL_FUSED_RHS_F64 : KERNEL_GENERIC;
-  if (!generic_forced(plan)) {
-    if (mo::fused_supported(a, plan->desc.dtype)) return KERNEL_FUSED_F64;
-    if (mo::fused_f32_supported(a, plan->desc.dtype)) return KERNEL_FUSED_F32;
-  }
-  return KERNEL_GENERIC;
-}
-
-int launch_chosen(const mo_plan* plan, const mo::KernelArgs& a_in, KernelChoice choice, void* stream) {
-  if (a_in.batch == 0) return MO_OK;
-  mo::KernelArgs a = a_in;
-  a.ticket = plan->ticket; a.static_rounds = fused_static_rounds(plan); a.no_tiny = (plan->desc.flags & MO_PLAN_NO_TINY) != 0;
+int launch(const mo_plan* plan, mo::KernelArgs a, const mo::KernelDecision& d, void* stream) {
+  if (a.batch == 0) return MO_OK;
   MO_HIP_CHECK(hipSetDevice(plan->desc.device));
   hipStream_t s = (hipStream_t)stream;
-  if (choice == KERNEL_FUSED_F64) {
+  if (d.kind == mo::KERNEL_FUSED_F64) {
     MO_HIP_CHECK(mo::launch_fused(a, plan->desc.dtype, plan->num_cus, s));
-  } else if (choice == KERNEL_FUSED_F32) {
+  } else if (d.kind == mo::KERNEL_FUSED_F32) {
     MO_HIP_CHECK(mo::launch_fused_f32(a, plan->num_cus, s));
-  } else if (choice == KERNEL_FUSED_RHS_F64) {
+  } else if (d.kind == mo::KERNEL_FUSED_RHS) {
     MO_HIP_CHECK(mo::launch_fused_rhs(a, plan->desc.dtype, plan->num_cus, s));
   } else {
     if (mo::generic_needs_large(a, plan->elem)) {  // H in a global workspace per workgroup: plan-owned, allocated by mo_plan_create
       const size_t need = mo::generic_large_lds_bytes(a, plan->elem);
-      if (need > 160 * 1024)
+      if (need > mo::kLdsBytes)
         return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d: not even the state / residual vectors of one problem fit the 160 KiB of LDS", a.n, a.k, a.m);
       if (!plan->H_work || mo::generic_large_workspace_elems(a) * plan->elem > plan->H_work_slot_bytes)
         return fail(MO_ERR_UNSUPPORTED, "the plan owns no H workspace for n = %d, k = %d (created for n = %d, k = %d)", a.n, a.k, plan->desc.n, plan->desc.k);
@@ -170,10 +166,19 @@ int launch_chosen(const mo_plan* plan, const mo::KernelArgs& a_in, KernelChoice 
   return MO_OK;
 }
 
-int launch(const mo_plan* plan, const mo::KernelArgs& a_in, void* stream) {
-  mo::KernelArgs a = a_in;
-  a.ticket = plan->ticket; a.static_rounds = fused_static_rounds(plan); a.no_tiny = (plan->desc.flags & MO_PLAN_NO_TINY) != 0;
-  return launch_chosen(plan, a, choose_kernel(plan, a), stream);
+int launch(const mo_plan* plan, const mo::KernelArgs& a, void* stream) { return launch(plan, a, decide(plan, a), stream); }
+
+// What mo_plan_step_kernel / mo_plan_solve_kernel / mo_plan_kkt_solve_kernel report: the name of the decision for a one-problem call.
+const char* plan_kernel_name(const mo_plan* plan, const mo_problem* prob, int mode) {
+  if (!plan || !prob) return "invalid";
+  mo::KernelArgs a;
+  if (fill_problem(plan, prob, 1, true, true, &a) != MO_OK) return "invalid";
+  a.mode = mode;
+  // layout query only: assume a 16-byte aligned, densely packed state / output (the right-hand side of mo_kkt_solve has no alignment rule)
+  a.vars = a.delta = reinterpret_cast<void*>(16);
+  a.rhs = reinterpret_cast<const void*>(32);
+  a.vars_stride = a.delta_stride = a.rhs_stride = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
+  return decide(plan, a).name;
 }
 
 }  // namespace
@@ -244,7 +249,7 @@ int mo_plan_create(const mo_plan_desc* desc, mo_plan** out) {
     memset(&sz, 0, sizeof(sz));
     sz.n = desc->n; sz.k = desc->k; sz.m = desc->m; sz.m_r = desc->m_r;
     const int elem = desc->dtype == MO_F64 ? 8 : 4;
-    if (mo::generic_needs_large(sz, elem) && mo::generic_large_lds_bytes(sz, elem) > 160 * 1024)
+    if (mo::generic_needs_large(sz, elem) && mo::generic_large_lds_bytes(sz, elem) > mo::kLdsBytes)
       return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d: the state / residual vectors of one problem exceed the 160 KiB of LDS", desc->n, desc->k, desc->m);
   }
   int ndev = 0;
@@ -310,14 +315,11 @@ int mo_plan_create(const mo_plan_desc* desc, mo_plan** out) {
     p->H_work_slot_bytes = slot_bytes;
     p->H_work_slots = slots;
   }
-  // Tile park of the fused fp64 Solve kernels beyond the 32 grid (qp_solve_impl): one slot per wave of the persistent grid (one workgroup
-  // per CU, at most twelve waves each), 22.5 KB at n = 64, 78 KB at n = 128.  Optional -- without it the kernels rebuild the tiles every
+  // Tile park of the fused fp64 Solve kernels beyond the 32 grid (qp_solve_impl; geometry: mo_fused_select.h): one slot per wave of the
+  // persistent grid, 22.5 KB at n = 64, 78 KB at n = 128.  Optional -- without it the kernels rebuild the tiles every
   // pass -- so a failed allocation is not an error.
   if (desc->dtype == MO_F64 && desc->n > 32 && desc->n <= 128 && desc->k <= 63 && desc->m <= 256) {
-    const int nt = desc->n > 96 ? 8 : desc->n > 64 ? 6 : 4;
-    const size_t per_slot = (size_t)(nt * (nt + 1) / 2) * 256 + (size_t)nt * 64;
-    const size_t slots = (size_t)p->num_cus * 12;
-    if (hipMalloc(&p->tile_scratch, slots * per_slot * p->elem) != hipSuccess) {
+    if (hipMalloc(&p->tile_scratch, mo::fused_tile_park_slots(p->num_cus) * mo::fused_tile_park_slot_elems(desc->n) * p->elem) != hipSuccess) {
       p->tile_scratch = nullptr;
       (void)hipGetLastError();
     }
@@ -338,48 +340,9 @@ int mo_plan_destroy(mo_plan* plan) {
   return MO_OK;
 }
 
-const char* mo_plan_step_kernel(const mo_plan* plan, const mo_problem* prob) {
-  if (!plan || !prob) return "invalid";
-  mo::KernelArgs a;
-  if (fill_problem(plan, prob, 1, true, true, &a) != MO_OK) return "invalid";
-  a.mode = mo::MODE_STEP;
-  a.vars = a.delta = reinterpret_cast<void*>(16);  // layout query only: assume 16-byte aligned, densely packed state / output
-  a.vars_stride = a.delta_stride = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
-  a.ticket = plan->ticket; a.static_rounds = fused_static_rounds(plan); a.no_tiny = (plan->desc.flags & MO_PLAN_NO_TINY) != 0;
-  switch (choose_kernel(plan, a)) {
-    case KERNEL_FUSED_F64: return mo::fused_name(a, plan->desc.dtype);
-    case KERNEL_FUSED_F32: return mo::fused_f32_name(a);
-    default: return "generic";
-  }
-}
-
-const char* mo_plan_solve_kernel(const mo_plan* plan, const mo_problem* prob) {
-  if (!plan || !prob) return "invalid";
-  mo::KernelArgs a;
-  if (fill_problem(plan, prob, 1, true, true, &a) != MO_OK) return "invalid";
-  a.mode = mo::MODE_SOLVE;
-  a.vars = reinterpret_cast<void*>(16);  // layout query only
-  a.vars_stride = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
-  a.ticket = plan->ticket; a.static_rounds = fused_static_rounds(plan); a.no_tiny = (plan->desc.flags & MO_PLAN_NO_TINY) != 0;
-  switch (choose_kernel(plan, a)) {
-    case KERNEL_FUSED_F64: return mo::fused_name(a, plan->desc.dtype);
-    case KERNEL_FUSED_F32: return mo::fused_f32_name(a);
-    default: return "generic";
-  }
-}
-
-const char* mo_plan_kkt_solve_kernel(const mo_plan* plan, const mo_problem* prob) {
-  if (!plan || !prob) return "invalid";
-  mo::KernelArgs a;
-  if (fill_problem(plan, prob, 1, true, true, &a) != MO_OK) return "invalid";
-  a.mode = mo::MODE_RHS;
-  a.vars = a.delta = reinterpret_cast<void*>(16);  // layout query only: the state, right-hand side and output have no alignment rule
-  a.rhs = reinterpret_cast<const void*>(32);
-  a.vars_stride = a.delta_stride = a.rhs_stride = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
-  a.ticket = plan->ticket; a.static_rounds = fused_static_rounds(plan); a.no_tiny = (plan->desc.flags & MO_PLAN_NO_TINY) != 0;
-  if (choose_kernel(plan, a) == KERNEL_FUSED_RHS_F64) return mo::fused_rhs_name(mo::fused_rhs_select(a, 1).key);
-  return "generic";
-}
+const char* mo_plan_step_kernel(const mo_plan* plan, const mo_problem* prob) { return plan_kernel_name(plan, prob, mo::MODE_STEP); }
+const char* mo_plan_solve_kernel(const mo_plan* plan, const mo_problem* prob) { return plan_kernel_name(plan, prob, mo::MODE_SOLVE); }
+const char* mo_plan_kkt_solve_kernel(const mo_plan* plan, const mo_problem* prob) { return plan_kernel_name(plan, prob, mo::MODE_RHS); }
 
 int mo_linearize(mo_plan* plan, const mo_problem* prob, int64_t batch, void* G_out, int64_t G_stride, int32_t G_ld,
                  void* c_out, int64_t c_stride, void* half_sq_out, void* stream) {
@@ -388,15 +351,13 @@ int mo_linearize(mo_plan* plan, const mo_problem* prob, int64_t batch, void* G_o
   mo::KernelArgs a;
   if (prob && !prob->J) return fail(MO_ERR_INVALID_ARGUMENT, "mo_linearize needs J-level input");
   // A_eq / constraints are not touched by the linearisation of the cost
-  mo_plan tmp = *plan;
-  tmp.desc.k = 0; tmp.desc.m = 0;
-  if (int rc = fill_problem(&tmp, prob, batch, true, false, &a)) return rc;
+  if (int rc = fill_problem(plan, prob, batch, true, false, &a, Dims{0, 0})) return rc;
   if (!G_out || !c_out) return fail(MO_ERR_INVALID_ARGUMENT, "G_out / c_out is NULL");
   if (G_ld < plan->desc.n) return fail(MO_ERR_DIMENSION, "G_ld %d < n", G_ld);
   a.mode = mo::MODE_LINEARIZE;
   a.G_out = G_out; a.G_out_stride = G_stride; a.G_out_ld = G_ld;
   a.c_out = c_out; a.c_out_stride = c_stride; a.half_sq_out = half_sq_out;
-  return launch(&tmp, a, stream);
+  return launch(plan, a, stream);
 }
 
 int mo_fill_qp(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* x, int64_t x_stride, void* G_out,
@@ -411,16 +372,14 @@ int mo_fill_qp(mo_plan* plan, const mo_problem* prob, int64_t batch, const void*
   mo::KernelArgs ka;
   if (int rc = fill_problem(plan, prob, batch, true, true, &ka)) return rc;  // validates A_eq / b_eq / constraints too
   // cost part: G = J^T J + lambda I, c = J^T r, f = 0.5 |r|^2 (nonlinear.cc:182-189) -> errors_out[2 p]
-  mo_plan tmp = *plan;
-  tmp.desc.k = 0; tmp.desc.m = 0;
   mo::KernelArgs a;
-  if (int rc = fill_problem(&tmp, prob, batch, true, false, &a)) return rc;
+  if (int rc = fill_problem(plan, prob, batch, true, false, &a, Dims{0, 0})) return rc;
   if (!G_out || !c_out) return fail(MO_ERR_INVALID_ARGUMENT, "G_out / c_out is NULL");
   if (G_ld < d.n) return fail(MO_ERR_DIMENSION, "G_ld %d < n", G_ld);
   a.mode = mo::MODE_LINEARIZE;
   a.G_out = G_out; a.G_out_stride = G_stride; a.G_out_ld = G_ld;
   a.c_out = c_out; a.c_out_stride = c_stride; a.half_sq_out = errors_out; a.half_sq_stride = 2;
-  if (int rc = launch(&tmp, a, stream)) return rc;
+  if (int rc = launch(plan, a, stream)) return rc;
   if (batch == 0) return MO_OK;
   // tail: shifted constraints and the equality L1 norm (nonlinear.cc:192-212)
   mo::AuxArgs x_args;
@@ -495,12 +454,10 @@ int mo_qp_eigenvalue_stats(mo_plan* plan, const mo_problem* prob, int64_t batch,
   g_err[0] = 0;
   if (int rc = check_plan(plan)) return rc;
   if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
-  mo_plan tmp = *plan;
-  tmp.desc.k = 0; tmp.desc.m = 0;   // only the cost (G, or J with its damping) takes part
   mo::KernelArgs a;
-  if (int rc = fill_problem(&tmp, prob, batch, true, false, &a)) return rc;
+  if (int rc = fill_problem(plan, prob, batch, true, false, &a, Dims{0, 0})) return rc;   // only the cost (G, or J with its damping) takes part
   if (batch == 0) return MO_OK;
-  if (mo::eig_lds_bytes(plan->desc.n, false) > 160 * 1024)
+  if (mo::eig_lds_bytes(plan->desc.n, false) > mo::kLdsBytes)
     return fail(MO_ERR_UNSUPPORTED, "n = %d: not even the vectors of the tridiagonal eigenvalue problem fit the 160 KiB of LDS", plan->desc.n);
   MO_HIP_CHECK(hipSetDevice(plan->desc.device));
   MO_HIP_CHECK(mo::launch_qp_eig(a, plan->desc.dtype, plan->num_cus, out, 3, plan->H_work, plan->H_work_slot_bytes, plan->H_work_slots,
@@ -562,7 +519,7 @@ int mo_kkt_solve(mo_plan* plan, const mo_problem* prob, int64_t batch, const voi
   a.vars = const_cast<void*>(vars); a.vars_stride = vars_stride;
   a.rhs = rhs; a.rhs_stride = rhs_stride;
   a.delta = out; a.delta_stride = out_stride; a.status = status;
-  // one decision per call (choose_kernel): the step kernel's right-hand-side twin on the shapes fused_rhs_supported names, else the generic kernel
+  // one decision per call (decide_kernel): the step kernel's right-hand-side twin on the shapes fused_rhs_supported names, else the generic kernel
   return launch(plan, a, stream);
 }
 
@@ -643,10 +600,8 @@ int qp_solve_impl(mo_plan* plan, const mo_problem* prob, int64_t batch, const mo
   a.termination = termination; a.num_iterations = num_iterations; a.iterations = iterations; a.lagrange = lagrange;
   a.status = status;
   a.skip = skip; a.skip_stride = skip_stride; a.skip_active = skip_active;
-  a.ticket = plan->ticket; a.static_rounds = fused_static_rounds(plan); a.no_tiny = (plan->desc.flags & MO_PLAN_NO_TINY) != 0;
-  const KernelChoice choice = choose_kernel(plan, a);
-  const bool use_fused = choice != KERNEL_GENERIC;
-  if (a.J && !use_fused) {  // the generic loop re-reads G after every factorisation: keep the linearised G, c in plan scratch
+  const mo::KernelDecision d = decide(plan, a);
+  if (a.J && d.kind == mo::KERNEL_GENERIC) {  // the generic loop re-reads G after every factorisation: keep the linearised G, c in plan scratch
     if (batch > plan->desc.max_batch) return fail(MO_ERR_INVALID_ARGUMENT, "batch %lld > plan max_batch %lld", (long long)batch, (long long)plan->desc.max_batch);
     const size_t n = (size_t)plan->desc.n;
     MO_HIP_CHECK(hipSetDevice(plan->desc.device));
@@ -665,16 +620,14 @@ int qp_solve_impl(mo_plan* plan, const mo_problem* prob, int64_t batch, const mo
     a.G_out = plan->G_scratch; a.G_out_stride = (long long)(n * n); a.G_out_ld = (int)n;
     a.c_out = plan->c_scratch; a.c_out_stride = (long long)n;
   }
-  if (use_fused && plan->desc.dtype == MO_F64 && plan->desc.n > 32) {   // (fp32 and the 32 grid park every tile in LDS)
+  if (d.kind == mo::KERNEL_FUSED_F64 && plan->desc.n > 32) {   // (fp32 and the 32 grid park every tile in LDS)
     // Tile park of the fused Solve kernels: the G tiles a wave cannot keep in LDS between the passes go to a scratch indexed by the
     // wave's slot in the persistent grid (one workgroup per CU, at most twelve waves each), so its size does not depend on the batch
     // and the lines a wave re-reads every pass stay in its XCD's L2.  Optional: without it the kernel rebuilds the tiles every pass.
-    // Plan-owned: mo_plan_create allocates it (round 4; it used to be allocated by the first Solve -- an allocation in the launch path).
-    const int nt = plan->desc.n > 96 ? 8 : plan->desc.n > 64 ? 6 : plan->desc.n > 32 ? 4 : 2;
-    const size_t per_slot = (size_t)(nt * (nt + 1) / 2) * 256 + (size_t)nt * 64;
-    a.G_out = plan->tile_scratch; a.G_out_stride = (long long)per_slot;
+    // Plan-owned: mo_plan_create allocates it, with the geometry of mo_fused_select.h.
+    a.G_out = plan->tile_scratch; a.G_out_stride = (long long)mo::fused_tile_park_slot_elems(plan->desc.n);
   }
-  return launch_chosen(plan, a, choice, stream);  // fused Solve kernel (fp64: n <= 128; fp32: n = 64 / 128), generic kernel otherwise
+  return launch(plan, a, d, stream);  // fused Solve kernel (fp64: n <= 128; fp32: n = 64 / 128), generic kernel otherwise
 }
 }  // namespace
 
@@ -694,15 +647,13 @@ int mo_nullspace_solve(mo_plan* plan, const mo_problem* prob, int64_t batch, voi
   if (plan->desc.k <= 0) return fail(MO_ERR_DIMENSION, "Problem must have at least one equality constraint");  // F_ASSERT_GT qp.cc:680
   if (plan->desc.k > plan->desc.n) return fail(MO_ERR_DIMENSION, "k = %d equality rows for n = %d variables", plan->desc.k, plan->desc.n);
   if (!x_out || !termination) return fail(MO_ERR_INVALID_ARGUMENT, "x_out / termination is NULL");
-  mo_plan tmp = *plan;
-  tmp.desc.m = 0;  // no inequalities on this path
   mo::KernelArgs a;
-  if (int rc = fill_problem(&tmp, prob, batch, true, false, &a)) return rc;
+  if (int rc = fill_problem(plan, prob, batch, true, false, &a, Dims{-1, 0})) return rc;  // no inequalities on this path
   if (batch == 0) return MO_OK;
   a.delta = x_out; a.delta_stride = x_stride;
   a.status = termination;  // MO_STATUS_* first; translated to QPNullSpaceTerminationState below
   const size_t need = mo::nullspace_lds_bytes(plan->desc.n, plan->desc.k, a.m_r, plan->elem);
-  if (need > 160 * 1024) return fail(MO_ERR_UNSUPPORTED, "the null-space solver keeps G and A_eq^T in LDS: %zu B needed (> 160 KiB)", need);
+  if (need > mo::kLdsBytes) return fail(MO_ERR_UNSUPPORTED, "the null-space solver keeps G and A_eq^T in LDS: %zu B needed (> 160 KiB)", need);
   MO_HIP_CHECK(hipSetDevice(plan->desc.device));
   MO_HIP_CHECK(mo::launch_nullspace(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
   mo::AuxArgs t;
@@ -739,7 +690,7 @@ void mo_default_nls_params(mo_nls_params* p) {
 
 static bool nls_takes_nullspace_path(const mo_plan* plan) {
   const mo_plan_desc& d = plan->desc;
-  return d.m == 0 && d.k > 0 && d.k <= d.n && mo::nullspace_lds_bytes(d.n, d.k, d.m_r, plan->elem) <= 160 * 1024;
+  return d.m == 0 && d.k > 0 && d.k <= d.n && mo::nullspace_lds_bytes(d.n, d.k, d.m_r, plan->elem) <= mo::kLdsBytes;
 }
 
 int mo_plan_nls_uses_nullspace(const mo_plan* plan) { return plan && nls_takes_nullspace_path(plan) ? 1 : 0; }
@@ -956,9 +907,8 @@ int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const m
     if (nls_takes_nullspace_path(plan)) {
       // equality constraints only: QPNullSpaceSolver (nonlinear.cc:83-86, 249-258) -- singular G = J^T J is fine as long as
       // the reduced Hessian is positive definite; NOT_POSITIVE_DEFINITE ends the problem with QP_INDEFINITE (:103-105)
-      mo_plan tmp = *plan;
       mo::KernelArgs ka;
-      if (int rc = fill_problem(&tmp, &qp, batch, true, false, &ka)) return rc;
+      if (int rc = fill_problem(plan, &qp, batch, true, false, &ka)) return rc;
       ka.delta = qp_vars; ka.delta_stride = Vs; ka.status = qp_status;
       MO_HIP_CHECK(hipMemsetAsync(qp_term, 0, sizeof(int) * (size_t)batch, s));
       MO_HIP_CHECK(hipMemsetAsync(qp_nit, 0, sizeof(int) * (size_t)batch, s));
@@ -972,10 +922,8 @@ int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const m
                                     hipMemcpyDeviceToDevice, s));
     }
     if (prm->log_qp_eigenvalues) {   // qp_.ComputeEigenvalueStats() of this iteration's QP (nonlinear.cc:138), still-active problems only
-      mo_plan tmp = *plan;
-      tmp.desc.k = 0; tmp.desc.m = 0;
       mo::KernelArgs ka;
-      if (int rc = fill_problem(&tmp, &qp, batch, true, false, &ka)) return rc;
+      if (int rc = fill_problem(plan, &qp, batch, true, false, &ka, Dims{0, 0})) return rc;
       ka.skip = si + mo::NLS_SI_TERM; ka.skip_stride = mo::NLS_SI;
       MO_HIP_CHECK(mo::launch_qp_eig(ka, d.dtype, plan->num_cus, (double*)np->qp_eigenvalues + (size_t)iter * (size_t)batch * 3, 3, plan->H_work,
                                      plan->H_work_slot_bytes, plan->H_work_slots, s));

@@ -1,7 +1,9 @@
-// mo_fused_select.h -- which fused fp64 kernel serves a launch, as data.  Host code only: the key that names one template instantiation, the
-// launch description (key + geometry + the values launch_fused writes into the argument block), the ONE function that derives it from the
-// arguments, and the public predicates beside it so that every rule is written once.  The instantiations themselves are rows {key, kernel}
-// of one table per translation unit (kkt_fused*.hip); launch_fused (kkt_fused.hip) selects, finds the row and launches it.
+// mo_fused_select.h -- which kernel serves a call, as data.  Host code only: the key that names one template instantiation of a fused
+// kernel (fp64, its right-hand-side twins, fp32), the launch description (key + geometry + the values written into the argument block), the
+// functions that derive it from the arguments (fused_select, fused_rhs_select, fused_f32_select) with the public predicates beside them, so
+// that every rule is written once; decide_kernel, the one decision of mo_api.hip between the fused families and the generic kernel; and
+// fused_launch, the one launch tail.  The instantiations themselves are rows {key, kernel} of one table per translation unit
+// (kkt_fused*.hip); the launchers there select, then fused_launch finds the row and launches it.
 #pragma once
 #include <stdlib.h>
 
@@ -33,10 +35,12 @@ struct FusedKey {
   int jmode = JMODE_VECTOR;
   int ny = 1;               // y tiles: k <= 16 ny - 1
   int pck = 1;              // Solve kernel: carries the code of the predictor-corrector's second solve
+  int f32 = 0;              // an fp32 kernel (kkt_fused_f32.hip): named by family, nt (4 / 8), wps and pad; every other field at its default
+  int pad = 0;              // fp32 step / Solve: n below the tile grid, masked inside the kernel
 };
 constexpr bool operator==(const FusedKey& a, const FusedKey& b) {
   return a.family == b.family && a.nt == b.nt && a.wps == b.wps && a.qpl == b.qpl && a.mc == b.mc && a.jmode == b.jmode && a.ny == b.ny &&
-         a.pck == b.pck;
+         a.pck == b.pck && a.f32 == b.f32 && a.pad == b.pad;
 }
 
 struct FusedLaunch {
@@ -49,8 +53,10 @@ struct FusedLaunch {
 
 // The translation unit whose table holds a key.  A function of the key alone: the routing conditions live in fused_select only, and a row
 // written into the wrong unit's table does not compile (MO_FUSED_ROW).
-enum FusedUnit : int { UNIT_MAIN = 0, UNIT_GATHER, UNIT_NY2, UNIT_NY34, UNIT_MC4, UNIT_TINY, FUSED_UNITS };
+// (FUSED_UNITS: the fp64 units fused_table() serves; the fp32 unit's table is fused_f32_table())
+enum FusedUnit : int { UNIT_MAIN = 0, UNIT_GATHER, UNIT_NY2, UNIT_NY34, UNIT_MC4, UNIT_TINY, FUSED_UNITS, UNIT_F32 = FUSED_UNITS };
 constexpr int fused_unit(const FusedKey& k) {
+  if (k.f32) return UNIT_F32;
   if (k.family == FUSED_TINY) return UNIT_TINY;
   if (k.ny >= 3) return UNIT_NY34;
   if (k.ny == 2) return UNIT_NY2;
@@ -64,6 +70,24 @@ struct FusedRow { FusedKey key; FusedKernel kernel; };
 struct FusedTable { const FusedRow* rows; int count; };
 FusedTable fused_table_main(), fused_table_gather(), fused_table_ny2(), fused_table_ny34(), fused_table_mc4(), fused_table_tiny();   // one per unit
 FusedTable fused_table(int unit);   // kkt_fused.hip
+#define MO_FUSED_TABLE_SIZE(rows) (int)(sizeof(rows) / sizeof(rows[0]))
+
+// The one launch tail: the row of L.key in `table`, the scheduling values of L into the argument block, the ticket zeroed on the stream
+// if L asks for it, the launch.  A key without a row is an internal error: there is no fallback kernel.
+inline hipError_t fused_launch(FusedTable table, const FusedLaunch& L, const KernelArgs& a_in, hipStream_t stream) {
+  FusedKernel kernel = nullptr;
+  for (int i = 0; i < table.count && !kernel; ++i)
+    if (table.rows[i].key == L.key) kernel = table.rows[i].kernel;
+  if (!kernel) return hipErrorInvalidDeviceFunction;
+  KernelArgs a = a_in;
+  a.stagger = L.stagger; a.chain_prio = L.chain_prio; a.static_rounds = L.static_rounds;
+  if (L.zero_ticket) {
+    hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(L.block), 0, stream, a);
+  return hipGetLastError();
+}
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -143,14 +167,31 @@ inline int fused_wps(const FusedKey& k) {
 inline int fused_env_int(const char* name, int otherwise) { const char* e = getenv(name); return e ? atoi(e) : otherwise; }
 #endif
 
+// The tile grid a problem of n variables is padded to (16 nt variables), and the tile park of the fused fp64 Solve kernels beyond the 32
+// grid: the elements of one wave slot -- the nt (nt + 1) / 2 tiles of G and nt vectors a wave cannot keep in LDS between the passes.  The
+// plan allocates fused_tile_park_slots slots of it (one workgroup per CU, at most twelve waves each) and hands the kernel the slot size.
+constexpr int fused_nt(int n) { return n > 96 ? 8 : n > 64 ? 6 : n > 32 ? 4 : 2; }
+constexpr size_t fused_tile_park_slot_elems(int n) { return (size_t)(fused_nt(n) * (fused_nt(n) + 1) / 2) * 256 + (size_t)fused_nt(n) * 64; }
+constexpr size_t fused_tile_park_slots(int num_cus) { return (size_t)num_cus * 12; }
+
+// Static rounds up to this many problems per wave (mo_kernels.h; measured): the caller's value, else equal-cost work
+// (step, Iterate, residual, linearisation) splits statically further than a Solve, whose problems need different numbers of passes.
+inline int fused_static_rounds(const KernelArgs& a) {
+  return a.static_rounds >= 0 ? a.static_rounds : a.mode == MODE_SOLVE ? (a.n > 32 ? 2 : 6) : (a.n > 32 ? 8 : 32);
+}
+// The work counter is zeroed on the stream in front of the kernel -- unless the launch is certain to run in static rounds, which never
+// touch it: every kernel has at least 4 waves per workgroup and min(CUs, ceil(batch / 4)) workgroups, so batch <= rounds x 4 x workgroups
+// is static whatever the instantiation (the kernels test batch <= rounds x waves).  One enqueued operation less per small launch.
+inline bool fused_zero_ticket(int static_rounds, long long batch, int num_cus) {
+  return !(static_rounds > 0 && batch <= (long long)static_rounds * 4 * fused_grid(batch, num_cus));
+}
+
 // Everything launch_fused needs to know about a launch of supported arguments (fused_supported(a, MO_F64) holds).
 // (static: an A/B library links objects built with and without -DMO_TUNING, tools/ab_build.sh, and each must keep its own copy)
 static inline FusedLaunch fused_select(const KernelArgs& a, int num_cus) {
   FusedLaunch L{};
   const bool solve = a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL;
-  // static rounds up to this many problems per wave (mo_kernels.h; measured): equal-cost work (step, Iterate, residual,
-  // linearisation) splits statically further than a Solve, whose problems need different numbers of passes
-  L.static_rounds = a.static_rounds >= 0 ? a.static_rounds : a.mode == MODE_SOLVE ? (a.n > 32 ? 2 : 6) : (a.n > 32 ? 8 : 32);
+  L.static_rounds = fused_static_rounds(a);
   // start stagger and chain priority: the 64-variable grid of the step kernel with J-level input (the BASELINE configs[2] / [4] shape);
   // measured neutral elsewhere
   const bool headline_shape = a.mode == MODE_STEP && a.J && a.n > 32 && a.n <= 64;
@@ -173,7 +214,7 @@ static inline FusedLaunch fused_select(const KernelArgs& a, int num_cus) {
     L.zero_ticket = true;         // the one-tile kernel hands out tickets of up to 64 problems whatever the size
   } else {
     key.family = a.mode == MODE_LINEARIZE ? FUSED_LINEARIZE : solve ? FUSED_SOLVE : FUSED_STEP;
-    key.nt = a.n > 96 ? 8 : a.n > 64 ? 6 : a.n > 32 ? 4 : 2;   // the tile grid the problem is padded to
+    key.nt = fused_nt(a.n);
     const bool qp = key.family != FUSED_LINEARIZE;
     key.qpl = !a.J;
     // one y tile up to k = 15, two up to 31, three / four up to 47 / 63; every y tile but the last is a full 16-pivot tile
@@ -210,10 +251,7 @@ static inline FusedLaunch fused_select(const KernelArgs& a, int num_cus) {
     if (key.family == FUSED_SOLVE && key.ny == 2 && key.nt == 4 && key.mc <= 2 && env_ny2_solve_wps == 1) { key.wps = 1; key.pck = 1; }
 #endif
     L.problems_per_wg = 4;
-    // The work counter is zeroed on the stream in front of the kernel -- unless the launch is certain to run in static rounds, which never
-    // touch it: every kernel has at least 4 waves per workgroup and min(CUs, ceil(batch / 4)) workgroups, so batch <= rounds x 4 x workgroups
-    // is static whatever the instantiation (the kernels test batch <= rounds x waves).  One enqueued operation less per small launch.
-    L.zero_ticket = !(L.static_rounds > 0 && a.batch <= (long long)L.static_rounds * 4 * fused_grid(a.batch, num_cus));
+    L.zero_ticket = fused_zero_ticket(L.static_rounds, a.batch, num_cus);
   }
   L.grid = fused_grid(a.batch, num_cus, L.problems_per_wg);   // one workgroup of 4 wps waves per CU; problems are pulled from the ticket counter
   L.block = 256u * key.wps;
@@ -229,8 +267,7 @@ inline const char* fused_name(const FusedKey& k) {
        {"fused_solve_qp_f64_n32", "fused_solve_qp_f64_n64", "fused_solve_qp_f64_n96", "fused_solve_qp_f64_n128"}}};
   return names[k.family == FUSED_SOLVE][k.qpl][k.nt / 2 - 1];
 }
-static inline const char* fused_name(const KernelArgs& a, int) {
-  const FusedKey key = fused_select(a, 1).key;
+inline const char* fused_name(const KernelArgs& a, const FusedKey& key) {
   if (key.family == FUSED_TINY) {  // one instantiation for every mode and input level: the name tells what it was asked for
     const bool solve = a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL;
     if (!a.J) return solve ? "fused_solve_qp_tiny_f64" : "fused_qp_tiny_f64";
@@ -238,6 +275,7 @@ static inline const char* fused_name(const KernelArgs& a, int) {
   }
   return fused_name(key);
 }
+static inline const char* fused_name(const KernelArgs& a, int) { return fused_name(a, fused_select(a, 1).key); }
 
 hipError_t launch_fused(const KernelArgs& a, int dtype, int num_cus, hipStream_t stream);   // kkt_fused.hip
 
@@ -275,5 +313,88 @@ inline const char* fused_rhs_name(const FusedKey& k) {
 // function only, and a supported key without a row is an error (launch_fused_rhs), never another kernel.
 FusedTable fused_rhs_table();                                                                    // kkt_fused_rhs.hip
 hipError_t launch_fused_rhs(const KernelArgs& a, int dtype, int num_cus, hipStream_t stream);   // kkt_fused_rhs.hip
+
+// ---- the fused fp32 kernels (kkt_fused_f32.hip): step, Solve / Iterate / residual and linearisation on the 64 / 128 grids -------------
+inline bool fused_f32_supported(const KernelArgs& a, int dtype) {
+  if (dtype != MO_F32) return false;
+  if (a.mode == MODE_LINEARIZE && a.n != 128 && a.n != 64) return false;
+  if (a.n < 4 || a.n > 128 || (a.n & 3)) return false;   // step / Solve / Iterate / residual: any multiple of 4, padded inside the kernels to the 64 / 128 grid
+  if (a.mode == MODE_LINEARIZE) {  // kkt_fused_f32_linearize_kernel: packed row-major J, rows in whole 4-row groups
+    return a.J && a.ticket && a.G_out && a.c_out && a.J_row_major && a.J_ld == a.n && a.m_r > 0 && !(a.m_r & 3) && aligned16(a.J) &&
+           !(a.J_stride & 3) && aligned16(a.r) && !(a.r_stride & 3) && a.G_out_ld >= a.n;
+  }
+  if (a.k > 16 || a.m > 64 || a.m < 0) return false;
+  if (!a.ticket || !a.vars) return false;
+  if (a.mode == MODE_SOLVE || a.mode == MODE_ITERATE || a.mode == MODE_RESIDUAL) {  // kkt_fused_f32_solve_kernel
+    if (a.mode == MODE_RESIDUAL ? ((a.flags & ~MO_STEP_NO_INEQUALITIES) != 0 || !a.r_out) : a.flags != 0) return false;
+    if (a.J) {
+      if (!a.J_row_major || a.J_ld != a.n || a.m_r <= 0) return false;
+      if (!aligned16(a.J) || (a.J_stride & 3)) return false;
+    } else if (!a.G || !a.c || a.G_ld < a.n) {
+      return false;
+    }
+    return true;
+  }
+  if ((a.flags & ~MO_STEP_NO_INEQUALITIES) != 0 || a.mode != MODE_STEP) return false;
+  if (!a.delta || !a.J) return false;
+  if (!a.J_row_major || a.J_ld != a.n || a.m_r <= 0) return false;
+  if (!aligned16(a.J) || (a.J_stride & 3)) return false;
+  return true;
+}
+
+inline const char* fused_f32_name(const KernelArgs& a) {
+  if (a.mode == MODE_LINEARIZE) return a.n > 64 ? "fused_linearize_f32_n128" : "fused_linearize_f32_n64";
+  if (a.mode == MODE_STEP) return a.n > 64 ? "fused_mfma_f32_n128" : "fused_mfma_f32_n64";
+  if (!a.J) return a.n > 64 ? "fused_solve_qp_f32_n128" : "fused_solve_qp_f32_n64";
+  return a.n > 64 ? "fused_solve_mfma_f32_n128" : "fused_solve_mfma_f32_n64";
+}
+
+// The launch of supported arguments (fused_f32_supported(a, MO_F32) holds).  Waves per SIMD: the 128 grid runs the step and the
+// linearisation at two (the step: 255 VGPRs, no scratch -- the 216 accumulator registers + operands just fit) and Solve / Iterate / residual
+// at one (216 tile registers + the state); the 64 grid runs everything at three.  PAD: n below the grid.
+static inline FusedLaunch fused_f32_select(const KernelArgs& a, int num_cus) {
+  FusedLaunch L{};
+  L.static_rounds = fused_static_rounds(a);
+  L.chain_prio = a.chain_prio;   // (as handed in: the fp32 kernels have no chain priority of their own)
+  FusedKey& key = L.key;
+  const bool big = a.n > 64;
+  key.family = a.mode == MODE_LINEARIZE ? FUSED_LINEARIZE : a.mode == MODE_STEP ? FUSED_STEP : FUSED_SOLVE;
+  key.f32 = 1;
+  key.nt = big ? 8 : 4;
+  key.wps = !big ? 3 : key.family == FUSED_SOLVE ? 1 : 2;
+  key.pad = key.family != FUSED_LINEARIZE && a.n != 16 * key.nt;
+#ifdef MO_TUNING
+  static const int env_stagger = fused_env_int("MO_FUSED_F32_STAGGER", -1);
+  if (env_stagger >= 0) L.stagger = env_stagger;
+  static const int env_wps = fused_env_int("MO_FUSED_F32_WPS", 0);   // the step on the 128 grid at one wave per SIMD
+  if (key.family == FUSED_STEP && big && env_wps == 1) key.wps = 1;
+#endif
+  L.problems_per_wg = 4;
+  L.zero_ticket = fused_zero_ticket(L.static_rounds, a.batch, num_cus);
+  L.grid = fused_grid(a.batch, num_cus);
+  L.block = 256u * key.wps;
+  return L;
+}
+FusedTable fused_f32_table();                                                       // kkt_fused_f32.hip
+hipError_t launch_fused_f32(const KernelArgs& a, int num_cus, hipStream_t stream);   // kkt_fused_f32.hip
+
+// ---- which kernel serves a call ------------------------------------------------------------------------------------------------------
+// The ONE decision of mo_api.hip, from the arguments, the plan's dtype and its force-generic flag: MODE_RHS (mo_kkt_solve) runs the step
+// kernel's right-hand-side twin where one exists and the generic kernel everywhere else; every other mode the fused fp64 kernels, then the
+// fused fp32 kernels, then the generic kernel.  `launch` is set for the fused kinds; `name` is what the plan's kernel queries report.
+enum KernelKind : int { KERNEL_GENERIC = 0, KERNEL_FUSED_F64, KERNEL_FUSED_F32, KERNEL_FUSED_RHS };
+struct KernelDecision { int kind; FusedLaunch launch; const char* name; };
+static inline KernelDecision decide_kernel(const KernelArgs& a, int dtype, bool force_generic, int num_cus) {
+  KernelDecision d{KERNEL_GENERIC, FusedLaunch{}, "generic"};
+  if (force_generic) return d;
+  if (a.mode == MODE_RHS) {
+    if (fused_rhs_supported(a, dtype)) { d.kind = KERNEL_FUSED_RHS; d.launch = fused_rhs_select(a, num_cus); d.name = fused_rhs_name(d.launch.key); }
+  } else if (fused_supported(a, dtype)) {
+    d.kind = KERNEL_FUSED_F64; d.launch = fused_select(a, num_cus); d.name = fused_name(a, d.launch.key);
+  } else if (fused_f32_supported(a, dtype)) {
+    d.kind = KERNEL_FUSED_F32; d.launch = fused_f32_select(a, num_cus); d.name = fused_f32_name(a);
+  }
+  return d;
+}
 
 }  // namespace mo

@@ -55,7 +55,7 @@ struct KernelArgs {
   long long skip_active;  // how many of them are still active (host-side count from the previous outer iteration; -1: unknown)
   // fused kernel: device work counter (plan-owned, zeroed on the launch stream before every launch)
   unsigned long long* ticket;
-  int stagger;     // fused step kernel: start offset between the waves that share a SIMD, in units of 127 x 64 cycles (set by launch_fused from fused_select)
+  int stagger;     // fused step kernel: start offset between the waves that share a SIMD, in units of 127 x 64 cycles (set by fused_launch from the selected FusedLaunch)
   int chain_prio;  // fused step kernel: s_setprio 1 while a wave is in the elimination / substitution chains
   int static_rounds;  // fused kernels: launches of at most this many problems per wave are split statically, round by round, with no ticket
                       // (mo_api.hip hands over -1 = "the launcher decides" or MO_FUSED_STATIC_ROUNDS; 0 = tickets always).  The grids are
@@ -72,6 +72,8 @@ struct KernelArgs {
   // so the kernarg offsets the other modes read are what they were.
   const void* rhs; long long rhs_stride;
 };
+
+constexpr size_t kLdsBytes = 160 * 1024;   // the LDS of a gfx950 CU: what one workgroup of the LDS-resident kernels may use
 
 // shape-generic LDS kernel (any n,k,m,m_r that fits LDS), kkt_generic.hip
 size_t generic_lds_bytes(const KernelArgs& a, int elem_size);
@@ -104,12 +106,7 @@ inline unsigned fused_grid(long long batch, int num_cus, int problems_per_wg = 4
   return (unsigned)grid;
 }
 
-// fused single-wave MFMA kernels for fixed tile grids (fp64): mo_fused_select.h
-
-// fused single-wave fp32 step kernel for n = 64 / 128 (J-level input), kkt_fused_f32.hip
-bool fused_f32_supported(const KernelArgs& a, int dtype);
-const char* fused_f32_name(const KernelArgs& a);
-hipError_t launch_fused_f32(const KernelArgs& a, int num_cus, hipStream_t stream);
+// fused single-wave MFMA kernels for fixed tile grids (fp64, its right-hand-side twins, fp32): mo_fused_select.h
 
 // small per-problem kernels around the QP (LinearizeAndFillQP tail, EvaluateNonlinearErrors, ComputeQPCostDerivative), nls_kernels.hip
 struct AuxArgs {

@@ -1,5 +1,6 @@
-// fused_dispatch_driver.cpp OUT_DIR -- walks the lattice of fused_dispatch_lattice.h through fused_supported / fused_select / fused_name and
-// the units' kernel tables (host objects only: nothing is launched) and writes, for tests/test_fused_dispatch_cpu.py:
+// fused_dispatch_driver.cpp OUT_DIR -- walks the lattice of fused_dispatch_lattice.h through mo::decide_kernel (the decision mo_api.hip
+// takes: fused_supported / fused_select / fused_name behind it) with an fp64 plan and the units' kernel tables (host objects only: nothing
+// is launched) and writes, for tests/test_fused_dispatch_cpu.py:
 //   OUT_DIR/records.txt   distinct launch descriptions, one per line, tab-separated in the field order of the golden; line 0: unsupported
 //   OUT_DIR/index.u16     one record index per lattice point, in enumeration order
 //   OUT_DIR/tables.txt    every table row: unit, the key, how many lattice points selected it
@@ -36,10 +37,17 @@ int main(int argc, char** argv) {
   intern("unsupported");
   std::vector<std::vector<long long>> hits(mo::FUSED_UNITS);
   for (int u = 0; u < mo::FUSED_UNITS; ++u) hits[u].assign(mo::fused_table(u).count, 0);
+  long long forced_not_generic = 0, other_fused_kind = 0;
 
   lattice::for_each_point([&](const mo::KernelArgs& a) {
-    if (!mo::fused_supported(a, MO_F64)) { idx.push_back(0); return; }
-    const mo::FusedLaunch L = mo::fused_select(a, lattice::kNumCus);
+    const mo::KernelDecision d = mo::decide_kernel(a, MO_F64, false, lattice::kNumCus);
+    if (mo::decide_kernel(a, MO_F64, true, lattice::kNumCus).kind != mo::KERNEL_GENERIC) ++forced_not_generic;
+    if (d.kind != mo::KERNEL_FUSED_F64) {   // an fp64 plan outside MODE_RHS: the fused fp64 kernels or the generic one, nothing else
+      if (d.kind != mo::KERNEL_GENERIC) ++other_fused_kind;
+      idx.push_back(0);
+      return;
+    }
+    const mo::FusedLaunch& L = d.launch;
     const int unit = mo::fused_unit(L.key);
     const mo::FusedTable t = mo::fused_table(unit);
     int found = 0;
@@ -47,10 +55,11 @@ int main(int argc, char** argv) {
       if (t.rows[i].key == L.key && t.rows[i].kernel) { ++hits[unit][i]; ++found; }
     char buf[256];
     snprintf(buf, sizeof buf, "\t%u\t%u\t%d\t%d\t%d\t%d\t%s\t%d", L.grid, L.block, (int)L.zero_ticket, L.stagger, L.chain_prio, L.static_rounds,
-             mo::fused_name(a, MO_F64), found);
+             d.name, found);
     idx.push_back((unsigned short)intern(key_text(L.key) + buf));
   });
   if (recs.size() > 65535) return 3;
+  if (forced_not_generic || other_fused_kind) return 5;
 
   FILE* f = fopen((out + "/records.txt").c_str(), "w");
   if (!f) return 4;

@@ -1,5 +1,5 @@
-// fused_rhs_dispatch_driver.cpp OUT_DIR -- walks a shape lattice of mo_kkt_solve arguments (MODE_RHS) through fused_rhs_supported /
-// fused_rhs_select / fused_rhs_name and the table of kkt_fused_rhs.hip (host objects only: nothing is launched) and writes, for
+// fused_rhs_dispatch_driver.cpp OUT_DIR -- walks a shape lattice of mo_kkt_solve arguments (MODE_RHS) through mo::decide_kernel (the
+// decision mo_api.hip takes: fused_rhs_supported / fused_rhs_select / fused_rhs_name behind it) and the table of kkt_fused_rhs.hip (host objects only: nothing is launched) and writes, for
 // tests/test_fused_rhs_dispatch_cpu.py:
 //   OUT_DIR/shapes.txt    one line per (n, k, m, kind, m_r, flags, no_tiny): supported, the key, the name, rows of the table with that key
 //   OUT_DIR/counters.txt  name <tab> count: points walked and every violation the walk counts itself
@@ -34,7 +34,7 @@ int main(int argc, char** argv) {
   const mo::FusedTable table = mo::fused_rhs_table();
   std::vector<long long> hits(table.count, 0);
   long long points = 0, supported = 0, supported_without_step = 0, launch_differs = 0, rows_not_one = 0, f32_supported = 0, not_rhs_mode_supported = 0,
-            null_rhs_supported = 0, varies_with_batch = 0;
+            null_rhs_supported = 0, varies_with_batch = 0, decision_differs = 0;
   FILE* f = fopen((out + "/shapes.txt").c_str(), "w");
   if (!f) return 4;
   for (int n : kN) for (int k : kK) for (int m : kM) for (int kind = 0; kind < lattice::kInputKinds; ++kind)
@@ -47,12 +47,15 @@ int main(int argc, char** argv) {
         a.alpha = nullptr; a.mu = nullptr;
         a.rhs = (const void*)(uintptr_t)0x20008; a.rhs_stride = a.vars_stride;   // 8-byte aligned only
         ++points;
-        if (mo::fused_rhs_supported(a, MO_F32)) ++f32_supported;
+        if (mo::fused_rhs_supported(a, MO_F32) || mo::decide_kernel(a, MO_F32, false, lattice::kNumCus).kind != mo::KERNEL_GENERIC) ++f32_supported;
         mo::KernelArgs b = a; b.mode = mo::MODE_STEP; b.flags = flags & ~(unsigned)MO_KKT_TRANSPOSE;
         if (mo::fused_rhs_supported(b, MO_F64)) ++not_rhs_mode_supported;
         b = a; b.rhs = nullptr;
         if (mo::fused_rhs_supported(b, MO_F64)) ++null_rhs_supported;
-        const bool sup = mo::fused_rhs_supported(a, MO_F64);
+        const mo::KernelDecision d = mo::decide_kernel(a, MO_F64, false, lattice::kNumCus);
+        const bool sup = d.kind == mo::KERNEL_FUSED_RHS;
+        if (sup != mo::fused_rhs_supported(a, MO_F64) || (!sup && d.kind != mo::KERNEL_GENERIC) ||
+            mo::decide_kernel(a, MO_F64, true, lattice::kNumCus).kind != mo::KERNEL_GENERIC) ++decision_differs;
         if (shape_supported >= 0 && shape_supported != (int)sup) ++varies_with_batch;
         shape_supported = sup;
         if (!sup) continue;
@@ -60,13 +63,13 @@ int main(int argc, char** argv) {
         // the step the same arguments would launch
         mo::KernelArgs s = a; s.mode = mo::MODE_STEP; s.flags = flags & ~(unsigned)MO_KKT_TRANSPOSE; s.rhs = nullptr;
         if (!mo::fused_supported(s, MO_F64)) { ++supported_without_step; continue; }
-        const mo::FusedLaunch Ls = mo::fused_select(s, lattice::kNumCus), Lr = mo::fused_rhs_select(a, lattice::kNumCus);
+        const mo::FusedLaunch Ls = mo::fused_select(s, lattice::kNumCus), Lr = d.launch;
         if (launch_text(Ls) != launch_text(Lr)) ++launch_differs;
         found = 0;
         for (int i = 0; i < table.count; ++i)
           if (table.rows[i].key == Lr.key && table.rows[i].kernel) { ++hits[i]; ++found; }
         if (found != 1) ++rows_not_one;
-        key = Lr.key; name = mo::fused_rhs_name(Lr.key);
+        key = Lr.key; name = d.name;
       }
       fprintf(f, "%d\t%d\t%d\t%d\t%d\t%u\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%d\n", n, k, m, kind, kind == 0 ? 0 : kMr[mr_i], flags, no_tiny, shape_supported,
               key.nt, key.wps, key.qpl, key.mc, key.jmode, key.ny, name, found);
@@ -75,8 +78,9 @@ int main(int argc, char** argv) {
   f = fopen((out + "/counters.txt").c_str(), "w");
   if (!f) return 4;
   fprintf(f, "points\t%lld\nsupported\t%lld\nsupported_without_step\t%lld\nlaunch_differs\t%lld\nrows_not_one\t%lld\nf32_supported\t%lld\n"
-             "not_rhs_mode_supported\t%lld\nnull_rhs_supported\t%lld\nvaries_with_batch\t%lld\n",
-          points, supported, supported_without_step, launch_differs, rows_not_one, f32_supported, not_rhs_mode_supported, null_rhs_supported, varies_with_batch);
+             "not_rhs_mode_supported\t%lld\nnull_rhs_supported\t%lld\nvaries_with_batch\t%lld\ndecision_differs\t%lld\n",
+          points, supported, supported_without_step, launch_differs, rows_not_one, f32_supported, not_rhs_mode_supported, null_rhs_supported, varies_with_batch,
+          decision_differs);
   fclose(f);
   f = fopen((out + "/table.txt").c_str(), "w");
   if (!f) return 4;

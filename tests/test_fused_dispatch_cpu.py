@@ -1,5 +1,5 @@
 """The fused fp64 dispatch is data (csrc/mo_fused_select.h + one kernel table per translation unit): this test walks a shape lattice through
-fused_supported / fused_select / fused_name and the tables on the CPU and compares every point with a recording of what the hand-written
+decide_kernel (the decision mo_api.hip takes: fused_supported / fused_select / fused_name behind it) and the tables on the CPU and compares every point with a recording of what the hand-written
 launchers of commit 662741eb chose (tests/golden/fused_dispatch: distinct launch descriptions + one index per lattice point, keys in
 normalised form -- template defaults written out, the constant sweep-flavour argument of that commit dropped).
 

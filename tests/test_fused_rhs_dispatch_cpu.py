@@ -1,4 +1,4 @@
-"""The dispatch of mo_kkt_solve's fused kernels is data (csrc/mo_fused_select.h: fused_rhs_supported / fused_rhs_select, and the table of
+"""The dispatch of mo_kkt_solve's fused kernels is data (csrc/mo_fused_select.h: fused_rhs_supported / fused_rhs_select behind decide_kernel, and the table of
 csrc/kkt_fused_rhs.hip): the right-hand-side kernel of a shape is the twin of that shape's step kernel.  This test walks a shape lattice on the
 CPU (tests/cpp/fused_rhs_dispatch_driver.cpp against the current sources, linked with the host-only object of the new unit; nothing is
 launched) and checks the rule from both sides: what the driver counts itself (supported implies the step is supported, equal launch
@@ -58,7 +58,7 @@ def test_supported_points_are_the_twins_of_their_step(walk):
     _, c, _ = walk
     assert c["points"] > 500000 and c["supported"] > 50000, c
     for name in ("supported_without_step", "launch_differs", "rows_not_one", "f32_supported", "not_rhs_mode_supported", "null_rhs_supported",
-                 "varies_with_batch"):
+                 "varies_with_batch", "decision_differs"):
         assert c[name] == 0, (name, c)
 
 

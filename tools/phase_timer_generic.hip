@@ -54,7 +54,7 @@ int main(int argc, char** argv) {
   a.vars = vars; a.vars_stride = V; a.mu = mu; a.mu_stride = 1; a.tau = 0.995;
   a.delta = delta; a.delta_stride = V; a.alpha = alpha; a.status = status; a.debug = dbg; a.ticket = ticket;
   hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, 0));
-  if (mo::generic_needs_large(a, 8)) {  // H in a global workspace per workgroup of the persistent grid (what mo_api.hip's launch_chosen allocates)
+  if (mo::generic_needs_large(a, 8)) {  // H in a global workspace per workgroup of the persistent grid (what mo_api.hip's launch hands over)
     const size_t per_wg = mo::generic_large_workspace_elems(a);
     const size_t wgs = (size_t)mo::generic_large_grid(a, 8, prop.multiProcessorCount);
     CK(hipMalloc(&a.H_work, wgs * per_wg * 8));

@@ -30,6 +30,7 @@
 
 #include <type_traits>
 
+#include "mo_fused_device.h"
 #include "mo_fused_select.h"
 
 namespace mo {
@@ -37,21 +38,6 @@ namespace {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef double d4 __attribute__((ext_vector_type(4)));
-
-// Phase stamps exist only in the diagnostic build of tools/phase_timer.hip; the product kernel executes none.
-#ifdef MO_FUSED_STAMPS
-#define MO_STAMP(i)                                                                                   \
-  do {                                                                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-    unsigned long long t__;                                                                           \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");                       \
-    stamp_acc[i] += t__ - stamp_prev;                                                                 \
-    stamp_prev = t__;                                                                                 \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-  } while (0)
-#else
-#define MO_STAMP(i) do { } while (0)
-#endif
 
 constexpr int kRC = 15;  // tile column that carries the right-hand side in the [A_eq^T | rhs] tile column
 
@@ -77,24 +63,12 @@ template <int CTRL> __device__ inline double dpp_f64(double v) {
 }
 // Sum / min over the 16 lanes of each row, result in every lane of the row.  DPP only (no LDS crossbar):
 // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror.
-// MO_ROWSUM_SWIZZLE (A/B builds): the same butterfly (bit-identical sums) through ds_swizzle_b32 -- the exchange goes over the LDS crossbar
-// (two LDS-pipe instructions per step) and only the four adds stay on the VALU: 4 instead of 12 VALU instructions per row sum.
-template <int PATTERN> __device__ inline double swizzle_f64(double v) {
-  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), PATTERN), hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), PATTERN);
-  return __hiloint2double(hi, lo);
-}
+// (The same butterfly through ds_swizzle_b32 was measured and rejected)
 __device__ inline double row_sum(double v) {
-#ifdef MO_ROWSUM_SWIZZLE
-  v += swizzle_f64<0x041F>(v);   // bit mode: lane ^ 1
-  v += swizzle_f64<0x081F>(v);   // lane ^ 2
-  v += swizzle_f64<0x101F>(v);   // lane ^ 4
-  v += swizzle_f64<0x201F>(v);   // lane ^ 8
-#else
   v += dpp_f64<0xB1>(v);
   v += dpp_f64<0x4E>(v);
   v += dpp_f64<0x141>(v);
   v += dpp_f64<0x140>(v);
-#endif
   return v;
 }
 // FOUR row sums at once (round 4).  p0 .. p3 are four values per lane whose sums over the 16 lanes of each row are wanted; the plain way is four
@@ -158,12 +132,6 @@ __device__ inline double cross_row_min(double v) {
   const double s = fmin(p.a, p.b);
   const Rows2 q = swap32_f64(s);
   return fmin(q.a, q.b);
-}
-// Row SG of v replicated into all four rows.
-template <int SG> __device__ inline double bcast_from_row(double v) {
-  const Rows2 p = swap16_f64(v);                  // p.a = [v0,v0,v2,v2], p.b = [v1,v1,v3,v3]
-  const Rows2 q = swap32_f64((SG & 1) ? p.b : p.a);  // q.a = [y0,y1,y0,y1], q.b = [y2,y3,y2,y3]
-  return (SG & 2) ? q.b : q.a;
 }
 __device__ inline double rcp_f64(double d) {
   double q = __builtin_amdgcn_rcp(d);
@@ -275,57 +243,23 @@ __device__ inline void load_g_tiles(const double* G, int ld, const double* cg, i
   }
 }
 
-// Lane index recomputed on the spot (two VALU ops).  The asm is volatile on purpose: nothing derived from it can be hoisted
-// out of a loop and kept live in VGPRs the tiles need.
-__device__ inline int lane_id() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-
-// The kernel's argument block as the hardware sees it (kernarg segment, constant address space), behind a pointer the
-// compiler cannot see through: loads through it stay where they are written instead of being hoisted to the kernel entry.
-typedef const KernelArgs __attribute__((address_space(4)))* KArgs;
-__device__ inline KArgs fresh_args() {
-  KArgs p = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return p;
-}
-
-// LDS-DMA: every lane's 16 bytes at `gsrc` land at LDS byte address lds_dst + 16 * lane (no VGPR destination).
-// hipcc does not count this load: its completion is waited for by hand with wait_vmcnt<N>() (loads retire in order).
-__device__ inline void dma16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
 // Scalar-base forms: global address = sbase (wave-uniform, SGPR pair) + voff (per-lane 32-bit byte offset) + IMM; the LDS
 // address is M0 + IMM + 16 * lane (the instruction offset applies to BOTH sides, found the hard way).  The address
 // arithmetic of a stream then lives on the scalar unit; the VALU (which the f64 MFMA shares) sees none of it.
 // The base and the LDS address are wave-uniform by construction; readfirstlane says so to hipcc where its divergence analysis
 // gives up (values carried around a loop with data-dependent exits) -- it folds away when the value already sits in SGPRs.
 __device__ inline const void* uniform_ptr(const void* p) {
-  const unsigned long long b = (unsigned long long)(uintptr_t)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-  return (const void*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
+  return (const void*)(uintptr_t)uniform64((unsigned long long)(uintptr_t)p);
 }
 // The J stream's loads carry the non-temporal hint: J is read once, by one CU, and without the hint it washes the lines other waves
 // re-read every pass of a Solve (spills, the parked tiles that did not fit the LDS) out of the XCD's L2 -- measured on the cfg 3 Solve:
-// FETCH_SIZE 4.30 -> 3.23 GB per launch, +0.8 % solves/s; the step kernel is indifferent (A/B builds: -DMO_J_NO_NT).
-#ifdef MO_J_NO_NT
-#define MO_J_POLICY ""
-#else
-#define MO_J_POLICY " nt"
-#endif
+// FETCH_SIZE 4.30 -> 3.23 GB per launch, +0.8 % solves/s; the step kernel is indifferent.
 template <int IMM> __device__ inline void dma16_s(const void* sbase_in, unsigned voff, unsigned lds_dst_in) {
   const void* sbase = uniform_ptr(sbase_in);
   const unsigned lds_dst = __builtin_amdgcn_readfirstlane(lds_dst_in);
   unsigned keep;
   asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4" MO_J_POLICY "\n\ts_mov_b32 m0, %0"
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4 nt\n\ts_mov_b32 m0, %0"
       : "=&s"(keep)
       : "v"(voff), "s"(sbase), "s"(lds_dst), "i"(IMM)
       : "memory");
@@ -338,15 +272,6 @@ __device__ inline void dma4_s(const void* sbase_in, unsigned voff, unsigned lds_
       "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
       : "=&s"(keep)
       : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
-// Same with 4 bytes per lane: LDS byte address lds_dst + 4 * lane.  64 lanes move 32 consecutive doubles.
-__device__ inline void dma4(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
       : "memory");
 }
 // `count` consecutive doubles (count <= 256, wave-uniform) from global memory to LDS without touching a VGPR destination.
@@ -365,8 +290,6 @@ __device__ inline void dma_doubles(const double* src, unsigned lds_dst, int coun
       if (lane + 64 * c < 2 * count) dma4_s(reinterpret_cast<const char*>(src) + 256 * c, voff, lds_dst + 256 * c);
   }
 }
-template <int N> __device__ inline void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-__device__ inline void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }  // single-wave workgroup
 
 // Symmetric sweep of pivots 0..NPIV-1 of a symmetric 16x16 tile held in the C/D layout.  Afterwards the swept block holds
 // -T11^-1, the swept x unswept block T11^-1 T12 (the solution for an augmented right-hand-side column) and the unswept
@@ -378,12 +301,7 @@ __device__ inline void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "me
 // Pad behind an EXEC-masked VALU write inside an asm block.  What the next instruction may need: a DPP read of the VGPR just written
 // (2 wait states: the s_mov_b64 that restores EXEC is one, `s_nop 0` the other).  The 5 wait states of "EXEC written -> DPP" apply to
 // VALU writes of EXEC (v_cmpx) only; an s_mov to EXEC is interlocked by the hardware (hipcc itself puts DPP ops right behind
-// s_or_b64 exec).  Rounds 1-2 padded with `s_nop 4`; A/B builds restore that with -DMO_MASKED_PAD_4.
-#ifdef MO_MASKED_PAD_4
-#define MO_MASKED_PAD "4"
-#else
-#define MO_MASKED_PAD "0"
-#endif
+// s_or_b64 exec).  Rounds 1-2 padded with `s_nop 4`.
 // 64-bit helpers for the lean sweep: one v_mov_b64_dpp instead of two 32-bit DPP movs, and EXEC-masked v_mov_b64
 // instead of v_cndmask_b32 pairs.  The asm blocks restore EXEC and end with the wait states a following DPP op needs.
 template <int LANE_IN_ROW> __device__ inline double row_bcast64(double v) {
@@ -394,14 +312,14 @@ template <int LANE_IN_ROW> __device__ inline double row_bcast64(double v) {
 template <unsigned long long MASK> __device__ inline void masked_set(double& dst, double src) {  // dst = src in the lanes of MASK
   unsigned long long save;
   asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\tv_mov_b64 %[d], %[s]\n\t"
-               "s_mov_b64 exec, %[sv]\n\ts_nop " MO_MASKED_PAD
+               "s_mov_b64 exec, %[sv]\n\ts_nop 0"
                : [d] "+v"(dst), [sv] "=&s"(save)
                : [s] "v"(src), [lo] "i"((unsigned)(MASK & 0xffffffffull)), [hi] "i"((unsigned)(MASK >> 32)));
 }
 template <unsigned long long MASK> __device__ inline void masked_set_neg(double& dst, double src) {  // dst = -src in the lanes of MASK
   unsigned long long save;  // v_max_f64 with both operands negated: the negation rides on the source modifiers (no xor + mov)
   asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\tv_max_f64 %[d], -%[s], -%[s]\n\t"
-               "s_mov_b64 exec, %[sv]\n\ts_nop " MO_MASKED_PAD
+               "s_mov_b64 exec, %[sv]\n\ts_nop 0"
                : [d] "+v"(dst), [sv] "=&s"(save)
                : [s] "v"(src), [lo] "i"((unsigned)(MASK & 0xffffffffull)), [hi] "i"((unsigned)(MASK >> 32)));
 }
@@ -410,7 +328,7 @@ template <unsigned long long MASK> __device__ inline void masked_zero4(d4& T) { 
   double t0 = T[0], t1 = T[1], t2 = T[2], t3 = T[3];
   asm volatile(
       "s_mov_b64 %[sv], exec\n\ts_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\tv_mov_b64 %[a], 0\n\tv_mov_b64 %[b], 0\n\t"
-      "v_mov_b64 %[c], 0\n\tv_mov_b64 %[d], 0\n\ts_mov_b64 exec, %[sv]\n\ts_nop " MO_MASKED_PAD
+      "v_mov_b64 %[c], 0\n\tv_mov_b64 %[d], 0\n\ts_mov_b64 exec, %[sv]\n\ts_nop 0"
       : [a] "+v"(t0), [b] "+v"(t1), [c] "+v"(t2), [d] "+v"(t3), [sv] "=&s"(save)
       : [lo] "i"((unsigned)(MASK & 0xffffffffull)), [hi] "i"((unsigned)(MASK >> 32)));
   T[0] = t0; T[1] = t1; T[2] = t2; T[3] = t3;
@@ -428,11 +346,7 @@ __device__ inline void sweep_step_lean(d4& T, double& bad, int g, int j) {
   double inv = __builtin_amdgcn_rcp(d);
   inv = fma(inv, fma(-d, inv, 1.0), inv);  // one Newton step: |inv d - 1| < 2e-15 (tools/microbench.hip)
   asm volatile("v_fma_f64 %0, %1, 0, %0" : "+v"(bad) : "v"(inv));  // volatile: hipcc would sink sixteen of these to the end
-#ifdef MO_SWEEP_VALU_ROW   // A/B builds: the row broadcast on the VALU (four v_permlane swaps) instead of over the LDS crossbar (two ds_bpermute)
-  double rk = bcast_from_row<src_g>(rowreg) * inv;
-#else
   double rk = bpermute_f64((16 * src_g + j) * 4, rowreg) * inv;  // T(k, j) / d for this lane's column j, in every row
-#endif
   masked_set_neg<mcol>(rk, inv);
   double f[4];
 #pragma unroll
@@ -613,21 +527,9 @@ struct JStream {
   // kernels with a second y tile on this grid (55 tiles, heavy spilling) did exactly that and their Solve differed from run to run, so
   // they keep the builtin; for the others tools/isa_lint.py checks every listing: no instruction but an MFMA may touch the destination
   // registers of a VGPR-form MFMA inside the blocks that hold one.
-#ifdef MO_ROW0_ALL_NY   // diagnostic: also with a second y tile (what tools/isa_lint.py flags there is the reason it is off)
-  static constexpr bool ROW0_VGPR = NT == 8 && ROW0;
-#elif !defined(MO_NO_ROW0_VGPR)
   static constexpr bool ROW0_VGPR = NT == 8 && NY == 1 && ROW0;
-#else
-  static constexpr bool ROW0_VGPR = false;
-#endif
-#ifndef MO_ROW0_ASM_QUAL
-#define MO_ROW0_ASM_QUAL
-#endif
-#ifndef MO_ROW0_PREFIX
-#define MO_ROW0_PREFIX "s_nop 3\n\t"
-#endif
   __device__ static inline void jtj_mfma(d4& acc, double a, double b, int ta) {
-    if (ROW0_VGPR && ta == 0) asm MO_ROW0_ASM_QUAL (MO_ROW0_PREFIX "v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+    if (ROW0_VGPR && ta == 0) asm("s_nop 3\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
     else acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
   }
   __device__ static inline void finish() {
@@ -706,9 +608,7 @@ __device__ inline bool block_eliminate(d4 (&U)[(NT + NY) * (NT + NY)], int k, in
   return ok;
 }
 
-#ifndef MO_LA_MIN_NT
-#define MO_LA_MIN_NT 6   // smallest tile grid (NT = n / 16) whose step kernel eliminates with look-ahead (A/B knob)
-#endif
+constexpr int kLookAheadMinNT = 6;   // smallest tile grid (NT = n / 16) whose step kernel eliminates with look-ahead
 // ---- look-ahead elimination ---------------------------------------------------------------------------------------------------
 // The diagonal sweeps are dependent VALU chains, the trailing updates independent MFMA chains; in program order "sweep, then all updates"
 // a wave alternates between a phase that can only wait on itself and a phase that only feeds the matrix pipe.  Here the update of block
@@ -1005,56 +905,28 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
   const unsigned long long stamp_t0 = stamp_prev, stamp_rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-  // Problems are handed out from a device-wide ticket counter (zeroed on the stream before the launch): the SIMD
-  // arbitrates oldest-wave-first and CUs do not run at identical speed, so a static split leaves 12-30 % of the waves
-  // idle at the end (measured with tools/phase_timer).  Tickets are taken in guided chunks (up to 8 problems while the
-  // queue is long, single problems at the end) because one counter word sustains only ~88 M atomics/s, and the next
-  // chunk is requested at the START of the current chunk's last problem, so the atomic's latency hides under the J stream.
-  const int chunk_shift = 63 - __builtin_clzll((unsigned long long)gridDim.x * WAVES * 4);  // ~ remaining / (4 waves' worth)
-  // Small launches -- at most a.static_rounds problems per wave -- are split STATICALLY, round by round, in slot-major wave order (first one wave on
-  // every SIMD of every CU, then the second wave of every SIMD, ...): no ticket at all.  A wave must otherwise wait for a ticket just to
-  // learn that nothing is left, and 3 072 waves asking one counter word at ~88 M atomics/s is 35 us -- as long as the whole first round of
-  // BASELINE configs[1] (4 096 problems).  A partial round then also lands one wave per SIMD instead of three per SIMD on a third of the CUs.
+  // which problem this wave works on next: the hand-out policy of mo_fused_device.h
+  const int chunk_shift = queue_chunk_shift<WAVES>();
   const long long waves_all = (long long)gridDim.x * WAVES;
   const bool st_rounds = a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * waves_all;   // wave-uniform
-  auto chunk_for = [&](long long observed) -> int {
+  queue_stagger(a, st_rounds, wave);
+  auto chunk_for = [&](long long observed) -> int {   // chunk size when `observed` problems are known to be handed out (mo_fused_device.h)
     if (st_rounds) return 1;
     const long long c = (a.batch - observed) >> chunk_shift;
     return c < 1 ? 1 : (c > 8 ? 8 : (int)c);
   };
-  auto take_ticket = [&](int chunk, long long p_now) -> unsigned long long {
-    if (st_rounds) return (unsigned long long)p_now;   // static rounds: the next problem of this wave is p_now + waves_all (= "ticket" p_now + ticket_base)
-    unsigned long long t = 0;
-    if (lane_id() == 0) t = atomicAdd(a.ticket, (unsigned long long)chunk);
-    return t;
-  };
-  auto uniform64 = [](unsigned long long v) -> long long {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-  };
-  // Start stagger.  Every problem costs the same, so the waves that share a SIMD (waves w, w + 4, w + 8 of the workgroup) would march
-  // through the phases in lockstep for the whole launch -- three J streams together, then three dependent pivot chains together.  Delaying
-  // the second and third wave of each SIMD once, by about a third of a problem each (a.stagger units of 127 x 64 cycles), keeps one wave
-  // in the matrix-bound phase while another is in the sweeps: +1.4 % at cfg 3 (A/B on one box), nothing at cfg 2.
-  if (a.stagger > 0 && !st_rounds) {
-    const int slot = wave >> 2;
-    for (int i = 0; i < slot * a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
-  // The FIRST chunk of every wave is static (wave w of the persistent grid takes problems [w c0, (w + 1) c0)); tickets from the counter start
-  // behind that part.  All waves asking one counter word for their first ticket at kernel start costs 3 072 / 88 M atomics/s = 35 us: most
-  // of a small launch (BASELINE configs[1]: 4 096 problems) and 2 % of the headline one.
   int chunk = chunk_for(0);
   const long long ticket_base = (long long)gridDim.x * WAVES * chunk;
   long long p = st_rounds ? (long long)(wave >> 2) * ((long long)gridDim.x * 4) + (long long)blockIdx.x * 4 + (wave & 3) : ((long long)blockIdx.x * WAVES + wave) * chunk;
   long long chunk_end = p + chunk;
 
   while (p < a.batch) {
-    const bool last_of_chunk = p + 1 >= chunk_end;  // wave-uniform
+    const bool last_of_chunk = p + 1 >= chunk_end;
     int next_chunk = 0;
     unsigned long long next_ticket = 0;
     if (last_of_chunk) {
       next_chunk = chunk_for(p);
-      next_ticket = take_ticket(next_chunk, p);
+      next_ticket = queue_take_ticket(a, st_rounds, next_chunk, p);
     }
     // Lane coordinates are made opaque once per problem so that nothing derived from them (gather addresses, masks,
     // bpermute addresses) is hoisted out of the problem loop and kept live for the whole kernel: the tile registers
@@ -1226,7 +1098,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
     // whatever is left): +0.4 % on two boxes; priority on the J stream instead: -0.8 %.
     if (a.chain_prio) __builtin_amdgcn_s_setprio(1);
     bool ok = true;
-    constexpr bool kLookAhead = NT >= MO_LA_MIN_NT && NY == 1;   // the large grids run one or two waves per SIMD: little else hides the sweeps there
+    constexpr bool kLookAhead = NT >= kLookAheadMinNT && NY == 1;   // the large grids run one or two waves per SIMD: little else hides the sweeps there
     if constexpr (kLookAhead) {
       ok = block_eliminate_lookahead<NT>(U, k, g, j);
     } else {
@@ -1339,12 +1211,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
     lds_fence();  // LDS vectors are re-initialised by the next problem
     if (a.chain_prio) __builtin_amdgcn_s_setprio(0);
     MO_STAMP(6);
-    if (last_of_chunk) {
-      p = uniform64(next_ticket) + ticket_base;
-      chunk_end = p + next_chunk;
-    } else {
-      ++p;
-    }
+    if (last_of_chunk) { p = queue_ticket_problem(next_ticket, ticket_base); chunk_end = p + next_chunk; } else { ++p; }
   }
 #ifdef MO_FUSED_STAMPS
   if ((threadIdx.x & 63) == 0 && a.debug) {
@@ -1376,31 +1243,15 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_linearize_kernel(con
   const int nn = a.n, m_r = a.m_r;
   for (int i = (int)(threadIdx.x & 63); i < D * SLOT / 8; i += 64) reinterpret_cast<double*>(smem)[i] = 0.0;
   lds_fence();
-  const int chunk_shift = 63 - __builtin_clzll((unsigned long long)gridDim.x * WAVES * 4);
-  // Small launches -- at most a.static_rounds problems per wave -- are split STATICALLY, round by round, in slot-major wave order (first one wave on
-  // every SIMD of every CU, then the second wave of every SIMD, ...): no ticket at all.  A wave must otherwise wait for a ticket just to
-  // learn that nothing is left, and 3 072 waves asking one counter word at ~88 M atomics/s is 35 us -- as long as the whole first round of
-  // BASELINE configs[1] (4 096 problems).  A partial round then also lands one wave per SIMD instead of three per SIMD on a third of the CUs.
+  // which problem this wave works on next: the hand-out policy of mo_fused_device.h
+  const int chunk_shift = queue_chunk_shift<WAVES>();
   const long long waves_all = (long long)gridDim.x * WAVES;
   const bool st_rounds = a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * waves_all;   // wave-uniform
-  auto chunk_for = [&](long long observed) -> int {
+  auto chunk_for = [&](long long observed) -> int {   // chunk size when `observed` problems are known to be handed out (mo_fused_device.h)
     if (st_rounds) return 1;
     const long long c = (a.batch - observed) >> chunk_shift;
     return c < 1 ? 1 : (c > 8 ? 8 : (int)c);
   };
-  auto take_ticket = [&](int chunk, long long p_now) -> unsigned long long {
-    if (st_rounds) return (unsigned long long)p_now;   // static rounds: the next problem of this wave is p_now + waves_all (= "ticket" p_now + ticket_base)
-    unsigned long long t = 0;
-    if (lane_id() == 0) t = atomicAdd(a.ticket, (unsigned long long)chunk);
-    return t;
-  };
-  auto uniform64 = [](unsigned long long v) -> long long {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-  };
-  // The FIRST chunk of every wave is static (wave w of the persistent grid takes problems [w c0, (w + 1) c0)); tickets from the counter start
-  // behind that part.  All waves asking one counter word for their first ticket at kernel start costs 3 072 / 88 M atomics/s = 35 us: most
-  // of a small launch (BASELINE configs[1]: 4 096 problems) and 2 % of the headline one.
   int chunk = chunk_for(0);
   const long long ticket_base = (long long)gridDim.x * WAVES * chunk;
   long long p = st_rounds ? (long long)(wave >> 2) * ((long long)gridDim.x * 4) + (long long)blockIdx.x * 4 + (wave & 3) : ((long long)blockIdx.x * WAVES + wave) * chunk;
@@ -1409,7 +1260,10 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_linearize_kernel(con
     const bool last_of_chunk = p + 1 >= chunk_end;
     int next_chunk = 0;
     unsigned long long next_ticket = 0;
-    if (last_of_chunk) { next_chunk = chunk_for(p); next_ticket = take_ticket(next_chunk, p); }
+    if (last_of_chunk) {
+      next_chunk = chunk_for(p);
+      next_ticket = queue_take_ticket(a, st_rounds, next_chunk, p);
+    }
     const int lane = lane_id();
     const int g = lane >> 4, j = lane & 15;
     JStream<NT, D, JMODE> stream;
@@ -1503,7 +1357,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_linearize_kernel(con
     }
     if (g == 0) stv_n<NT, false>((double*)a.c_out + p * a.c_out_stride, j, nn, cvec);
     if (lane == 0 && a.half_sq_out) ((double*)a.half_sq_out)[p * (a.half_sq_stride ? a.half_sq_stride : 1)] = half_sq;
-    if (last_of_chunk) { p = uniform64(next_ticket) + ticket_base; chunk_end = p + next_chunk; } else { ++p; }
+    if (last_of_chunk) { p = queue_ticket_problem(next_ticket, ticket_base); chunk_end = p + next_chunk; } else { ++p; }
   }
 }
 
@@ -1580,31 +1434,15 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_solve_kernel(const K
   for (int i = (int)(threadIdx.x & 63); i < D * SLOT / 8; i += 64) reinterpret_cast<double*>(smem)[i] = 0.0;
   lds_fence();
 
-  const int chunk_shift = 63 - __builtin_clzll((unsigned long long)gridDim.x * WAVES * 4);  // ~ remaining / (4 waves' worth)
-  // Small launches -- at most a.static_rounds problems per wave -- are split STATICALLY, round by round, in slot-major wave order (first one wave on
-  // every SIMD of every CU, then the second wave of every SIMD, ...): no ticket at all.  A wave must otherwise wait for a ticket just to
-  // learn that nothing is left, and 3 072 waves asking one counter word at ~88 M atomics/s is 35 us -- as long as the whole first round of
-  // BASELINE configs[1] (4 096 problems).  A partial round then also lands one wave per SIMD instead of three per SIMD on a third of the CUs.
+  // which problem this wave works on next: the hand-out policy of mo_fused_device.h
+  const int chunk_shift = queue_chunk_shift<WAVES>();
   const long long waves_all = (long long)gridDim.x * WAVES;
   const bool st_rounds = a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * waves_all;   // wave-uniform
-  auto chunk_for = [&](long long observed) -> int {
+  auto chunk_for = [&](long long observed) -> int {   // chunk size when `observed` problems are known to be handed out (mo_fused_device.h)
     if (st_rounds) return 1;
     const long long c = (a.batch - observed) >> chunk_shift;
     return c < 1 ? 1 : (c > 8 ? 8 : (int)c);
   };
-  auto take_ticket = [&](int chunk, long long p_now) -> unsigned long long {
-    if (st_rounds) return (unsigned long long)p_now;   // static rounds: the next problem of this wave is p_now + waves_all (= "ticket" p_now + ticket_base)
-    unsigned long long t = 0;
-    if (lane_id() == 0) t = atomicAdd(a.ticket, (unsigned long long)chunk);
-    return t;
-  };
-  auto uniform64 = [](unsigned long long v) -> long long {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-  };
-  // The FIRST chunk of every wave is static (wave w of the persistent grid takes problems [w c0, (w + 1) c0)); tickets from the counter start
-  // behind that part.  All waves asking one counter word for their first ticket at kernel start costs 3 072 / 88 M atomics/s = 35 us: most
-  // of a small launch (BASELINE configs[1]: 4 096 problems) and 2 % of the headline one.
   int chunk = chunk_for(0);
   const long long ticket_base = (long long)gridDim.x * WAVES * chunk;
   long long p = st_rounds ? (long long)(wave >> 2) * ((long long)gridDim.x * 4) + (long long)blockIdx.x * 4 + (wave & 3) : ((long long)blockIdx.x * WAVES + wave) * chunk;
@@ -1622,10 +1460,10 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_solve_kernel(const K
     unsigned long long next_ticket = 0;
     if (last_of_chunk) {
       next_chunk = chunk_for(p);
-      next_ticket = take_ticket(next_chunk, p);
+      next_ticket = queue_take_ticket(a, st_rounds, next_chunk, p);
     }
     if (ka->skip && ka->skip[p * ka->skip_stride] >= 0) {  // wave-uniform: a problem the caller's outer loop has finished with
-      if (last_of_chunk) { p = uniform64(next_ticket) + ticket_base; chunk_end = p + next_chunk; } else { ++p; }
+      if (last_of_chunk) { p = queue_ticket_problem(next_ticket, ticket_base); chunk_end = p + next_chunk; } else { ++p; }
       continue;
     }
     const int lane = lane_id();
@@ -2130,16 +1968,12 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_solve_kernel(const K
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-#ifndef MO_SOLVE_NO_LOOKAHEAD
       // the look-ahead elimination (bit-identical results) on the 64 grid: no gain in the step kernel at three waves per SIMD (DESIGN.md
       // section 8), but the Solve kernel runs two and its cached passes are chains: 9.38 -> 9.55 M solves/s, 11.86 -> 12.03 M predictor-corrector
       bool elim_ok;
-      if constexpr (NY == 1 && (NT == 4 || NT >= MO_LA_MIN_NT)) elim_ok = block_eliminate_lookahead<NT>(U, k, g, j);
+      if constexpr (NY == 1 && (NT == 4 || NT >= kLookAheadMinNT)) elim_ok = block_eliminate_lookahead<NT>(U, k, g, j);
       else elim_ok = block_eliminate<NT, NY>(U, k, g, j);
       if (!__all(elim_ok)) { st = MO_STATUS_FACTORIZATION_FAILED; break; }   // (__all: a scalar branch, see the decision point)
-#else
-      if (!__all(block_eliminate<NT, NY>(U, k, g, j))) { st = MO_STATUS_FACTORIZATION_FAILED; break; }
-#endif
       double xb[NB];
       back_substitute<NT, NY>(U, k, j, xb);  // xb[c] = dx (permuted), xb[NT + q] = -dy
       double dyv[NY], dsv[MC], dzv[MC], ap = 1.0, ad = 1.0;
@@ -2350,12 +2184,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_solve_kernel(const K
     }
     }
     lds_fence();
-    if (last_of_chunk) {
-      p = uniform64(next_ticket) + ticket_base;
-      chunk_end = p + next_chunk;
-    } else {
-      ++p;
-    }
+    if (last_of_chunk) { p = queue_ticket_problem(next_ticket, ticket_base); chunk_end = p + next_chunk; } else { ++p; }
   }
 }
 

@@ -5,11 +5,13 @@
 // What differs from fp64:
 //   * C/D fragment layout: lane (g = l >> 4, j = l & 15), register t <-> element (row 4g + t, col j)   (fp64: row g + 4t);
 //   * a 16-byte J piece carries FOUR columns, so the variable permutation is position 16c + i <-> column 64(c>>2) + 4i + (c&3);
-//   * k may be 16 (all of the y tile), so the right-hand side rides in a tile column of its own (index NT + 1, column 0)
-//     instead of column 15 of the [A_eq^T | rhs] tiles: (NT+1)(NT+2)/2 + NT + 1 tiles of 4 VGPRs (216 VGPRs at n = 128).
+//   * k may be 16 (all of the y tile), so the right-hand side cannot ride in column 15 of the [A_eq^T | rhs] tiles.  The Solve / Iterate
+//     kernel gives it a tile column of its own (index NT + 1, column 0): (NT+1)(NT+2)/2 + NT + 1 tiles of 4 VGPRs (216 VGPRs at n = 128).
+//     The step kernel carries it as a vector instead (NT + 1 registers and two LDS hops per block step).
 // Reference lines: residual.hpp:206-224 + nonlinear.cc:187-189 (J^T J, J^T r, lambda), qp.cc:281-298 (assembly),
 // qp.cc:302-311 + 318-364 (factorisation and solve; no explicit inverse of H here), qp.cc:485-507 (alpha).
 // Which instantiation serves a launch: fused_f32_supported / fused_f32_select (mo_fused_select.h) and the table at the end of this file.
+#include "mo_fused_device.h"
 #include "mo_fused_select.h"
 
 namespace mo {
@@ -17,33 +19,8 @@ namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-// Phase stamps exist only in the diagnostic build of tools/phase_timer_f32.hip; the product kernel executes none.
-#ifdef MO_F32_STAMPS
-#define MO_STAMP32(i)                                                                                 \
-  do {                                                                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-    unsigned long long t__;                                                                           \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");                       \
-    stamp_acc[i] += t__ - stamp_prev;                                                                 \
-    stamp_prev = t__;                                                                                 \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-  } while (0)
-#else
-#define MO_STAMP32(i) do { } while (0)
-#endif
 typedef unsigned u2v __attribute__((ext_vector_type(2)));
 
-__device__ inline int lane_id32() {  // volatile on purpose: nothing derived from it is hoisted out of the problem loop
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-typedef const KernelArgs __attribute__((address_space(4)))* KArgs32;
-__device__ inline KArgs32 fresh_args32() {
-  KArgs32 p = (KArgs32)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return p;
-}
 __device__ inline float readlane_f32(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 __device__ inline float bpermute_f32(int byte_addr, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v))); }
 template <int CTRL> __device__ inline float dpp_f32(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false)); }
@@ -82,48 +59,26 @@ __device__ inline f4 mfma4_f32(const f4& a, const f4& b, f4 c) {  // c += A^T-fr
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
   return c;
 }
-// LDS-DMA (no VGPR destination; completion is waited for by hand, loads retire in order)
-__device__ inline void dma16_f32(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void dma4_f32(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 // `count` consecutive 4-byte words (count <= 128, wave-uniform) global -> LDS
 __device__ inline void dma_words(const void* src, unsigned lds_dst, int count, int lane) {
   const char* s4 = reinterpret_cast<const char*>(src) + 4 * lane;
-  if (lane < count) dma4_f32(s4, lds_dst);
-  if (lane + 64 < count) dma4_f32(s4 + 256, lds_dst + 256);
+  if (lane < count) dma4(s4, lds_dst);
+  if (lane + 64 < count) dma4(s4 + 256, lds_dst + 256);
 }
-template <int N> __device__ inline void wait_vmcnt32() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-__device__ inline void lds_fence32() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // EXEC-masked moves with immediate lane masks (see kkt_fused.hip for why the masks are immediates, and for the pad: a DPP read of the VGPR
-// just written needs 2 wait states -- the s_mov_b64 that restores EXEC and `s_nop 0`; rounds 1-2 padded with `s_nop 4`, -DMO_F32_MASKED_PAD_4
-// restores that for A/B builds)
-#ifdef MO_F32_MASKED_PAD_4
-#define MO_F32_PAD "4"
-#else
-#define MO_F32_PAD "0"
-#endif
-#ifndef MO_F32_RHS_VECTOR   // A/B knob (step kernel): 0 = the right-hand side in tile column NT + 1, as in rounds 1 - 3
-#define MO_F32_RHS_VECTOR 1   // round 4: a vector (registers + two LDS hops per block step): -180 MFMAs at NT = 8, +1.0 %
-#endif
+// just written needs 2 wait states -- the s_mov_b64 that restores EXEC and `s_nop 0`; rounds 1-2 padded with `s_nop 4`)
 template <unsigned long long MASK> __device__ inline void masked_set_f32(float& dst, float src) {
   unsigned long long save;
   asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\tv_mov_b32 %[d], %[s]\n\t"
-               "s_mov_b64 exec, %[sv]\n\ts_nop " MO_F32_PAD
+               "s_mov_b64 exec, %[sv]\n\ts_nop 0"
                : [d] "+v"(dst), [sv] "=&s"(save)
                : [s] "v"(src), [lo] "i"((unsigned)(MASK & 0xffffffffull)), [hi] "i"((unsigned)(MASK >> 32)));
 }
 template <unsigned long long MASK> __device__ inline void masked_set_neg_f32(float& dst, float src) {
   unsigned long long save;
   asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\tv_max_f32 %[d], -%[s], -%[s]\n\t"
-               "s_mov_b64 exec, %[sv]\n\ts_nop " MO_F32_PAD
+               "s_mov_b64 exec, %[sv]\n\ts_nop 0"
                : [d] "+v"(dst), [sv] "=&s"(save)
                : [s] "v"(src), [lo] "i"((unsigned)(MASK & 0xffffffffull)), [hi] "i"((unsigned)(MASK >> 32)));
 }
@@ -131,7 +86,7 @@ template <unsigned long long MASK> __device__ inline void masked_zero4_f32(f4& T
   unsigned long long save;
   float t0 = T[0], t1 = T[1], t2 = T[2], t3 = T[3];
   asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\tv_mov_b32 %[a], 0\n\tv_mov_b32 %[b], 0\n\t"
-               "v_mov_b32 %[c], 0\n\tv_mov_b32 %[d], 0\n\ts_mov_b64 exec, %[sv]\n\ts_nop " MO_F32_PAD
+               "v_mov_b32 %[c], 0\n\tv_mov_b32 %[d], 0\n\ts_mov_b64 exec, %[sv]\n\ts_nop 0"
                : [a] "+v"(t0), [b] "+v"(t1), [c] "+v"(t2), [d] "+v"(t3), [sv] "=&s"(save)
                : [lo] "i"((unsigned)(MASK & 0xffffffffull)), [hi] "i"((unsigned)(MASK >> 32)));
   T[0] = t0; T[1] = t1; T[2] = t2; T[3] = t3;
@@ -225,7 +180,7 @@ template <int NT, int WPS, bool PAD>
 __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const KernelArgs a) {
   using C = Cfg32<NT, WPS>;
   constexpr int N = C::N, NH = C::NH, DPS = C::DPS, SLOT = C::SLOT, D = C::D;
-  constexpr int NB = NT + 2, NR = NT + 1;          // tile columns: x blocks 0..NT-1, y block NT, right-hand side NR
+  constexpr int NB = NT + 2;                       // tile columns: x blocks 0..NT-1, y block NT (column NT + 1 is unused: the right-hand side is a vector)
   constexpr int WAVES = 4 * WPS;
 
   __shared__ __attribute__((aligned(16))) char smem_all[WAVES * C::LDS];
@@ -254,39 +209,20 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
   const int nn = PAD ? a.n : N;   // variables (PAD: a multiple of 4, N - 63 .. N)
   const int nsteps = m_r >> 2;
 
-  const int chunk_shift = 63 - __builtin_clzll((unsigned long long)gridDim.x * WAVES * 4);
-  // Small launches -- at most a.static_rounds problems per wave -- are split STATICALLY, round by round, in slot-major wave order (first one wave on
-  // every SIMD of every CU, then the second wave of every SIMD, ...): no ticket at all.  A wave must otherwise wait for a ticket just to
-  // learn that nothing is left, and 3 072 waves asking one counter word at ~88 M atomics/s is 35 us -- as long as the whole first round of
-  // BASELINE configs[1] (4 096 problems).  A partial round then also lands one wave per SIMD instead of three per SIMD on a third of the CUs.
+  // which problem this wave works on next: the hand-out policy of mo_fused_device.h
+  const int chunk_shift = queue_chunk_shift<WAVES>();
   const long long waves_all = (long long)gridDim.x * WAVES;
   const bool st_rounds = a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * waves_all;   // wave-uniform
-  auto chunk_for = [&](long long observed) -> int {
+  if (PAD && nn < N) {  // the lanes beyond a row of J never write their ring bytes: zeros there, once
+    for (int i = lane_id() * 16; i < D * SLOT; i += 64 * 16) *(f4*)(smem + i) = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    lds_fence();
+  }
+  queue_stagger(a, st_rounds, wave);
+  auto chunk_for = [&](long long observed) -> int {   // chunk size when `observed` problems are known to be handed out (mo_fused_device.h)
     if (st_rounds) return 1;
     const long long c = (a.batch - observed) >> chunk_shift;
     return c < 1 ? 1 : (c > 8 ? 8 : (int)c);
   };
-  auto take_ticket = [&](int chunk, long long p_now) -> unsigned long long {
-    if (st_rounds) return (unsigned long long)p_now;   // static rounds: the next problem of this wave is p_now + waves_all (= "ticket" p_now + ticket_base)
-    unsigned long long t = 0;
-    if (lane_id32() == 0) t = atomicAdd(a.ticket, (unsigned long long)chunk);
-    return t;
-  };
-  auto uniform64 = [](unsigned long long v) -> long long {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-  };
-  if (PAD && nn < N) {  // the lanes beyond a row of J never write their ring bytes: zeros there, once
-    for (int i = lane_id32() * 16; i < D * SLOT; i += 64 * 16) *(f4*)(smem + i) = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    lds_fence32();
-  }
-  if (a.stagger > 0 && !st_rounds) {  // start stagger between the waves that share a SIMD (see kkt_fused.hip): equal-cost problems keep waves in lockstep
-    const int slot = wave >> 2;
-    for (int i = 0; i < slot * a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
-  // The FIRST chunk of every wave is static (wave w of the persistent grid takes problems [w c0, (w + 1) c0)); tickets from the counter start
-  // behind that part.  All waves asking one counter word for their first ticket at kernel start costs 3 072 / 88 M atomics/s = 35 us: most
-  // of a small launch (BASELINE configs[1]: 4 096 problems) and 2 % of the headline one.
   int chunk = chunk_for(0);
   const long long ticket_base = (long long)gridDim.x * WAVES * chunk;
   long long p = st_rounds ? (long long)(wave >> 2) * ((long long)gridDim.x * 4) + (long long)blockIdx.x * 4 + (wave & 3) : ((long long)blockIdx.x * WAVES + wave) * chunk;
@@ -302,9 +238,9 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
     unsigned long long next_ticket = 0;
     if (last_of_chunk) {
       next_chunk = chunk_for(p);
-      next_ticket = take_ticket(next_chunk, p);
+      next_ticket = queue_take_ticket(a, st_rounds, next_chunk, p);
     }
-    const int lane = lane_id32();
+    const int lane = lane_id();
     const int g = lane >> 4, j = lane & 15;
 
     // ---- J stream set-up: lane (g, j) of 4-row group s fetches J(4s + g, 64h + 4j .. +3), h < NH; lane 0 fetches r[4s .. 4s+3]
@@ -316,8 +252,8 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
       const unsigned dst = ring_base + slot * SLOT;
 #pragma unroll
       for (int h = 0; h < NH; ++h)
-        if (!PAD || 64 * h + 4 * j < nn) dma16_f32(jsrc + 256 * h, dst + h * 1024);   // (lane 0 of every piece is inside the row: the grid is the smallest that holds nn)
-      if (lane < 4) dma4_f32(rsrc + 4 * lane, dst + NH * 1024);   // r[4s .. 4s+3] as four dwords: no alignment asked of r
+        if (!PAD || 64 * h + 4 * j < nn) dma16(jsrc + 256 * h, dst + h * 1024);   // (lane 0 of every piece is inside the row: the grid is the smallest that holds nn)
+      if (lane < 4) dma4(rsrc + 4 * lane, dst + NH * 1024);   // r[4s .. 4s+3] as four dwords: no alignment asked of r
       jsrc += 4 * nn * 4;
       rsrc += 16;
     };
@@ -326,7 +262,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
       if (u < nsteps) issue(u);
 
     // ---- P0: small vectors global -> LDS by DMA (no VGPRs held while J streams)
-    KArgs32 ka = fresh_args32();
+    KArgs ka = fresh_args();
     const float* vp = (const float*)ka->vars + p * ka->vars_stride;
     f4 U[NB * NB];
 #pragma unroll
@@ -346,7 +282,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
       dma_words((const float*)ka->b + p * ka->b_stride, vec_base + (3 * N + 336) * 4, k, lane);
     }
 
-    MO_STAMP32(0);
+    MO_STAMP(0);
     // ---- P1: G = J^T J on the matrix cores (upper block triangle), c = J^T r on the VALU
     float cpart[NT];
 #pragma unroll
@@ -357,10 +293,10 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
         const int q = q0 + u;
         if (q < nsteps) {
           const int younger = nsteps - 1 - q;  // groups that may stay in flight (DPS DMAs each)
-          if (younger >= D - 1) wait_vmcnt32<(D - 1) * DPS>();
-          else if (younger == 2) wait_vmcnt32<2 * DPS>();
-          else if (younger == 1) wait_vmcnt32<1 * DPS>();
-          else wait_vmcnt32<0>();
+          if (younger >= D - 1) wait_vmcnt<(D - 1) * DPS>();
+          else if (younger == 2) wait_vmcnt<2 * DPS>();
+          else if (younger == 1) wait_vmcnt<1 * DPS>();
+          else wait_vmcnt<0>();
           float ops[NT];
 #pragma unroll
           for (int h = 0; h < NH; ++h) {
@@ -368,7 +304,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
             ops[4 * h] = v[0]; ops[4 * h + 1] = v[1]; ops[4 * h + 2] = v[2]; ops[4 * h + 3] = v[3];
           }
           const float rq = *(const float*)(r_elem + u * SLOT);
-          lds_fence32();  // the slot's bytes are in registers before the slot is handed back to the DMA engine
+          lds_fence();  // the slot's bytes are in registers before the slot is handed back to the DMA engine
           if (q + D < nsteps) issue(u);
 #pragma unroll
           for (int ta = 0; ta < NT; ++ta) {
@@ -408,15 +344,15 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
 #pragma unroll
     for (int c = 0; c < NT; ++c) cvec[c] = cross_row_sum_f32(cpart[c]);
 
-    MO_STAMP32(1);
+    MO_STAMP(1);
     // ---- P3: barrier terms scattered per variable through LDS (duplicates on one variable accumulate)
-    wait_vmcnt32<0>();
-    ka = fresh_args32();
+    wait_vmcnt<0>();
+    ka = fresh_args();
     const float mu = ka->mu ? ((const float*)ka->mu)[p * ka->mu_stride] : 0.0f;
     for (int i = lane; i < N; i += 64) { diagS[i] = 0.0f; rhsS[i] = 0.0f; }
     int cvar = 0; float ca = 1.0f, cb = 0.0f, cs = 1.0f, cz = 0.0f;
     if (lane < m) { cvar = cV[lane]; ca = cA[lane]; cb = cB[lane]; cs = cS[lane]; cz = cZ[lane]; }
-    lds_fence32();
+    lds_fence();
     bool bad_index = (lane < m) && ((cvar < 0) || (cvar >= nn));
     if (bad_index) cvar = 0;
     const bool slack_bad = __any((lane < m) && !(cs > 0.0f));
@@ -433,7 +369,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
       atomicAdd(&diagS[cvar], ca * zs * ca);                         // qp.cc:296
       atomicAdd(&rhsS[cvar], ca * (cz * (cs - cb) + mu) * cs_inv);    // x+ form of qp.cc:340-341
     }
-    lds_fence32();
+    lds_fence();
     float dS[NT], rS[NT];
     ldv32<NT>(diagS, j, dS);
     ldv32<NT>(rhsS, j, rS);
@@ -441,7 +377,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
 #pragma unroll
       for (int c = 0; c < NT; ++c) rp[16 * c + j] = rS[c] - cvec[c];
     }
-    lds_fence32();
+    lds_fence();
 
     // ---- P2/P4: lambda + Sigma on the diagonal tiles, [A_eq^T] tile column, right-hand side tile column
     const float lam_in = ka->lambda_vec ? ((const float*)ka->lambda_vec)[p * ka->lambda_vec_stride] : (float)ka->lambda;
@@ -456,18 +392,9 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
           const int natcol = 64 * (c >> 2) + 16 * g + 4 * t + (c & 3);  // variable at position 16c + 4g + t
           U[c * NB + c][t] += (j == 4 * g + t) ? ((!PAD || natcol < nn) ? lam + dS[c] : 1.0f) : 0.0f;   // padding: identity rows, zero right-hand side
           U[c * NB + NT][t] = (j < k && (!PAD || natcol < nn)) ? Ap[j + (size_t)natcol * A_ld] : 0.0f;
-#if !MO_F32_RHS_VECTOR
-          const float rv = rp[16 * c + 4 * g + t];
-          U[c * NB + NR][t] = (j == 0) ? rv : 0.0f;
-#endif
         }
       }
-#if !MO_F32_RHS_VECTOR
-#pragma unroll
-      for (int t = 0; t < 4; ++t) U[NT * NB + NR][t] = (j == 0 && 4 * g + t < k) ? -bb[4 * g + t] : 0.0f;  // -b_eq
-#endif
     }
-#if MO_F32_RHS_VECTOR
     // The right-hand side as a VECTOR: rj[c] = its entry at position 16 c + j (every lane group holds a copy).  Tile column NT + 1 costs
     // 4 MFMAs per tile product for one useful column in sixteen (180 MFMAs at NT = 8); the vector pays 4 FMAs + a cross-row sum per product
     // and two LDS hops per block step (lane j <-> rows 4 g .. 4 g + 3, the layout a tile product wants its operand in).  rp (= diagS) holds
@@ -477,23 +404,19 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
     for (int c = 0; c < NT; ++c) rj[c] = rS[c] - cvec[c];
     rj[NT] = (j < k) ? -bb[j] : 0.0f;                                 // -b_eq
     float* const zS = rhsS + 16;
-#endif
 
-    // ---- P5: block elimination with 16x16 pivot blocks (pivot blocks 0..NT; column NR only rides along)
+    // ---- P5: block elimination with 16x16 pivot blocks (pivot blocks 0..NT; the right-hand side vector rides along)
     __builtin_amdgcn_sched_barrier(0);
-    MO_STAMP32(2);
+    MO_STAMP(2);
     bool ok = true;
 #pragma unroll
     for (int pa = 0; pa <= NT; ++pa) {
-#if MO_F32_RHS_VECTOR
       if (g == 0) rp[16 * pa + j] = rj[pa];                           // block pa of the right-hand side is final: to LDS (the sweep covers the hop)
-#endif
       ok = sweep_tile_f32(U[pa * NB + pa], pa < NT ? 16 : k, j) && ok;
       __builtin_amdgcn_sched_barrier(0);
-      MO_STAMP32(3);
-#if MO_F32_RHS_VECTOR
+      MO_STAMP(3);
       {
-        lds_fence32();
+        lds_fence();
         const f4 ra4 = *(const f4*)(rp + 16 * pa + 4 * g);            // rows 4 g .. 4 g + 3 of block pa
         float zs = 0.0f;
 #pragma unroll
@@ -502,17 +425,15 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
         if (g == 0) zS[j] = zs;
       }
       __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
-      for (int pc = pa + 1; pc < (MO_F32_RHS_VECTOR ? NB - 1 : NB); ++pc) {
+      for (int pc = pa + 1; pc < NB - 1; ++pc) {
         const f4 negZ = mfma4_f32(U[pa * NB + pa], U[pa * NB + pc], f4{0.0f, 0.0f, 0.0f, 0.0f});  // (-T^-1) U_ac
 #pragma unroll
         for (int pb = pa + 1; pb <= (pc < NT ? pc : NT); ++pb) U[pb * NB + pc] = mfma4_f32(U[pa * NB + pb], negZ, U[pb * NB + pc]);
         __builtin_amdgcn_sched_barrier(0);
       }
-#if MO_F32_RHS_VECTOR
       if (pa < NT) {
-        lds_fence32();
+        lds_fence();
         const f4 z4 = *(const f4*)(zS + 4 * g);
 #pragma unroll
         for (int pb = pa + 1; pb <= NT; ++pb) {
@@ -523,11 +444,10 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-#endif
-      MO_STAMP32(4);
+      MO_STAMP(4);
     }
     __builtin_amdgcn_sched_barrier(0);
-    MO_STAMP32(4);
+    MO_STAMP(4);
 
     // ---- P6: backward substitution; xb[c] = solution at permuted position 16c + j (replicated over g); xb[NT] = -y+
     float xb[NT + 1];
@@ -540,11 +460,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
 #pragma unroll
         for (int pb = pa + 1; pb <= NT; ++pb) pt = fmaf(U[pa * NB + pb][t], xb[pb], pt);
         pt = row_sum_f32(pt);
-#if MO_F32_RHS_VECTOR
         vt[t] = rp[16 * pa + 4 * g + t] - pt;
-#else
-        vt[t] = row_bcast_f32<0>(U[pa * NB + NR][t]) - pt;
-#endif
       }
       float q = 0.0f;
 #pragma unroll
@@ -553,9 +469,9 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
       __builtin_amdgcn_sched_barrier(0);
     }
 
-    MO_STAMP32(5);
+    MO_STAMP(5);
     // ---- P7: direction, step lengths, status
-    ka = fresh_args32();
+    ka = fresh_args();
     float dxv[NT];
     {
       float xn[NT];
@@ -567,7 +483,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
 #pragma unroll
     for (int c = 0; c < NT; ++c) finite = finite && (fabsf(dxv[c]) < INFINITY);
     if (g == 0) stv32<NT>(dxs, j, dxv);
-    lds_fence32();
+    lds_fence();
     float dsv = 0.0f, dzv = 0.0f, ap = 1.0f, ad = 1.0f;
     if (lane < m) {
       const float ca2 = cA[lane], cb2 = cB[lane], cs2 = cS[lane], cz2 = cZ[lane];
@@ -618,14 +534,9 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_kernel(const Ker
       }
       if (ka->status) ka->status[p] = st;
     }
-    lds_fence32();  // the LDS vectors are re-initialised by the next problem
-    MO_STAMP32(6);
-    if (last_of_chunk) {
-      p = uniform64(next_ticket) + ticket_base;
-      chunk_end = p + next_chunk;
-    } else {
-      ++p;
-    }
+    lds_fence();  // the LDS vectors are re-initialised by the next problem
+    MO_STAMP(6);
+    if (last_of_chunk) { p = queue_ticket_problem(next_ticket, ticket_base); chunk_end = p + next_chunk; } else { ++p; }
   }
 #ifdef MO_F32_STAMPS
   if ((threadIdx.x & 63) == 0 && a.debug) {
@@ -670,7 +581,7 @@ __device__ inline void solve_second_rhs_f32(const f4 (&U)[(NT + 2) * (NT + 2)], 
 #pragma unroll
   for (int pa = 0; pa <= NT; ++pa) {  // forward: r_b += U_ab^T (-T_a^-1 r_a), b > a
     if (g == 0) { hop[j] = rb[pa]; (pa < NT ? rbuf_x + 16 * pa : rbuf_y)[j] = rb[pa]; }
-    lds_fence32();
+    lds_fence();
     if (pa < NT) {
       float q = 0.0f;
       {
@@ -679,9 +590,9 @@ __device__ inline void solve_second_rhs_f32(const f4 (&U)[(NT + 2) * (NT + 2)], 
         for (int t = 0; t < 4; ++t) q = fmaf(U[pa * NB + pa][t], h4[t], q);
       }
       const float w = cross_row_sum_f32(q);  // (-T_a^-1 r_a)(j)
-      lds_fence32();                         // hop has been read
+      lds_fence();                         // hop has been read
       if (g == 0) hop[j] = w;
-      lds_fence32();
+      lds_fence();
       const f4 wr = *(const f4*)(hop + 4 * g);
 #pragma unroll
       for (int pb = pa + 1; pb <= NT; ++pb) {
@@ -690,7 +601,7 @@ __device__ inline void solve_second_rhs_f32(const f4 (&U)[(NT + 2) * (NT + 2)], 
         for (int t = 0; t < 4; ++t) q2 = fmaf(U[pa * NB + pb][t], wr[t], q2);
         rb[pb] += cross_row_sum_f32(q2);
       }
-      lds_fence32();                         // hop has been read before the next block overwrites it
+      lds_fence();                         // hop has been read before the next block overwrites it
     }
   }
 #pragma unroll
@@ -739,31 +650,15 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
   const float inv_m = m > 0 ? 1.0f / (float)m : 0.0f;
   const bool qpl = a.J == nullptr;  // wave-uniform: QP-level input (G, c given)
 
-  const int chunk_shift = 63 - __builtin_clzll((unsigned long long)gridDim.x * WAVES * 4);
-  // Small launches -- at most a.static_rounds problems per wave -- are split STATICALLY, round by round, in slot-major wave order (first one wave on
-  // every SIMD of every CU, then the second wave of every SIMD, ...): no ticket at all.  A wave must otherwise wait for a ticket just to
-  // learn that nothing is left, and 3 072 waves asking one counter word at ~88 M atomics/s is 35 us -- as long as the whole first round of
-  // BASELINE configs[1] (4 096 problems).  A partial round then also lands one wave per SIMD instead of three per SIMD on a third of the CUs.
+  // which problem this wave works on next: the hand-out policy of mo_fused_device.h
+  const int chunk_shift = queue_chunk_shift<WAVES>();
   const long long waves_all = (long long)gridDim.x * WAVES;
   const bool st_rounds = a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * waves_all;   // wave-uniform
-  auto chunk_for = [&](long long observed) -> int {
+  auto chunk_for = [&](long long observed) -> int {   // chunk size when `observed` problems are known to be handed out (mo_fused_device.h)
     if (st_rounds) return 1;
     const long long c = (a.batch - observed) >> chunk_shift;
     return c < 1 ? 1 : (c > 8 ? 8 : (int)c);
   };
-  auto take_ticket = [&](int chunk, long long p_now) -> unsigned long long {
-    if (st_rounds) return (unsigned long long)p_now;   // static rounds: the next problem of this wave is p_now + waves_all (= "ticket" p_now + ticket_base)
-    unsigned long long t = 0;
-    if (lane_id32() == 0) t = atomicAdd(a.ticket, (unsigned long long)chunk);
-    return t;
-  };
-  auto uniform64 = [](unsigned long long v) -> long long {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-  };
-  // The FIRST chunk of every wave is static (wave w of the persistent grid takes problems [w c0, (w + 1) c0)); tickets from the counter start
-  // behind that part.  All waves asking one counter word for their first ticket at kernel start costs 3 072 / 88 M atomics/s = 35 us: most
-  // of a small launch (BASELINE configs[1]: 4 096 problems) and 2 % of the headline one.
   int chunk = chunk_for(0);
   const long long ticket_base = (long long)gridDim.x * WAVES * chunk;
   long long p = st_rounds ? (long long)(wave >> 2) * ((long long)gridDim.x * 4) + (long long)blockIdx.x * 4 + (wave & 3) : ((long long)blockIdx.x * WAVES + wave) * chunk;
@@ -772,20 +667,20 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
   while (p < a.batch) {
     // the argument block and the shape are re-read from the kernarg segment where they are used (see kkt_fused_solve_kernel): held in SGPRs
     // for the whole kernel they were spilled into VGPR lanes (226 v_writelane / 534 v_readlane in round 2's build)
-    KArgs32 ka = fresh_args32();
+    KArgs ka = fresh_args();
     const int k = ka->k, m = ka->m, nn = PAD ? ka->n : N;   // nn variables (PAD: a multiple of 4) on the N = 16 NT grid
     const bool last_of_chunk = p + 1 >= chunk_end;
     int next_chunk = 0;
     unsigned long long next_ticket = 0;
     if (last_of_chunk) {
       next_chunk = chunk_for(p);
-      next_ticket = take_ticket(next_chunk, p);
+      next_ticket = queue_take_ticket(a, st_rounds, next_chunk, p);
     }
     if (ka->skip && ka->skip[p * ka->skip_stride] >= 0) {  // wave-uniform: a problem the caller's outer loop has finished with
-      if (last_of_chunk) { p = uniform64(next_ticket) + ticket_base; chunk_end = p + next_chunk; } else { ++p; }
+      if (last_of_chunk) { p = queue_ticket_problem(next_ticket, ticket_base); chunk_end = p + next_chunk; } else { ++p; }
       continue;
     }
-    const int lane = lane_id32();
+    const int lane = lane_id();
     const int g = lane >> 4, j = lane & 15;
 
     float* vp = (float*)ka->vars + p * ka->vars_stride;
@@ -827,7 +722,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
     // s = max(1e-9, a x + b), z = 1/s after clamping x into the feasible region in constraint order (qp.cc:464-481)
     auto clamp_and_init_slacks = [&]() {
       if (g == 0) stv32<NT>(xs, j, xv);
-      lds_fence32();
+      lds_fence();
       for (int c = 0; c < m; ++c) {  // wave-uniform loop; one constraint at a time keeps the reference's order
         if (lane == c) {
           const float x0 = xs[cvar];
@@ -836,7 +731,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
           else { const float lim = -cb / ca; x1 = x0 > lim ? x0 : lim; }
           xs[cvar] = x1;
         }
-        lds_fence32();
+        lds_fence();
       }
       ldv32<NT>(xs, j, xv);
       float sz = 0.0f;
@@ -877,8 +772,8 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
 
     while (st == MO_STATUS_OK) {
       const bool include_ineq = !guess_pass && !(residual_mode && (ka->flags & MO_STEP_NO_INEQUALITIES));
-      const int lane = lane_id32(), g = lane >> 4, j = lane & 15;  // re-made opaque every pass (nothing lane-derived is kept across the factorisation)
-      ka = fresh_args32();
+      const int lane = lane_id(), g = lane >> 4, j = lane & 15;  // re-made opaque every pass (nothing lane-derived is kept across the factorisation)
+      ka = fresh_args();
       const int k = ka->k, m = ka->m, nn = PAD ? ka->n : N;
       // ---------------------------------------------------------------- part A: tiles, residual, norms
       const bool stream_now = !qpl && __builtin_amdgcn_readfirstlane((int)!tiles_cached) != 0;
@@ -888,8 +783,8 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
         const unsigned dst = ring_base + slot * SLOT;
 #pragma unroll
         for (int h = 0; h < NH; ++h)
-          if (!PAD || 64 * h + 4 * j < nn) dma16_f32(jsrc + 256 * h, dst + h * 1024);   // (lane 0 of every piece is inside the row)
-        if (lane < 4) dma4_f32(rsrc + 4 * lane, dst + NH * 1024);   // r[4s .. 4s+3] as four dwords: no alignment asked of r
+          if (!PAD || 64 * h + 4 * j < nn) dma16(jsrc + 256 * h, dst + h * 1024);   // (lane 0 of every piece is inside the row)
+        if (lane < 4) dma4(rsrc + 4 * lane, dst + NH * 1024);   // r[4s .. 4s+3] as four dwords: no alignment asked of r
         jsrc += 4 * nn * 4;
         rsrc += 16;
       };
@@ -900,7 +795,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
 #pragma unroll
             for (int h = 0; h < NH; ++h)
               if (PAD && 64 * h + 4 * j >= nn) *(f4*)(smem + lane * 16 + u * SLOT + h * 1024) = f4{0.0f, 0.0f, 0.0f, 0.0f};
-          lds_fence32();
+          lds_fence();
         }
 #pragma unroll
         for (int u = 0; u < D; ++u)
@@ -946,10 +841,10 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
             const int q = q0 + u;
             if (q < nsteps) {
               const int younger = nsteps - 1 - q;  // groups that may stay in flight (DPS DMAs each)
-              if (younger >= D - 1) wait_vmcnt32<(D - 1) * DPS>();
-              else if (younger == 2) wait_vmcnt32<2 * DPS>();
-              else if (younger == 1) wait_vmcnt32<1 * DPS>();
-              else wait_vmcnt32<0>();
+              if (younger >= D - 1) wait_vmcnt<(D - 1) * DPS>();
+              else if (younger == 2) wait_vmcnt<2 * DPS>();
+              else if (younger == 1) wait_vmcnt<1 * DPS>();
+              else wait_vmcnt<0>();
               float ops[NT];
 #pragma unroll
               for (int h = 0; h < NH; ++h) {
@@ -957,7 +852,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
                 ops[4 * h] = v[0]; ops[4 * h + 1] = v[1]; ops[4 * h + 2] = v[2]; ops[4 * h + 3] = v[3];
               }
               const float rq = *(const float*)(r_elem + u * SLOT);
-              lds_fence32();  // the slot's bytes are in registers before the slot is handed back to the DMA engine
+              lds_fence();  // the slot's bytes are in registers before the slot is handed back to the DMA engine
               if (q + D < nsteps) issue(u);
 #pragma unroll
               for (int ta = 0; ta < NT; ++ta) {
@@ -969,7 +864,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
             }
           }
         }
-        wait_vmcnt32<0>();
+        wait_vmcnt<0>();
         if (m_r & 3) {  // wave-uniform: up to three rows behind the last whole group -- plain loads, the lanes of the missing rows feed zeros
           float ops[NT];
 #pragma unroll
@@ -1028,7 +923,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
 #pragma unroll
         for (int t = 0; t < 4; ++t) U[c * NB + NT][t] = (j < k && (!PAD || natvar32(c, 4 * g + t) < nn)) ? Ap[j + (size_t)natvar32(c, 4 * g + t) * ka->A_ld] : 0.0f;
       }
-      lds_fence32();
+      lds_fence();
       float r_pi = 0.0f, r_comp = 0.0f;
       if (include_ineq && lane < m) {
         atomicAdd(&azS[cvar], ca * cz);               // qp.cc:415
@@ -1060,7 +955,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
           }
           if (j == 0) *(f4*)(tmp + 16 * ra + 4 * g) = pt4;
         }
-        lds_fence32();
+        lds_fence();
         {
           float azv[NT];
           ldv32<NT>(azS, j, azv);
@@ -1134,7 +1029,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
         }
       }
       // ---------------------------------------------------------------- part B: right-hand side, factorisation, direction
-      ka = fresh_args32();
+      ka = fresh_args();
       const bool predictor_pass = use_pc && !guess_pass;
       const float mu_step = m > 0 ? (predictor_pass ? 0.0f : mu) : 0.0f;  // qp.cc:165-187
       float aff = 0.0f, cs_inv = 1.0f;  // aff = ds_aff dz_aff (qp.cc:341), set by the predictor
@@ -1147,7 +1042,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
           atomicAdd(&rhoS[cvar], ca * zs * r_pi + ca * (r_comp + aff - mu_step) * cs_inv);  // qp.cc:340-341
         }
       }
-      lds_fence32();
+      lds_fence();
       {
         float dd[NT], rr[NT];
         ldv32<NT>(diagS, j, dd);
@@ -1160,7 +1055,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
         }
       }
       if (g == 0) ysm[16 + j] = -r_pe;
-      lds_fence32();
+      lds_fence();
 #pragma unroll
       for (int c = 0; c < NT; ++c) {
         const f4 rv = *(const f4*)(tmp + 16 * c + 4 * g);
@@ -1218,7 +1113,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
           for (int c = 0; c < NT; ++c) dxn[c] = xb[c];
           stv32<NT>(tmp, j, dxn);  // dx, natural order
         }
-        lds_fence32();
+        lds_fence();
         ap = 1.0f; ad = 1.0f; dsv = 0.0f; dzv = 0.0f;
         if (lane < m) {
           dsv = ca * tmp[cvar] + r_pi;                                         // qp.cc:361
@@ -1260,12 +1155,12 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
         mu_pc = (ratio * ratio * ratio) * mu;                                          // qp.cc:182-183
         // The corrector solve (qp.cc:187): same matrix, right-hand side with ds_aff dz_aff and sigma mu -- through the factors
         for (int i = lane; i < N; i += 64) rhoS[i] = 0.0f;
-        lds_fence32();
+        lds_fence();
         if (lane < m) {
           const float zs = cz * cs_inv;
           atomicAdd(&rhoS[cvar], ca * zs * r_pi + ca * (r_comp + aff - mu_pc) * cs_inv);  // qp.cc:340-341
         }
-        lds_fence32();
+        lds_fence();
         float rb[NT + 1];
         {
           float rr[NT];
@@ -1321,14 +1216,9 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_solve_kernel(con
         ((float*)ka->lagrange)[2 * p + 1] = k > 0 ? yabs : nanf32;
       }
     }
-    wait_vmcnt32<0>();  // nothing of this problem's ring traffic is left in flight (a pass may leave through a break)
-    lds_fence32();
-    if (last_of_chunk) {
-      p = uniform64(next_ticket) + ticket_base;
-      chunk_end = p + next_chunk;
-    } else {
-      ++p;
-    }
+    wait_vmcnt<0>();  // nothing of this problem's ring traffic is left in flight (a pass may leave through a break)
+    lds_fence();
+    if (last_of_chunk) { p = queue_ticket_problem(next_ticket, ticket_base); chunk_end = p + next_chunk; } else { ++p; }
   }
 }
 
@@ -1346,31 +1236,15 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
   char* const smem = smem_all + wave * WAVE_LDS;
   const unsigned ring_base = (unsigned)(uintptr_t)smem;
   const int nsteps = a.m_r >> 2;
-  const int chunk_shift = 63 - __builtin_clzll((unsigned long long)gridDim.x * WAVES * 4);
-  // Small launches -- at most a.static_rounds problems per wave -- are split STATICALLY, round by round, in slot-major wave order (first one wave on
-  // every SIMD of every CU, then the second wave of every SIMD, ...): no ticket at all.  A wave must otherwise wait for a ticket just to
-  // learn that nothing is left, and 3 072 waves asking one counter word at ~88 M atomics/s is 35 us -- as long as the whole first round of
-  // BASELINE configs[1] (4 096 problems).  A partial round then also lands one wave per SIMD instead of three per SIMD on a third of the CUs.
+  // which problem this wave works on next: the hand-out policy of mo_fused_device.h
+  const int chunk_shift = queue_chunk_shift<WAVES>();
   const long long waves_all = (long long)gridDim.x * WAVES;
   const bool st_rounds = a.static_rounds > 0 && a.batch <= (long long)a.static_rounds * waves_all;   // wave-uniform
-  auto chunk_for = [&](long long observed) -> int {
+  auto chunk_for = [&](long long observed) -> int {   // chunk size when `observed` problems are known to be handed out (mo_fused_device.h)
     if (st_rounds) return 1;
     const long long c = (a.batch - observed) >> chunk_shift;
     return c < 1 ? 1 : (c > 8 ? 8 : (int)c);
   };
-  auto take_ticket = [&](int chunk, long long p_now) -> unsigned long long {
-    if (st_rounds) return (unsigned long long)p_now;   // static rounds: the next problem of this wave is p_now + waves_all (= "ticket" p_now + ticket_base)
-    unsigned long long t = 0;
-    if (lane_id32() == 0) t = atomicAdd(a.ticket, (unsigned long long)chunk);
-    return t;
-  };
-  auto uniform64 = [](unsigned long long v) -> long long {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-  };
-  // The FIRST chunk of every wave is static (wave w of the persistent grid takes problems [w c0, (w + 1) c0)); tickets from the counter start
-  // behind that part.  All waves asking one counter word for their first ticket at kernel start costs 3 072 / 88 M atomics/s = 35 us: most
-  // of a small launch (BASELINE configs[1]: 4 096 problems) and 2 % of the headline one.
   int chunk = chunk_for(0);
   const long long ticket_base = (long long)gridDim.x * WAVES * chunk;
   long long p = st_rounds ? (long long)(wave >> 2) * ((long long)gridDim.x * 4) + (long long)blockIdx.x * 4 + (wave & 3) : ((long long)blockIdx.x * WAVES + wave) * chunk;
@@ -1379,16 +1253,19 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
     const bool last_of_chunk = p + 1 >= chunk_end;
     int next_chunk = 0;
     unsigned long long next_ticket = 0;
-    if (last_of_chunk) { next_chunk = chunk_for(p); next_ticket = take_ticket(next_chunk, p); }
-    const int lane = lane_id32();
+    if (last_of_chunk) {
+      next_chunk = chunk_for(p);
+      next_ticket = queue_take_ticket(a, st_rounds, next_chunk, p);
+    }
+    const int lane = lane_id();
     const int g = lane >> 4, j = lane & 15;
     const char* jsrc = reinterpret_cast<const char*>((const float*)a.J + p * a.J_stride + (size_t)g * N + 4 * j);
     const char* rsrc = reinterpret_cast<const char*>((const float*)a.r + p * a.r_stride);
     auto issue = [&](int slot) {
       const unsigned dst = ring_base + slot * SLOT;
 #pragma unroll
-      for (int h = 0; h < NH; ++h) dma16_f32(jsrc + 256 * h, dst + h * 1024);
-      if (lane < 1) dma16_f32(rsrc, dst + NH * 1024);
+      for (int h = 0; h < NH; ++h) dma16(jsrc + 256 * h, dst + h * 1024);
+      if (lane < 1) dma16(rsrc, dst + NH * 1024);
       jsrc += 4 * N * 4;
       rsrc += 16;
     };
@@ -1409,10 +1286,10 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
         const int q = q0 + u;
         if (q < nsteps) {
           const int younger = nsteps - 1 - q;
-          if (younger >= D - 1) wait_vmcnt32<(D - 1) * DPS>();
-          else if (younger == 2) wait_vmcnt32<2 * DPS>();
-          else if (younger == 1) wait_vmcnt32<1 * DPS>();
-          else wait_vmcnt32<0>();
+          if (younger >= D - 1) wait_vmcnt<(D - 1) * DPS>();
+          else if (younger == 2) wait_vmcnt<2 * DPS>();
+          else if (younger == 1) wait_vmcnt<1 * DPS>();
+          else wait_vmcnt<0>();
           float ops[NT];
 #pragma unroll
           for (int h = 0; h < NH; ++h) {
@@ -1420,7 +1297,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
             ops[4 * h] = v[0]; ops[4 * h + 1] = v[1]; ops[4 * h + 2] = v[2]; ops[4 * h + 3] = v[3];
           }
           const float rq = *(const float*)(r_elem + u * SLOT);
-          lds_fence32();
+          lds_fence();
           if (q + D < nsteps) issue(u);
           rsq = fmaf(rq, rq, rsq);
 #pragma unroll
@@ -1433,7 +1310,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
         }
       }
     }
-    wait_vmcnt32<0>();
+    wait_vmcnt<0>();
     const float half_sq = 0.5f * cross_row_sum_f32(rsq);  // every lane of row g holds the sum over its rows 4s + g
     const float lam_in = a.lambda_vec ? ((const float*)a.lambda_vec)[p * a.lambda_vec_stride] : (float)a.lambda;
     const float lam = lam_in > 0.0f ? lam_in : 0.0f;  // nonlinear.cc:187-189
@@ -1476,7 +1353,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
                 }
               }
             }
-            lds_fence32();
+            lds_fence();
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
               const int e = it * 256 + lane * 4;
@@ -1485,7 +1362,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
               *(f4*)(Go + (64 * sb + row) + (size_t)(64 * sa + col) * ld) = v;
               if (sa != sb) *(f4*)(Go + (64 * sa + row) + (size_t)(64 * sb + col) * ld) = f4{0.0f, 0.0f, 0.0f, 0.0f};   // strict upper triangle: exactly zero
             }
-            lds_fence32();
+            lds_fence();
           }
         }
       }
@@ -1514,8 +1391,8 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f32_linearize_kernel
       for (int c = 0; c < NT; ++c) co[natvar32(c, j)] = cvec[c];
     }
     if (lane == 0 && a.half_sq_out) ((float*)a.half_sq_out)[p * (a.half_sq_stride ? a.half_sq_stride : 1)] = half_sq;
-    lds_fence32();
-    if (last_of_chunk) { p = uniform64(next_ticket) + ticket_base; chunk_end = p + next_chunk; } else { ++p; }
+    lds_fence();
+    if (last_of_chunk) { p = queue_ticket_problem(next_ticket, ticket_base); chunk_end = p + next_chunk; } else { ++p; }
   }
 }
 

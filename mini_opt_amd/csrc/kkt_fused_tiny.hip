@@ -61,16 +61,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_tiny_kernel(const KernelAr
     const long long c = (batch - observed) >> chunk_shift;
     return c < floor_chunk ? floor_chunk : (c > 64 ? 64 : (int)c);
   };
-  auto take_ticket = [&](int chunk) -> unsigned long long {
-    unsigned long long t = 0;
-    if (lane_id() == 0) t = atomicAdd(fresh_args()->ticket, (unsigned long long)chunk);
-    return t;
-  };
-  auto uniform64 = [](unsigned long long v) -> long long {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-  };
-  // the first ticket of every wave is static (see kkt_fused.hip): tickets from the counter start behind that part
+  // the first ticket of every wave is static (see mo_fused_device.h): tickets from the counter start behind that part
   int chunk = chunk_for(0);
   const long long ticket_base = (long long)gridDim.x * WAVES * chunk;
   long long base = ((long long)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * chunk;
@@ -78,7 +69,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_tiny_kernel(const KernelAr
   while (base < batch) {
     const int len = (batch - base < chunk) ? (int)(batch - base) : chunk;
     const int next_chunk = chunk_for(base);
-    const unsigned long long next_ticket = take_ticket(next_chunk);   // asked for early: its latency hides under this ticket's problems
+    const unsigned long long next_ticket = take_counter_ticket(fresh_args()->ticket, next_chunk);   // asked for early: its latency hides under this ticket's problems
     unsigned long long active;
     {
       KArgs kq = fresh_args();

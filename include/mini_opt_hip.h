@@ -38,7 +38,7 @@ extern "C" {
 #endif
 
 #define MO_VERSION_MAJOR 0
-#define MO_VERSION_MINOR 2
+#define MO_VERSION_MINOR 3
 
 /* return codes */
 #define MO_OK 0
@@ -454,6 +454,43 @@ typedef struct {
 } mo_qp_grads;
 int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* u,
                     int64_t u_stride, const mo_qp_grads* out, void* stream);
+
+/* The same gradients for RESIDUAL-BLOCK input (the packed local Jacobians of a mo_residual_layout), without forming an n x n or an
+ * m_r x n matrix: the transpose of the gather mo_linearize_blocks / mo_jacobian_blocks perform, applied to the pair (x, u_x).
+ * mo_linearize_blocks forms, per block b and local pair q <= p, G_low[max(i, j), min(i, j)] += J_b[:, p] . J_b[:, q] with i = idx_b[p],
+ * j = idx_b[q] (residual.hpp:206-224), c[idx_b[p]] += J_b[:, p] . r_b, and lambda on the diagonal after the sum.  With the loss gradient
+ * of the LOWER entries, W[i][j] = -(u_i x_j + x_i u_j) for i > j and W[i][i] = -u_i x_i (u = u_x), transposing the pair map gives
+ *   dJ_b[:, p] = sum_q w_b(p, q) J_b[:, q] - u[idx_b[p]] r_b
+ *       w_b(p, p) = -2 u_i x_i                    (i = idx_b[p])
+ *       w_b(p, q) = -u_i x_i                      q != p on the SAME variable i (a repeated index: the pair lands once, on the diagonal)
+ *       w_b(p, q) = -(u_i x_j + x_i u_j)          otherwise (j = idx_b[q])
+ *   dr_b = -sum_p u[idx_b[p]] J_b[:, p]           dlambda = -u_x . x   (lambda counts only where it was added: lambda > 0)
+ * The kernel evaluates it as  dJ_b[q, p] = -u_p t_b[q] - x_p w_b[q] + sum over the OTHER local columns q' on p's variable of
+ * (u_p x_p) J_b[q, q']  with t_b = J_b x_loc + r_b, w_b = J_b u_loc (x_loc[p] = x[idx_b[p]]); dr_b = -w_b.  Without repeated indices
+ * the last sum is empty (the partner lists are built by mo_residual_layout_create and are empty for almost every layout).
+ * The plan is that of the (G, c) solve: it supplies n, k, m, dtype and device (vars, u: [batch][V]); no m_r requirement.  The layout's n
+ * must equal the plan's.  J_stride / r_stride 0 = one instance shared by the batch; outputs are always per problem, dJ_blocks in the order
+ * and packing of J_blocks.  A NULL member of mo_block_grads is neither computed nor written; J_blocks and r are read only for dJ_blocks /
+ * dr.  Arguments are judged before the plan is looked at.  Every output element has one owner and a fixed order of operations, products
+ * are rounded before they are added: no atomics, two launches give the same bits.  No allocation and no synchronisation on the launch
+ * path: the backward schedule is part of the layout.  MO_ERR_UNSUPPORTED if 2 (n + sum R_b) values exceed 63 KiB (the vectors the kernel
+ * keeps in LDS). */
+typedef struct {
+  void* dJ_blocks; int64_t dJ_stride;     /* sum R_b P_b per problem, the order and packing of J_blocks */
+  void* dr;        int64_t dr_stride;     /* sum R_b */
+  void* dlambda;   int64_t dlambda_stride;
+} mo_block_grads;
+int mo_qp_gradients_blocks(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride, const void* r,
+                           int64_t r_stride, int64_t batch, const void* vars, int64_t vars_stride, const void* u, int64_t u_stride,
+                           const mo_block_grads* out, void* stream);
+/* Equality blocks (mo_jacobian_blocks: columns ASSIGNED, a duplicate index keeps the last local column; A_eq = the stack, b_eq = r_eq).
+ * With dA_eq = y u_x^T - u_y x^T and row = the block's first row + q:
+ *   dJeq_b[q, a] = y[row] u_x[idx_b[a]] - u_y[row] x[idx_b[a]]   if local column a is the one that wins its global column, else exactly 0
+ *   dr_eq[row]   = -u_y[row]
+ * The layout's rows must equal the plan's k.  dJ_eq_blocks and dr_eq may each be NULL.  Reads no block values. */
+int mo_qp_gradients_eq_blocks(mo_plan* plan, const mo_residual_layout* eq_layout, int64_t batch, const void* vars, int64_t vars_stride,
+                              const void* u, int64_t u_stride, void* dJ_eq_blocks, int64_t dJ_eq_stride, void* dr_eq,
+                              int64_t dr_eq_stride, void* stream);
 
 #ifdef __cplusplus
 }

@@ -34,7 +34,8 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_qp_solve", "mo_fill_qp", "mo_nonlinear_errors", "mo_qp_cost_derivative",
            "mo_default_nls_params", "mo_nls_solve", "mo_nullspace_solve", "mo_residual_eval", "mo_qp_eigenvalue_stats",
            "mo_residual_layout_create", "mo_residual_layout_destroy", "mo_residual_layout_values", "mo_residual_layout_rows",
-           "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks", "mo_kkt_solve", "mo_qp_gradients"]
+           "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks", "mo_kkt_solve", "mo_qp_gradients",
+           "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks"]
 
 
 class PlanDesc(C.Structure):
@@ -93,6 +94,13 @@ class QPGrads(C.Structure):
                 ("db_eq", C.c_void_p), ("db_stride", C.c_int64),
                 ("dcons_a", C.c_void_p), ("dcons_b", C.c_void_p), ("dcons_stride", C.c_int64),
                 ("dJ", C.c_void_p), ("dJ_stride", C.c_int64), ("dJ_ld", C.c_int32), ("dJ_layout", C.c_int32),
+                ("dr", C.c_void_p), ("dr_stride", C.c_int64),
+                ("dlambda", C.c_void_p), ("dlambda_stride", C.c_int64)]
+
+
+class BlockGrads(C.Structure):
+    """mo_block_grads: optional device outputs of mo_qp_gradients_blocks, in the packed layouts of the residual-block input."""
+    _fields_ = [("dJ_blocks", C.c_void_p), ("dJ_stride", C.c_int64),
                 ("dr", C.c_void_p), ("dr_stride", C.c_int64),
                 ("dlambda", C.c_void_p), ("dlambda_stride", C.c_int64)]
 
@@ -173,6 +181,8 @@ def lib() -> C.CDLL:
     L.mo_nls_solve_blocks.argtypes = [vp, C.POINTER(NlsProblem), vp, vp, i64, C.POINTER(NlsParams), NLS_EVAL_FN, vp, vp, vp, vp, vp, vp]
     L.mo_kkt_solve.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, u32, vp, i64, vp, vp]
     L.mo_qp_gradients.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, C.POINTER(QPGrads), vp]
+    L.mo_qp_gradients_blocks.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.POINTER(BlockGrads), vp]
+    L.mo_qp_gradients_eq_blocks.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what the header declares
     _lib = L

@@ -333,6 +333,18 @@ class BatchedQPInteriorPointSolver {
              int32_t* num_iterations, void* iterations, void* lagrange, int32_t* status, hipStream_t stream = nullptr) {
     detail::check(mo_qp_solve(plan_, &prob, batch, &params, vars, vars_stride, termination, num_iterations, iterations, lagrange, status, stream));
   }
+  // Gradients of a loss with respect to packed residual blocks from the state and the adjoint u = K^-T g (mo_kkt_solve, MO_KKT_TRANSPOSE)
+  void GradientsBlocks(const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride, const void* r, int64_t r_stride,
+                       int64_t batch, const void* vars, int64_t vars_stride, const void* u, int64_t u_stride, const mo_block_grads& out,
+                       hipStream_t stream = nullptr) {
+    detail::check(mo_qp_gradients_blocks(plan_, cost_layout, J_blocks, J_stride, r, r_stride, batch, vars, vars_stride, u, u_stride, &out, stream));
+  }
+  void GradientsEqBlocks(const mo_residual_layout* eq_layout, int64_t batch, const void* vars, int64_t vars_stride, const void* u,
+                         int64_t u_stride, void* dJ_eq_blocks, int64_t dJ_eq_stride, void* dr_eq, int64_t dr_eq_stride,
+                         hipStream_t stream = nullptr) {
+    detail::check(mo_qp_gradients_eq_blocks(plan_, eq_layout, batch, vars, vars_stride, u, u_stride, dJ_eq_blocks, dJ_eq_stride, dr_eq,
+                                            dr_eq_stride, stream));
+  }
   const char* StepKernel(const mo_problem& prob) const { return mo_plan_step_kernel(plan_, &prob); }
   const char* KktSolveKernel(const mo_problem& prob) const { return mo_plan_kkt_solve_kernel(plan_, &prob); }
   mo_plan* plan() const { return plan_; }

@@ -57,6 +57,8 @@ struct mo_residual_layout {
   long long values;
   void* dev;
   const int* g_ptr; const int4* g_ent; const int* c_ptr; const int4* c_ent; const int2* row_info; const int* win;
+  // the backward schedule (mo_qp_gradients_blocks / mo_qp_gradients_eq_blocks, mo::BlockGradArgs)
+  const int4* d_row; const int4* d_val; const int2* e_val; const int* d_idx; const int* d_dup;
 };
 
 namespace {
@@ -204,7 +206,7 @@ struct NlsScratch {  // one allocation carved into 256-byte aligned pieces
 
 extern "C" {
 
-const char* mo_version_string(void) { return "mini_opt_hip 0.2 (gfx950)"; }
+const char* mo_version_string(void) { return "mini_opt_hip 0.3 (gfx950)"; }
 
 const char* mo_status_string(int32_t status) {
   switch (status) {
@@ -713,6 +715,16 @@ int check_layout(const mo_plan* plan, const mo_residual_layout* layout) {
   return MO_OK;
 }
 
+mo::BlockGradArgs block_grad_args(const mo_plan* plan, const mo_residual_layout* l, int64_t batch, const void* vars, int64_t vars_stride,
+                                  const void* u, int64_t u_stride) {
+  mo::BlockGradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = plan->desc.n; a.k = plan->desc.k; a.m = plan->desc.m; a.rows = l->rows; a.values = l->values; a.batch = batch;
+  a.d_row = l->d_row; a.d_idx = l->d_idx; a.d_val = l->d_val; a.d_dup = l->d_dup; a.e_val = l->e_val;
+  a.vars = vars; a.vars_stride = vars_stride; a.u = u; a.u_stride = u_stride;
+  return a;
+}
+
 // The SQP loop of mo_nls_solve and mo_nls_solve_blocks.  Without block input (dense stacks) it launches exactly the kernels of
 // mo_nls_solve; with block input every outer iteration first forms G, c and A_eq from the packed blocks into per-call scratch and the QP,
 // the eigenvalue statistics and the directional derivatives read that (G, c) input.
@@ -1032,15 +1044,47 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
       ib += P; off += (long long)R * P; roff += R;
     }
   }
-  // one device allocation: [g_ent | c_ent | g_ptr | c_ptr | row_info | win], 16-byte aligned pieces
+  // the backward schedule: per stacked row where its block lives, per packed value its row, its variable and the other local columns on
+  // that variable (almost always none), and for equality blocks whether the value's column is the one that won its global column
+  std::vector<int4> d_row((size_t)total_rows), d_val((size_t)values);
+  std::vector<int2> e_val((size_t)values);
+  std::vector<int> d_idx(index, index + total_idx), d_dup;
+  {
+    long long ib = 0, off = 0, roff = 0;
+    for (int b = 0; b < num_blocks; ++b) {
+      const int R = rows[b], P = params[b];
+      const int32_t* idx = index + ib;
+      for (int q = 0; q < R; ++q) d_row[(size_t)(roff + q)] = make_int4((int)(off + q), R, P, (int)ib);
+      for (int a = 0; a < P; ++a) {
+        int partners = 0;
+        for (int c = 0; c < P; ++c) partners += c != a && idx[c] == idx[a];
+        int dup = -1;
+        if (partners) {
+          dup = (int)d_dup.size();
+          d_dup.push_back(partners);
+          for (int c = 0; c < P; ++c)
+            if (c != a && idx[c] == idx[a]) d_dup.push_back((int)(off + (long long)c * R));
+        }
+        const bool wins = win[(size_t)b * n + idx[a]] == (int)(off + (long long)a * R);
+        for (int q = 0; q < R; ++q) {
+          d_val[(size_t)(off + (long long)a * R + q)] = make_int4((int)(roff + q), idx[a], q, dup);
+          e_val[(size_t)(off + (long long)a * R + q)] = make_int2((int)(roff + q), wins ? idx[a] : -1);
+        }
+      }
+      ib += P; off += (long long)R * P; roff += R;
+    }
+  }
+  // one device allocation: [g_ent | c_ent | g_ptr | c_ptr | row_info | win | d_row | d_val | e_val | d_idx | d_dup], 16-byte aligned pieces
   auto pad = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
   const size_t b_ge = pad(g_ent.size() * sizeof(int4)), b_ce = pad(c_ent.size() * sizeof(int4)), b_gp = pad(g_ptr.size() * sizeof(int)),
-               b_cp = pad(c_ptr.size() * sizeof(int)), b_ri = pad(row_info.size() * sizeof(int2)), b_w = pad(win.size() * sizeof(int));
+               b_cp = pad(c_ptr.size() * sizeof(int)), b_ri = pad(row_info.size() * sizeof(int2)), b_w = pad(win.size() * sizeof(int)),
+               b_dr = pad(d_row.size() * sizeof(int4)), b_dv = pad(d_val.size() * sizeof(int4)), b_ev = pad(e_val.size() * sizeof(int2)),
+               b_di = pad(d_idx.size() * sizeof(int)), b_dd = pad(d_dup.size() * sizeof(int));
   mo_residual_layout* L = new (std::nothrow) mo_residual_layout();
   if (!L) return fail(MO_ERR_HIP, "out of host memory");
   L->device = plan->desc.device; L->n = n; L->num_blocks = num_blocks; L->rows = (int)total_rows; L->values = values;
   L->dev = nullptr;
-  const size_t total = b_ge + b_ce + b_gp + b_cp + b_ri + b_w;
+  const size_t total = b_ge + b_ce + b_gp + b_cp + b_ri + b_w + b_dr + b_dv + b_ev + b_di + b_dd;
   if (hipSetDevice(plan->desc.device) != hipSuccess || hipMalloc(&L->dev, total) != hipSuccess) {
     (void)hipGetLastError();
     delete L;
@@ -1050,10 +1094,13 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
   struct Piece { const void* src; size_t bytes, padded; } pieces[] = {
       {g_ent.data(), g_ent.size() * sizeof(int4), b_ge}, {c_ent.data(), c_ent.size() * sizeof(int4), b_ce},
       {g_ptr.data(), g_ptr.size() * sizeof(int), b_gp},  {c_ptr.data(), c_ptr.size() * sizeof(int), b_cp},
-      {row_info.data(), row_info.size() * sizeof(int2), b_ri}, {win.data(), win.size() * sizeof(int), b_w}};
+      {row_info.data(), row_info.size() * sizeof(int2), b_ri}, {win.data(), win.size() * sizeof(int), b_w},
+      {d_row.data(), d_row.size() * sizeof(int4), b_dr}, {d_val.data(), d_val.size() * sizeof(int4), b_dv},
+      {e_val.data(), e_val.size() * sizeof(int2), b_ev}, {d_idx.data(), d_idx.size() * sizeof(int), b_di},
+      {d_dup.data(), d_dup.size() * sizeof(int), b_dd}};
   size_t at = 0;
-  const void* dst[6];
-  for (int i = 0; i < 6; ++i) {
+  const void* dst[11];
+  for (int i = 0; i < 11; ++i) {
     dst[i] = base + at;
     if (pieces[i].bytes && hipMemcpy(base + at, pieces[i].src, pieces[i].bytes, hipMemcpyHostToDevice) != hipSuccess) {
       (void)hipGetLastError();
@@ -1065,6 +1112,8 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
   }
   L->g_ent = (const int4*)dst[0]; L->c_ent = (const int4*)dst[1]; L->g_ptr = (const int*)dst[2]; L->c_ptr = (const int*)dst[3];
   L->row_info = (const int2*)dst[4]; L->win = (const int*)dst[5];
+  L->d_row = (const int4*)dst[6]; L->d_val = (const int4*)dst[7]; L->e_val = (const int2*)dst[8]; L->d_idx = (const int*)dst[9];
+  L->d_dup = (const int*)dst[10];
   *out = L;
   return MO_OK;
 }
@@ -1123,6 +1172,50 @@ int mo_jacobian_blocks(mo_plan* plan, const mo_residual_layout* layout, const vo
   a.abs_sum_out = abs_sum_out;
   MO_HIP_CHECK(hipSetDevice(plan->desc.device));
   MO_HIP_CHECK(mo::launch_blocks_jacobian(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+int mo_qp_gradients_blocks(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride, const void* r,
+                           int64_t r_stride, int64_t batch, const void* vars, int64_t vars_stride, const void* u, int64_t u_stride,
+                           const mo_block_grads* out, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
+  if (!vars) return fail(MO_ERR_INVALID_ARGUMENT, "vars is NULL");
+  if (!u) return fail(MO_ERR_INVALID_ARGUMENT, "u is NULL");
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if ((out->dJ_blocks || out->dr) && (!J_blocks || !r)) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_blocks / dr asked for but J_blocks / r is NULL");
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, cost_layout)) return rc;
+  if (!mo::blocks_grad_fits(plan->desc.n, cost_layout->rows, plan->elem))
+    return fail(MO_ERR_UNSUPPORTED, "n = %d, %d residual rows: the vectors of one problem exceed the 63 KiB of LDS the block gradient kernel uses", plan->desc.n, cost_layout->rows);
+  if (batch == 0 || (!out->dJ_blocks && !out->dr && !out->dlambda)) return MO_OK;
+  mo::BlockGradArgs a = block_grad_args(plan, cost_layout, batch, vars, vars_stride, u, u_stride);
+  a.J = J_blocks; a.J_stride = J_stride; a.r = r; a.r_stride = r_stride;
+  a.dJ = out->dJ_blocks; a.dJ_stride = out->dJ_stride; a.dr = out->dr; a.dr_stride = out->dr_stride;
+  a.dlambda = out->dlambda; a.dlambda_stride = out->dlambda_stride;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_blocks_grad(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+int mo_qp_gradients_eq_blocks(mo_plan* plan, const mo_residual_layout* eq_layout, int64_t batch, const void* vars, int64_t vars_stride,
+                              const void* u, int64_t u_stride, void* dJ_eq_blocks, int64_t dJ_eq_stride, void* dr_eq,
+                              int64_t dr_eq_stride, void* stream) {
+  g_err[0] = 0;
+  if (!eq_layout) return fail(MO_ERR_INVALID_ARGUMENT, "eq_layout is NULL");
+  if (!vars) return fail(MO_ERR_INVALID_ARGUMENT, "vars is NULL");
+  if (!u) return fail(MO_ERR_INVALID_ARGUMENT, "u is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, eq_layout)) return rc;
+  if (eq_layout->rows != plan->desc.k) return fail(MO_ERR_DIMENSION, "eq_layout has %d rows, plan k = %d", eq_layout->rows, plan->desc.k);
+  if (batch == 0 || (!dJ_eq_blocks && !dr_eq)) return MO_OK;
+  mo::BlockGradArgs a = block_grad_args(plan, eq_layout, batch, vars, vars_stride, u, u_stride);
+  a.dJ = dJ_eq_blocks; a.dJ_stride = dJ_eq_stride; a.dr = dr_eq; a.dr_stride = dr_eq_stride;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_blocks_eq_grad(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
   return MO_OK;
 }
 

@@ -191,6 +191,29 @@ struct BlocksArgs {
 hipError_t launch_blocks_linearize(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
 hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
 
+// gradients with respect to the packed block values (mo_qp_gradients_blocks / mo_qp_gradients_eq_blocks), residual_blocks.hip: the transpose
+// of the gathers above applied to (x, u_x).  The schedule is built by mo_residual_layout_create beside the forward one.
+struct BlockGradArgs {
+  int n, k, m, rows;          // plan n, k, m; sum R_b of the layout
+  long long values;
+  long long batch;
+  const int4* d_row;          // [rows] {offset of J_b[q, 0], R_b (the column stride), P_b, start of idx_b in d_idx}
+  const int* d_idx;           // the concatenated index lists
+  const int4* d_val;          // [values] {stacked row, global index, row within the block, start of the partner list in d_dup or -1}
+  const int* d_dup;           // partner lists: {count, count x offset of J_b[0, q']}: the other local columns q' on the same variable
+  const int2* e_val;          // [values] equality blocks: {stacked row, global index or -1 for a column that loses its global column}
+  const void* J; long long J_stride;
+  const void* r; long long r_stride;
+  const void* vars; long long vars_stride;
+  const void* u; long long u_stride;
+  void* dJ; long long dJ_stride;
+  void* dr; long long dr_stride;
+  void* dlambda; long long dlambda_stride;
+};
+bool blocks_grad_fits(int n, int rows, int elem_size);   // the vectors the kernel keeps in LDS (x, u_x, t, w) within 63 KiB
+hipError_t launch_blocks_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream);
+hipError_t launch_blocks_eq_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream);
+
 // gradients of a loss through the solution of a QP (mo_qp_gradients), qp_grad.hip: rank-2 updates of the state v = [x | s | y | z] and the
 // adjoint u = K^-T g.  Inputs that are not needed for the outputs asked for may be NULL (J, r only for dJ / dr).
 struct GradArgs {

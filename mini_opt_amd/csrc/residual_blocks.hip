@@ -2,6 +2,8 @@
 // residual is an R_b x P_b column-major local Jacobian over an index list of P_b of the n variables (Residual::Model, residual.hpp:60-143).
 //   blocks_linearize_kernel   sum_b UpdateHessian (residual.hpp:186-226) + lambda I: G (lower, strict upper 0), c, 0.5 |r|^2
 //   blocks_jacobian_kernel    UpdateJacobian stacked (residual.hpp:230-250): the dense (sum R_b) x n matrix, |r|_1
+//   blocks_grad_kernel        the transpose of the first gather applied to (x, u_x): dJ_blocks, dr, dlambda (mo_qp_gradients_blocks)
+//   blocks_eq_grad_kernel     the transpose of the second: dJ_eq_blocks, dr_eq (mo_qp_gradients_eq_blocks)
 // Gather formulation: mo_residual_layout_create lists, for every cell of G and every entry of c, its contributions
 // in the reference's order (blocks in order, then row_local / col_local).  A lane owns one cell at a time and sums its list in that order,
 // so there are no atomics, no G accumulator and the result is the same on every launch.  The schedule is shared by the batch: it stays in
@@ -13,6 +15,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr size_t kStageBudget = 48 * 1024;  // per workgroup: above it the packed values are read straight from global memory
+constexpr size_t kGradLds = 63 * 1024;      // blocks_grad_kernel: the vectors it always keeps in LDS (x, u_x, t, w) and, staged, the values on top
 
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
@@ -119,6 +122,114 @@ __global__ __launch_bounds__(kThreads) void blocks_jacobian_kernel(const BlocksA
   }
 }
 
+// mo_qp_gradients_blocks (the formulas: include/mini_opt_hip.h).  The same hand-out as blocks_linearize_kernel.  Phase 1: a lane owns a stacked
+// residual row (b, q) and walks the block's P_b columns in order: t = J_b x_loc + r_b, w = J_b u_loc, into LDS; dr = -w.  Phase 2: consecutive
+// lanes own consecutive packed values (column-major inside a block: whole-line stores), dJ = -u_p t[q] - x_p w[q] plus (u_p x_p) J_b[q, q'] for
+// every other local column q' on the same variable.  Every product is rounded before it is added.
+template <typename T, bool kStaged>
+__global__ __launch_bounds__(kThreads) void blocks_grad_kernel(const BlockGradArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ T red[kThreads / 64];
+  T* sx = reinterpret_cast<T*>(smem);
+  T* su = sx + a.n;
+  T* st = su + a.n;
+  T* sw = st + a.rows;
+  T* sJ = sw + a.rows;
+  T* sR = sJ + a.values;
+  const int tid = threadIdx.x;
+  const int n = a.n, rows = a.rows;
+  const bool need_rows = a.dJ || a.dr;
+  for (long long p = blockIdx.x; p < a.batch; p += gridDim.x) {
+    const T* vp = (const T*)a.vars + p * a.vars_stride;
+    const T* up = (const T*)a.u + p * a.u_stride;
+    const T* Jv = (const T*)a.J + p * a.J_stride;
+    const T* rv = (const T*)a.r + p * a.r_stride;
+    for (int i = tid; i < n; i += kThreads) { sx[i] = vp[i]; su[i] = up[i]; }
+    if (kStaged && need_rows) {
+      for (long long i = tid; i < a.values; i += kThreads) sJ[i] = Jv[i];
+      for (int i = tid; i < rows; i += kThreads) sR[i] = rv[i];
+      Jv = sJ;
+      rv = sR;
+    }
+    __syncthreads();
+    if (need_rows) {
+      T* dr = a.dr ? (T*)a.dr + p * a.dr_stride : nullptr;
+      for (int row = tid; row < rows; row += kThreads) {
+        const int4 ri = a.d_row[row];
+        T t = 0, w = 0;
+        for (int c = 0; c < ri.z; ++c) {
+          const int g = a.d_idx[ri.w + c];
+          const T v = Jv[ri.x + c * ri.y];
+          const T tx = v * sx[g], tu = v * su[g];
+          t += tx;
+          w += tu;
+        }
+        st[row] = t + rv[row];
+        sw[row] = w;
+        if (dr) dr[row] = -w;
+      }
+      __syncthreads();
+      if (a.dJ) {
+        T* dJ = (T*)a.dJ + p * a.dJ_stride;
+        for (long long e = tid; e < a.values; e += kThreads) {
+          const int4 vi = a.d_val[e];
+          const T ug = su[vi.y], xg = sx[vi.y];
+          const T p1 = ug * st[vi.x], p2 = xg * sw[vi.x];
+          T s = -p1 - p2;
+          if (vi.w >= 0) {  // a repeated variable inside the block: the pair landed once, on the diagonal
+            const T ux = ug * xg;
+            const int cnt = a.d_dup[vi.w];
+            for (int d = 1; d <= cnt; ++d) {
+              const T pd = ux * Jv[a.d_dup[vi.w + d] + vi.z];
+              s += pd;
+            }
+          }
+          dJ[e] = s;
+        }
+      }
+    }
+    if (a.dlambda) {
+      T s = 0;
+      for (int i = tid; i < n; i += kThreads) {
+        const T pr = su[i] * sx[i];
+        s += pr;
+      }
+      s = block_sum(s, red);
+      if (tid == 0) ((T*)a.dlambda)[p * a.dlambda_stride] = -s;
+    }
+    __syncthreads();  // the next problem overwrites the staged values, the vectors and the reduction slots
+  }
+}
+
+// mo_qp_gradients_eq_blocks: consecutive lanes own consecutive packed equality values; a column that lost its global column gets exactly 0
+template <typename T>
+__global__ __launch_bounds__(kThreads) void blocks_eq_grad_kernel(const BlockGradArgs a) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  const int yo = a.n + a.m;  // v = [x | s | y | z]
+  for (long long p = blockIdx.x; p < a.batch; p += gridDim.x) {
+    const T* vp = (const T*)a.vars + p * a.vars_stride;
+    const T* up = (const T*)a.u + p * a.u_stride;
+    if (a.dJ) {
+      T* dJ = (T*)a.dJ + p * a.dJ_stride;
+      for (long long e = tid; e < a.values; e += kThreads) {
+        const int2 vi = a.e_val[e];
+        T s = 0;
+        if (vi.y >= 0) {
+          const T p1 = vp[yo + vi.x] * up[vi.y], p2 = up[yo + vi.x] * vp[vi.y];
+          s = p1 - p2;
+        }
+        dJ[e] = s;
+      }
+    }
+    if (a.dr) {
+      T* dr = (T*)a.dr + p * a.dr_stride;
+      for (int i = tid; i < a.rows; i += kThreads) dr[i] = -up[yo + i];
+    }
+  }
+}
+
 // a workgroup per problem in turn: as many resident workgroups as the LDS allows, at most eight per CU (eight waves per SIMD)
 unsigned grid_for(long long batch, int num_cus, size_t lds_bytes) {
   long long per_cu = 8;
@@ -141,6 +252,17 @@ template <typename T> hipError_t launch_linearize_t(const BlocksArgs& a, int num
   return hipGetLastError();
 }
 
+template <typename T> hipError_t launch_grad_t(const BlockGradArgs& a, int num_cus, hipStream_t stream) {
+  const size_t vectors = (size_t)(2 * a.n + 2 * a.rows) * sizeof(T);
+  const size_t stage = (size_t)(a.values + a.rows) * sizeof(T);
+  if (stage <= kStageBudget && vectors + stage <= kGradLds) {
+    hipLaunchKernelGGL((blocks_grad_kernel<T, true>), dim3(grid_for(a.batch, num_cus, vectors + stage)), dim3(kThreads), vectors + stage, stream, a);
+  } else {
+    hipLaunchKernelGGL((blocks_grad_kernel<T, false>), dim3(grid_for(a.batch, num_cus, vectors)), dim3(kThreads), vectors, stream, a);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_blocks_linearize(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream) {
@@ -153,6 +275,22 @@ hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, h
   const dim3 g(grid_for(a.batch, num_cus, 0)), b(kThreads);
   if (dtype == MO_F64) hipLaunchKernelGGL(blocks_jacobian_kernel<double>, g, b, 0, stream, a);
   else hipLaunchKernelGGL(blocks_jacobian_kernel<float>, g, b, 0, stream, a);
+  return hipGetLastError();
+}
+
+bool blocks_grad_fits(int n, int rows, int elem_size) { return (size_t)(2 * (long long)n + 2 * (long long)rows) * elem_size <= kGradLds; }
+
+hipError_t launch_blocks_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream) {
+  if (a.batch <= 0) return hipSuccess;
+  if (!blocks_grad_fits(a.n, a.rows, dtype == MO_F64 ? 8 : 4)) return hipErrorInvalidValue;  // (mo_qp_gradients_blocks refuses with its own message)
+  return dtype == MO_F64 ? launch_grad_t<double>(a, num_cus, stream) : launch_grad_t<float>(a, num_cus, stream);
+}
+
+hipError_t launch_blocks_eq_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream) {
+  if (a.batch <= 0) return hipSuccess;
+  const dim3 g(grid_for(a.batch, num_cus, 0)), b(kThreads);
+  if (dtype == MO_F64) hipLaunchKernelGGL(blocks_eq_grad_kernel<double>, g, b, 0, stream, a);
+  else hipLaunchKernelGGL(blocks_eq_grad_kernel<float>, g, b, 0, stream, a);
   return hipGetLastError();
 }
 

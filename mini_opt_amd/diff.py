@@ -2,6 +2,7 @@
 
     kkt_solve       mo_kkt_solve     the KKT system of a state for the caller's right-hand side (direct or transposed)
     qp_gradients    mo_qp_gradients  gradients of a loss with respect to the QP's data from the state v and the adjoint u = K^-T g
+    qp_gradients_blocks, qp_gradients_eq_blocks    the same for residual-block input: gradients of the PACKED local Jacobians
     solve_qp        the user-facing call: forward = Solve (the kernels of qp.QPInteriorPointSolver, fused where the shape allows),
                     backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient
 
@@ -16,7 +17,7 @@ from typing import Dict, Iterable, Optional
 import torch
 
 from . import _lib as L
-from .qp import _DT, BatchedQP, Params, _ptr, _stream
+from .qp import _DT, BatchedQP, Params, ResidualLayout, _ptr, _stream, jacobian_blocks, linearize_blocks
 
 _PLANS: Dict[tuple, C.c_void_p] = {}
 GRADIENTS = ("G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b")
@@ -24,11 +25,14 @@ GRADIENTS = ("G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b")
 
 def plan_for(problem: BatchedQP, batch: int) -> C.c_void_p:
     """The cached plan of (shape, dtype, device, batch); created on first use, kept until clear_plan_cache()."""
-    dev = problem.device
-    key = (problem.n, problem.k, problem.m, problem.m_r, problem.dtype, dev.index or 0, int(batch))
+    return _plan_of(problem.n, problem.k, problem.m, problem.m_r, problem.dtype, problem.device, batch)
+
+
+def _plan_of(n: int, k: int, m: int, m_r: int, dtype, dev, batch: int) -> C.c_void_p:
+    key = (n, k, m, m_r, dtype, dev.index or 0, int(batch))
     plan = _PLANS.get(key)
     if plan is None:
-        desc = L.PlanDesc(problem.n, problem.k, problem.m, problem.m_r, _DT[problem.dtype], dev.index or 0, L.EXTRA_PLAN_FLAGS, 0, int(batch))
+        desc = L.PlanDesc(n, k, m, m_r, _DT[dtype], dev.index or 0, L.EXTRA_PLAN_FLAGS, 0, int(batch))
         plan = C.c_void_p()
         L.check(L.lib().mo_plan_create(C.byref(desc), C.byref(plan)))
         _PLANS[key] = plan
@@ -183,6 +187,129 @@ class QPSolveFunction(torch.autograd.Function):
         return (*out, None, None)
 
 
+def _check_vu(layout: ResidualLayout, vars: torch.Tensor, u: torch.Tensor, k: int, m: int) -> int:
+    V = layout.n + 2 * int(m) + int(k)
+    for t, name in ((vars, "vars"), (u, "u")):
+        if t.dim() != 2 or int(t.shape[1]) != V or not t.is_contiguous() or t.dtype != layout.dtype or t.device != layout.device:
+            raise ValueError(f"{name}: expected a contiguous [B, {V}] {layout.dtype} tensor on {layout.device}, got {tuple(t.shape)} {t.dtype}")
+    if vars.shape[0] != u.shape[0]:
+        raise ValueError("vars and u must have the same batch")
+    return int(vars.shape[0])
+
+
+def qp_gradients_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, vars: torch.Tensor, u: torch.Tensor, k: int = 0,
+                        m: int = 0, want: Iterable[str] = ("J_blocks", "r", "lam")) -> Dict[str, torch.Tensor]:
+    """mo_qp_gradients_blocks: gradients of a loss with respect to the packed cost blocks of `layout` (the inputs of linearize_blocks) from the
+    state `vars` [B, V] and the adjoint `u` [B, V] of the (G, c) problem they were linearised into; k, m: that problem's equality and
+    inequality rows (V = n + 2 m + k).  J_blocks [B or 1, values], r [B or 1, rows] (1: shared by the batch; the outputs are per problem).
+    Returns the ones named in `want`: "J_blocks" [B, values] (the packing of J_blocks), "r" [B, rows], "lam" [B]."""
+    want = tuple(want)
+    for w in want:
+        if w not in ("J_blocks", "r", "lam"):
+            raise ValueError(f"unknown gradient {w!r}: one of ('J_blocks', 'r', 'lam')")
+    B = _check_vu(layout, vars, u, k, m)
+    for t, w, name in ((J_blocks, layout.values, "J_blocks"), (r, layout.rows, "r")):
+        if t.dim() != 2 or int(t.shape[1]) != w or int(t.shape[0]) not in (1, B) or not t.is_contiguous() or t.dtype != layout.dtype or t.device != layout.device:
+            raise ValueError(f"{name}: expected a contiguous [{B} or 1, {w}] {layout.dtype} tensor on {layout.device}, got {tuple(t.shape)} {t.dtype}")
+    new = lambda *shape: torch.empty(*shape, dtype=layout.dtype, device=layout.device)
+    out: Dict[str, torch.Tensor] = {}
+    g = L.BlockGrads()
+    if "J_blocks" in want:
+        out["J_blocks"] = new(B, layout.values)
+        g.dJ_blocks, g.dJ_stride = _ptr(out["J_blocks"]), layout.values
+    if "r" in want:
+        out["r"] = new(B, layout.rows)
+        g.dr, g.dr_stride = _ptr(out["r"]), layout.rows
+    if "lam" in want:
+        out["lam"] = new(B)
+        g.dlambda, g.dlambda_stride = _ptr(out["lam"]), 1
+    plan = _plan_of(layout.n, int(k), int(m), 0, layout.dtype, layout.device, B)
+    L.check(L.lib().mo_qp_gradients_blocks(plan, layout.h, _ptr(J_blocks), 0 if J_blocks.shape[0] == 1 else layout.values, _ptr(r),
+                                           0 if r.shape[0] == 1 else layout.rows, B, _ptr(vars), int(vars.shape[1]), _ptr(u), int(u.shape[1]),
+                                           C.byref(g), _stream()))
+    return out
+
+
+def qp_gradients_eq_blocks(eq_layout: ResidualLayout, vars: torch.Tensor, u: torch.Tensor, m: int = 0,
+                           want: Iterable[str] = ("J_eq_blocks", "r_eq")) -> Dict[str, torch.Tensor]:
+    """mo_qp_gradients_eq_blocks: gradients with respect to the packed equality blocks of `eq_layout` (the inputs of jacobian_blocks; k = its
+    rows) from `vars`, `u` [B, n + 2 m + k]: "J_eq_blocks" [B, values] (exactly 0 for a column that loses its global column), "r_eq" [B, k]."""
+    want = tuple(want)
+    for w in want:
+        if w not in ("J_eq_blocks", "r_eq"):
+            raise ValueError(f"unknown gradient {w!r}: one of ('J_eq_blocks', 'r_eq')")
+    k = eq_layout.rows
+    B = _check_vu(eq_layout, vars, u, k, m)
+    out: Dict[str, torch.Tensor] = {}
+    if "J_eq_blocks" in want:
+        out["J_eq_blocks"] = torch.empty(B, eq_layout.values, dtype=eq_layout.dtype, device=eq_layout.device)
+    if "r_eq" in want:
+        out["r_eq"] = torch.empty(B, k, dtype=eq_layout.dtype, device=eq_layout.device)
+    plan = _plan_of(eq_layout.n, k, int(m), 0, eq_layout.dtype, eq_layout.device, B)
+    L.check(L.lib().mo_qp_gradients_eq_blocks(plan, eq_layout.h, B, _ptr(vars), int(vars.shape[1]), _ptr(u), int(u.shape[1]),
+                                              _ptr(out.get("J_eq_blocks")), eq_layout.values, _ptr(out.get("r_eq")), k, _stream()))
+    return out
+
+
+def _masked(t: Optional[torch.Tensor], ok: torch.Tensor) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    return torch.where(ok.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros((), dtype=t.dtype, device=t.device))
+
+
+class QPSolveBlocksFunction(torch.autograd.Function):
+    """QPSolveFunction for residual-block input.  forward(J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, cons_var, layout, eq_layout,
+    params) -> (v, status): linearize_blocks gives (G, c), jacobian_blocks gives A_eq (b_eq = r_eq), mo_qp_solve runs on the (G, c) problem --
+    the sequence of mo_nls_solve_blocks.  The backward solves K(v)^T u = g once on that problem (the fused right-hand-side twin where
+    kkt_solve_kernel says so), launches mo_qp_gradients_blocks once, mo_qp_gradients_eq_blocks if an equality input requires a gradient and
+    mo_qp_gradients for cons_a / cons_b if asked.  No n x n or m_r x n gradient is formed.  lam's gradient counts only where lam was added
+    (lam > 0).  Zero gradients for problems whose forward or adjoint status is not OK, as QPSolveFunction."""
+
+    @staticmethod
+    def forward(ctx, J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, cons_var, layout, eq_layout, params):
+        det = lambda t: None if t is None else t.detach()
+        J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b = (det(t) for t in (J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b))
+        G, c, _ = linearize_blocks(layout, J_blocks, r, lam_vec=lam)
+        B, n = int(G.shape[0]), layout.n
+        k = 0 if eq_layout is None else eq_layout.rows
+        m = 0 if cons_a is None else int(cons_a.shape[1])
+        A_eq = None
+        if eq_layout is not None:
+            A_eq, _ = jacobian_blocks(eq_layout, J_eq_blocks, r_eq)       # [B, n, k]: memory = k x n column-major, BatchedQP's layout
+        problem = BatchedQP(n=n, k=k, m=m, G=G, c=c, A_eq=A_eq, b_eq=r_eq if k else None, cons_var=cons_var, cons_a=cons_a, cons_b=cons_b)
+        v = torch.zeros(B, problem.V, dtype=G.dtype, device=G.device)
+        term = torch.empty(B, dtype=torch.int32, device=G.device)
+        nit = torch.empty(B, dtype=torch.int32, device=G.device)
+        status = torch.empty(B, dtype=torch.int32, device=G.device)
+        prob, sp = problem.as_struct(), params.as_struct()
+        L.check(L.lib().mo_qp_solve(plan_for(problem, B), C.byref(prob), B, C.byref(sp), _ptr(v), problem.V, _ptr(term), _ptr(nit), None, None,
+                                    _ptr(status), _stream()))
+        ctx.problem, ctx.v, ctx.status = problem, v, status
+        ctx.layout, ctx.eq_layout, ctx.J_blocks, ctx.r, ctx.lam = layout, eq_layout, J_blocks, r, lam
+        ctx.adjoint_status = None
+        ctx.termination_state, ctx.num_iterations = term, nit
+        ctx.mark_non_differentiable(status)
+        return v.clone(), status
+
+    @staticmethod
+    def backward(ctx, g, _g_status):
+        problem, v = ctx.problem, ctx.v
+        u, adj = kkt_solve(problem, v, g.contiguous(), transpose=True)
+        ctx.adjoint_status = adj
+        need = ctx.needs_input_grad
+        ok = (ctx.status == L.MO_STATUS_OK) & (adj == L.MO_STATUS_OK)
+        want = [nm for nm, nd in zip(("J_blocks", "r", "lam"), need[:3]) if nd]
+        cost = qp_gradients_blocks(ctx.layout, ctx.J_blocks, ctx.r, v, u, k=problem.k, m=problem.m, want=want) if want else {}
+        if "lam" in cost:
+            cost["lam"] = torch.where(ctx.lam > 0, cost["lam"], torch.zeros((), dtype=v.dtype, device=v.device))
+        want = [nm for nm, nd in zip(("J_eq_blocks", "r_eq"), need[3:5]) if nd]
+        eq = qp_gradients_eq_blocks(ctx.eq_layout, v, u, m=problem.m, want=want) if want else {}
+        want = [nm for nm, nd in zip(("cons_a", "cons_b"), need[5:7]) if nd]
+        cons = qp_gradients(problem, v, u, want) if want else {}
+        out = [cost.get("J_blocks"), cost.get("r"), cost.get("lam"), eq.get("J_eq_blocks"), eq.get("r_eq"), cons.get("cons_a"), cons.get("cons_b")]
+        return (*[_masked(t, ok) for t in out], None, None, None, None)
+
+
 def adjoint_status(t: torch.Tensor) -> Optional[torch.Tensor]:
     """The [B] status words of the adjoint solve behind a tensor solve_qp returned (None before the first backward)."""
     seen, todo = set(), [t.grad_fn]
@@ -198,11 +325,16 @@ def adjoint_status(t: torch.Tensor) -> Optional[torch.Tensor]:
 
 
 def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons_var=None, cons_a=None, cons_b=None,
-             params: Optional[Params] = None, return_all: bool = False, return_status: bool = False):
+             params: Optional[Params] = None, return_all: bool = False, return_status: bool = False, layout: Optional[ResidualLayout] = None,
+             J_blocks=None, eq_layout: Optional[ResidualLayout] = None, J_eq_blocks=None, r_eq=None):
     """Solve a batch of QPs   min 1/2 x^T G x + c^T x   s.t.  A_eq x + b_eq = 0,  cons_a[i] x[cons_var[i]] + cons_b[i] >= 0   on the GPU and
     keep the result on the autograd graph.  Give EITHER (G [B, n, n] SYMMETRIC, c [B, n]) OR the least-squares form (J [B, m_r, n], r [B, m_r],
     lam: float or [B] tensor; G = J^T J + lam I, c = J^T r, lam added where > 0).  A_eq [B, k, n] (rows = constraints), b_eq [B, k];
     cons_var int32 [B, m] (never differentiable), cons_a, cons_b [B, m]; a leading dimension of 1 is broadcast over the batch.
+    OR the residual-block form (the reference's own cost model): layout = a qp.ResidualLayout, J_blocks [B, layout.values] the packed local
+    Jacobians, r [B, layout.rows], lam as above; equalities, if any, as eq_layout, J_eq_blocks [B, eq_layout.values], r_eq [B, k] (A_eq = the
+    stacked UpdateJacobian, b_eq = r_eq) instead of A_eq / b_eq.  Its gradients arrive in the packed layouts and are computed from the
+    blocks alone (QPSolveBlocksFunction).  The three forms are mutually exclusive.
     Returns x [B, n] (return_all: x, s, y, z), and with return_status also the [B] int32 forward status (MO_STATUS_*).
 
     Gradients: every floating-point input that requires_grad receives one, nothing else is computed.  G's gradient is the one with respect
@@ -211,6 +343,10 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     at the returned point: it is as accurate as the solve (termination_kkt_tol), and at an active inequality the slack sits at the
     interior-point floor, so K is ill-conditioned there by construction."""
     params = params if params is not None else Params()
+    if layout is not None or J_blocks is not None or eq_layout is not None or J_eq_blocks is not None or r_eq is not None:
+        if G is not None or c is not None or J is not None or A_eq is not None or b_eq is not None:
+            raise ValueError("layout= (residual-block input) excludes G, c, J, A_eq and b_eq: the three input forms are mutually exclusive")
+        return _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status)
     if (J is None) == (G is None):
         raise ValueError("give either (G, c) or (J, r)")
     ref = J if J is not None else G
@@ -239,6 +375,34 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     m = 0 if cons_a is None else int(cons_a.shape[1])
     x = v[:, :n]
     res = (x, v[:, n:n + m], v[:, n + m:n + m + k], v[:, n + m + k:]) if return_all else (x,)
+    if return_status:
+        res = res + (status,)
+    return res[0] if len(res) == 1 else res
+
+
+def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status):
+    if layout is None or J_blocks is None or r is None:
+        raise ValueError("the residual-block form needs layout, J_blocks and r")
+    if (eq_layout is None) != (J_eq_blocks is None) or (eq_layout is None) != (r_eq is None):
+        raise ValueError("eq_layout, J_eq_blocks and r_eq come together")
+    if eq_layout is not None and (eq_layout.n != layout.n or eq_layout.dtype != layout.dtype or eq_layout.device != layout.device):
+        raise ValueError("eq_layout must share n, dtype and device with layout")
+    if (cons_var is None) != (cons_a is None) or (cons_a is None) != (cons_b is None):
+        raise ValueError("cons_var, cons_a and cons_b come together")
+    if cons_var is not None and cons_var.dtype != torch.int32:
+        raise ValueError("cons_var must be int32")
+    tensors = [t for t in (J_blocks, r, J_eq_blocks, r_eq, cons_a, cons_b) if t is not None]
+    if isinstance(lam, torch.Tensor):
+        lam = lam.reshape(-1)
+        tensors.append(lam)
+    B = max(int(t.shape[0]) for t in tensors)
+    full = lambda t: None if t is None else (t.expand(B, *t.shape[1:]) if t.shape[0] != B else t).contiguous()
+    lam_t = full(lam) if isinstance(lam, torch.Tensor) else torch.full((B,), float(lam), dtype=layout.dtype, device=layout.device)
+    v, status = QPSolveBlocksFunction.apply(full(J_blocks), full(r), lam_t, full(J_eq_blocks), full(r_eq), full(cons_a), full(cons_b),
+                                            full(cons_var), layout, eq_layout, params)
+    n, k = layout.n, 0 if eq_layout is None else eq_layout.rows
+    m = 0 if cons_a is None else int(cons_a.shape[1])
+    res = (v[:, :n], v[:, n:n + m], v[:, n + m:n + m + k], v[:, n + m + k:]) if return_all else (v[:, :n],)
     if return_status:
         res = res + (status,)
     return res[0] if len(res) == 1 else res

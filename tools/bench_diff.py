@@ -9,7 +9,13 @@ yardsticks of mo_kkt_solve: mo_newton_step on the plan's own kernel and on the g
 mo_kkt_solve does strictly less than the Newton step of the same kernel family (no residual, no alpha) and reads one more V-vector:
 kkt_over_step (generic pair) and kkt_over_fused_step (the plan's own pair) are expected at or below 1.1.  backward = the transposed solve +
 the gradient launch of the input level; backward_over_forward is that over the ten-iteration forward Solve.  mo_qp_gradients is data movement: achieved bytes/s against its algorithmic bytes (the vectors and matrices it must
-read and write once)."""
+read and write once).
+
+  blocksA  n = 64, 96 residual blocks of 2 x 4        blocksC  n = 128, 200 residual blocks of 3 x 6        
+Residual-block input: mo_qp_gradients_blocks (dJ_blocks + dr + dlambda) against its yardstick in the same run, mo_qp_gradients (dJ + dr +
+dlambda) on the dense scattered stack of the same problems; the forward mo_linearize_blocks; solve_qp(layout=...) forward and backward as
+the user calls them (autograd and Python included).  The block launch moves 2 (values + rows) + 2 n elements per problem, the dense one
+2 m_r n."""
 import argparse
 import ctypes as C
 import json
@@ -20,10 +26,12 @@ import torch
 
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 from mini_opt_amd import _lib as L  # noqa: E402
+from mini_opt_amd import diff as D  # noqa: E402
 from mini_opt_amd import qp as Q  # noqa: E402
 from mini_opt_amd import synth  # noqa: E402
 
 SHAPES = {"cfg3": (64, 8, 32, 128), "ref8": (8, 2, 4, 16), "n128": (128, 14, 64, 256)}
+BLOCK_SHAPES = {"blocksA": (64, 96, 2, 4), "blocksC": (128, 200, 3, 6)}   # n, blocks, R, P
 HBM = 8.0e12
 
 
@@ -136,6 +144,81 @@ def run(shape, dtype, batch, reps, warmup, rounds):
     return res
 
 
+def run_blocks(shape, dtype, batch, reps, warmup, rounds):
+    import numpy as np
+    n, count, R, Pn = BLOCK_SHAPES[shape]
+    dev = torch.device("cuda:0")
+    elem = 8 if dtype == torch.float64 else 4
+    rng = np.random.default_rng(47)
+    blocks = [(tuple(int(i) for i in rng.permutation(n)[:Pn]), R) for _ in range(count)]      # distinct variables: the dense stack can express it
+    lay = Q.ResidualLayout(n, blocks, dtype=dtype)
+    values, rows = lay.values, lay.rows
+    gen = torch.Generator(device=dev).manual_seed(48)
+    Jb = torch.rand(batch, values, dtype=dtype, device=dev, generator=gen) * 2 - 1
+    r = torch.rand(batch, rows, dtype=dtype, device=dev, generator=gen) * 2 - 1
+    v = torch.randn(batch, n, dtype=dtype, device=dev, generator=gen)
+    u = torch.randn(batch, n, dtype=dtype, device=dev, generator=gen)
+    Jd = torch.zeros(batch, rows, n, dtype=dtype, device=dev)
+    for b, (idx, _) in enumerate(blocks):
+        Jd[:, b * R:(b + 1) * R, list(idx)] = Jb[:, b * R * Pn:(b + 1) * R * Pn].reshape(batch, Pn, R).transpose(1, 2)
+    lib = L.lib()
+    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    s = Q._stream()
+    plan_g = D._plan_of(n, 0, 0, 0, dtype, dev, batch)                 # the plan of the (G, c) solve: what the block gradients run on
+    dense = Q.BatchedQP(n=n, J=Jd, r=r, lam=0.1)
+    plan_d = D.plan_for(dense, batch)
+    pd = dense.as_struct()
+    dJb, dr, dlam = torch.empty_like(Jb), torch.empty_like(r), torch.empty(batch, dtype=dtype, device=dev)
+    dJd = torch.empty_like(Jd)
+    gb = L.BlockGrads()
+    gb.dJ_blocks, gb.dJ_stride, gb.dr, gb.dr_stride, gb.dlambda, gb.dlambda_stride = dJb.data_ptr(), values, dr.data_ptr(), rows, dlam.data_ptr(), 1
+    gd = L.QPGrads()
+    gd.dJ, gd.dJ_stride, gd.dJ_ld, gd.dJ_layout = dJd.data_ptr(), rows * n, n, L.MO_ROW_MAJOR
+    gd.dr, gd.dr_stride, gd.dlambda, gd.dlambda_stride = dr.data_ptr(), rows, dlam.data_ptr(), 1
+    prm = Q.Params(max_iterations=10)
+    Jb_leaf, r_leaf = Jb.clone().requires_grad_(True), r.clone().requires_grad_(True)
+    gx = torch.randn(batch, n, dtype=dtype, device=dev, generator=gen)
+    graph = {}
+
+    def forward():
+        graph["x"], graph["status"] = D.solve_qp(layout=lay, J_blocks=Jb_leaf, r=r_leaf, lam=0.1, params=prm, return_status=True)
+
+    def backward():
+        Jb_leaf.grad = r_leaf.grad = None
+        graph["x"].backward(gx, retain_graph=True)
+
+    calls = {
+        "gradients_blocks": lambda: L.check(lib.mo_qp_gradients_blocks(plan_g, lay.h, P(Jb), values, P(r), rows, batch, P(v), n, P(u), n, C.byref(gb), s)),
+        "gradients_J_dense": lambda: L.check(lib.mo_qp_gradients(plan_d, C.byref(pd), batch, P(v), n, P(u), n, C.byref(gd), s)),
+        "linearize_blocks": lambda: Q.linearize_blocks(lay, Jb, r, lam=0.1),
+        "solve_qp_blocks_forward": forward,
+        "solve_qp_blocks_backward": backward,
+    }
+    for fn in calls.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    best = {key: float("inf") for key in calls}
+    for _ in range(rounds):  # alternating rounds, best of
+        for key, fn in calls.items():
+            best[key] = min(best[key], timed(fn, reps if not key.startswith("solve_qp") else max(1, reps // 4)))
+    x = graph["x"]
+    qg = Q.BatchedQP(n=n, G=torch.empty(1, n, n, dtype=dtype, device=dev), c=torch.empty(1, n, dtype=dtype, device=dev))
+    res = {"shape": shape, "n": n, "blocks": count, "R": R, "P": Pn, "values": values, "rows": rows, "dtype": str(dtype).split(".")[-1],
+           "batch": batch, "kkt_solve_kernel": D.kkt_solve_kernel(qg, batch),
+           "forward_status_ok": bool(torch.all(graph["status"] == 0)),
+           "adjoint_status_ok": bool(torch.all(D.adjoint_status(x) == 0))}
+    res.update({key + "_s": t for key, t in best.items()})
+    res["blocks_over_dense"] = best["gradients_blocks"] / best["gradients_J_dense"]
+    res["backward_over_forward"] = best["solve_qp_blocks_backward"] / best["solve_qp_blocks_forward"]
+    algo = {"gradients_blocks": elem * (2 * (values + rows) + 2 * n + 1), "gradients_J_dense": elem * (2 * rows * n + 2 * rows + 2 * n + 1)}
+    for key, b in algo.items():
+        res[key + "_bytes_per_problem"] = b
+        res[key + "_TBps"] = b * batch / best[key] / 1e12
+        res[key + "_frac_8TBps"] = b * batch / best[key] / HBM
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="cfg3,ref8")
@@ -149,7 +232,7 @@ def main():
     L.build()
     lines = []
     for sh in a.shapes.split(","):
-        res = run(sh, torch.float64 if a.dtype == "f64" else torch.float32, a.batch, a.reps, a.warmup, a.rounds)
+        res = (run_blocks if sh in BLOCK_SHAPES else run)(sh, torch.float64 if a.dtype == "f64" else torch.float32, a.batch, a.reps, a.warmup, a.rounds)
         print(json.dumps(res), flush=True)
         lines.append(res)
         torch.cuda.empty_cache()

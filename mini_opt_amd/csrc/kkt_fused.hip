@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "mo_fused_device.h"
+#include "mo_fused_diag.h"
 #include "mo_fused_select.h"
 
 namespace mo {
@@ -385,9 +386,15 @@ __device__ inline bool sweep_tile(d4& T, int npiv, int g, int j) {
 // fetches its own operands J(4s+g, col) as two dwords each through per-lane LDS-DMA addresses (wave-uniform part of the address on the
 // scalar unit: base + column part; one VGPR holds the lane part g * row_stride + 2j * column_stride).  2 NT + 1 DMAs per group, operand c
 // at dwords [2c][lane] and [2c+1][lane] of the slot.  The memory system sees 4-byte pieces: this is the flexible path, not the fast one.
-template <int NT, int D, int JMODE = JMODE_VECTOR, int NY = 1, bool ROW0 = true>
+// DIAG4 (16-byte stream, 64 grid, one y tile): the four diagonal tiles G(c, c) on v_mfma_f64_4x4x4_4b_f64, lower 4x4 sub-blocks only --
+// five block instructions per tile pair and group instead of two 16x16x4 ones (80 instead of 128 matrix-pipe cycles).  The block
+// instruction wants the four rows of a group on different lanes of ONE LDS read; rows sit 256 bytes apart in the slot (the same banks),
+// so lane (g, j) fetches piece j ^ 4 X[g] instead of piece j (mo_fused_diag.h): free for the DMA, and both the lane's own 16-byte read
+// and the block operands' 8-byte reads stay conflict-free.  The ten accumulators become the four tiles in diag_tiles().
+template <int NT, int D, int JMODE = JMODE_VECTOR, int NY = 1, bool ROW0 = true, bool DIAG4 = false>
 struct JStream {
   static constexpr bool FLAT = JMODE == JMODE_FLAT, GATHER = JMODE == JMODE_GATHER;
+  static_assert(!DIAG4 || (JMODE == JMODE_VECTOR && NY == 1 && NT == 4), "DIAG4: the 16-byte stream of the 64 grid with one y tile");
   static constexpr int N = 16 * NT, NB = NT + NY, NH = NT / 2, NI = GATHER ? 2 * NT : (FLAT ? N / 8 : NH), DPS = NI + 1, SLOT = NH * 1024 + 64;
   static_assert((D - 1) * DPS <= 63, "vmcnt is a 6-bit counter");
   static_assert(D >= 2 && D <= 8, "ring depth");
@@ -399,6 +406,8 @@ struct JStream {
   bool act0, act1, act2, act3;  // does this lane's piece h lie inside the row (nn < N pads the system; the ring is zeroed once)
   const char* lane_piece;
   const char* r_elem;
+  const char* dop[DIAG4 ? diag4::kNumVec : 1];       // DIAG4: this lane's 8 bytes of operand vector Va .. Ve inside tile pair 0 of slot 0
+  double dacc[DIAG4 ? NT / 2 : 1][diag4::kNumIns];   // DIAG4: the block accumulators of tile pair h
   unsigned ring_base;
   int lane, nsteps;
   long long rs_, cs_;  // GATHER: row / column stride of J in bytes (wave-uniform)
@@ -415,6 +424,12 @@ struct JStream {
     act0 = 2 * j < nn; act1 = 32 + 2 * j < nn; act2 = 64 + 2 * j < nn; act3 = 96 + 2 * j < nn;
     roff = 4u * (unsigned)lane_;                             // lanes 0..7 fetch the eight dwords of r[4s .. 4s+3] (no 16-byte alignment)
     lane_piece = smem + lane_ * 16;                          // this lane's 16 bytes inside a 1 KiB DMA piece
+    if (DIAG4) {                                             // lane (g, j) fetches piece j ^ 4 X[g] and reads piece j back from where it landed
+      const int jp = diag4::swz(g, j);
+      joff = (unsigned)(g * nn + 2 * jp) * 8u;
+      act0 = 2 * jp < nn; act1 = 32 + 2 * jp < nn; act2 = 64 + 2 * jp < nn; act3 = 96 + 2 * jp < nn;
+      lane_piece = smem + diag4::natural_off(lane_);
+    }
     r_elem = smem + NH * 1024 + 8 * g;                       // r[4s + g] inside a slot
     ring_base = ring_base_; lane = lane_; nsteps = m_r >> 2;
     rem = m_r & 3; row_len = nn; g_ = g; j_ = j;
@@ -486,6 +501,7 @@ struct JStream {
   double rsq;  // sum of r[4s + g]^2 seen by this lane (accumulated only by run<true>: the standalone linearisation wants 0.5 |r|^2)
   template <int SL, bool RSQ = false> __device__ inline void consume(int q, d4 (&U)[NB * NB], double (&cpart)[NT]) {  // group q sits in slot SL
     wait_for_oldest(nsteps - 1 - q);
+    if constexpr (DIAG4) diag_products(SL * SLOT);  // first: their operands are dead before the lane's own pieces are read (no registers for both)
     double ops[NT];
     if (GATHER) {
       const int* src = reinterpret_cast<const int*>(lane_piece - lane * 16 + SL * SLOT) + lane;
@@ -514,7 +530,48 @@ struct JStream {
     for (int ta = 0; ta < NT; ++ta) {
       cpart[ta] = fma(ops[ta], rq, cpart[ta]);
 #pragma unroll
-      for (int tb = ta; tb < NT; ++tb) jtj_mfma(U[ta * NB + tb], ops[ta], ops[tb], ta);
+      for (int tb = DIAG4 ? ta + 1 : ta; tb < NT; ++tb) jtj_mfma(U[ta * NB + tb], ops[ta], ops[tb], ta);
+    }
+  }
+  // DIAG4: the block products of the group in the slot at byte `off` of the ring, one tile pair at a time (five operand vectors, five
+  // instructions; the second pair's reads wait for the first pair's products: ten operand registers instead of twenty)
+  __device__ inline void diag_products(int off) {
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      double dv[diag4::kNumVec];
+#pragma unroll
+      for (int v = 0; v < diag4::kNumVec; ++v) dv[v] = *(const double*)(dop[v] + off + h * 1024);
+#pragma unroll
+      for (int i = 0; i < diag4::kNumIns; ++i)
+        dacc[h][i] = __builtin_amdgcn_mfma_f64_4x4x4f64(dv[diag4::kInsA[i]], dv[diag4::kInsB[i]], dacc[h][i], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  // DIAG4, after run(): the ten accumulators -> the four diagonal tiles in the 16x16x4 C/D layout, both triangles, through the drained ring
+  // (row-major tiles; every lane stores its element of each lower sub-block and the mirror image of the off-diagonal ones, then reads the
+  // 512 consecutive bytes of each of its registers).  rezero (wave-uniform, nn < N): the ring's never-fetched pieces must read zero again.
+  __device__ inline void diag_tiles(d4 (&U)[NB * NB], char* ring, bool rezero) {
+    static_assert(!DIAG4 || D * SLOT >= diag4::kStageBytes, "the ring holds the four staged tiles");
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int c = 2 * h + diag4::acc_tile(lane);
+#pragma unroll
+      for (int i = 0; i < diag4::kNumIns; ++i) {
+        const int row = diag4::acc_row(i, lane), col = diag4::acc_col(i, lane);
+        *(double*)(ring + diag4::stage_off(c, row, col)) = dacc[h][i];
+        if (!diag4::ins_diagonal(i)) *(double*)(ring + diag4::stage_off(c, col, row)) = dacc[h][i];
+      }
+    }
+    lds_fence();
+#pragma unroll
+    for (int c = 0; c < NT; ++c)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) U[c * NB + c][t] = *(const double*)(ring + diag4::stage_off(c, 4 * t + (lane >> 4), lane & 15));
+    lds_fence();
+    if (rezero) {
+#pragma unroll
+      for (int i = 0; i < diag4::kStageBytes / 512; ++i) *(double*)(ring + i * 512 + lane * 8) = 0.0;
+      lds_fence();
     }
   }
   // One J^T J MFMA.  On the 128 grid the 36 accumulator tiles (288 registers) exceed the 256 AGPRs, and with one wave per SIMD hipcc selects
@@ -544,6 +601,15 @@ struct JStream {
   template <bool RSQ = false>
   __device__ inline void run(d4 (&U)[NB * NB], double (&cpart)[NT]) {  // G tiles += J^T J, cpart += J^T r partials
     if (RSQ) rsq = 0.0;
+    if (DIAG4) {  // (the operand addresses are made here, not in init(): nothing of them is live while P0 issues its loads)
+#pragma unroll
+      for (int h = 0; h < NH; ++h)
+#pragma unroll
+        for (int i = 0; i < diag4::kNumIns; ++i) dacc[h][i] = 0.0;
+      const char* slot0 = lane_piece - diag4::natural_off(lane);   // tile pair 0 of slot 0
+#pragma unroll
+      for (int v = 0; v < diag4::kNumVec; ++v) dop[v] = slot0 + diag4::operand_off(v, lane);
+    }
     for (int q0 = 0; q0 < nsteps; q0 += D) {
 #define MO_CONSUME(u) if (u < D && q0 + u < nsteps) consume<(u < D ? u : 0), RSQ>(q0 + u, U, cpart);
       MO_FOR_SLOTS(MO_CONSUME)
@@ -573,11 +639,17 @@ struct JStream {
         rq = tail_r[g_];
       }
       if (RSQ) rsq = fma(rq, rq, rsq);
+      if constexpr (DIAG4) {  // the leftover rows go through slot 0 (drained: every DMA has landed and been read) at their swizzled places, zeros for the missing rows
+#pragma unroll
+        for (int h = 0; h < NH; ++h) *(d2*)const_cast<char*>(lane_piece + h * 1024) = d2{ops[2 * h], ops[2 * h + 1]};
+        lds_fence();
+        diag_products(0);
+      }
 #pragma unroll
       for (int ta = 0; ta < NT; ++ta) {
         cpart[ta] = fma(ops[ta], rq, cpart[ta]);
 #pragma unroll
-        for (int tb = ta; tb < NT; ++tb) jtj_mfma(U[ta * NB + tb], ops[ta], ops[tb], ta);
+        for (int tb = DIAG4 ? ta + 1 : ta; tb < NT; ++tb) jtj_mfma(U[ta * NB + tb], ops[ta], ops[tb], ta);
       }
     }
     finish();
@@ -895,6 +967,12 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
   const int k = a.k, m = no_ineq ? 0 : a.m, m_r = a.m_r;
   const int nn = a.n;  // actual number of variables <= N; the system is padded to whole tiles (unit diagonal, zero solution)
   const bool transpose = RHS && (a.flags & MO_KKT_TRANSPOSE) != 0;
+  constexpr bool DIAG4 = !RHS && !QPL && NT == 4 && NY == 1 && MC == 1 && JMODE == JMODE_VECTOR;   // the headline step kernel: diagonal tiles on block MFMAs
+  if constexpr (DIAG4) {  // what fused_supported() guarantees, said to the compiler: the wave-uniform "more than 64 / 128 elements" tests of the P0 loads
+    __builtin_assume(m <= MCAP);   // fold away instead of sitting in registers for the whole kernel (this kernel has none to spare)
+    __builtin_assume(nn <= N);
+    __builtin_assume(k <= 15);
+  }
   // Once per wave: the ring (lanes whose J piece lies beyond the row never receive DMA data and must read zeros) and x's padding.
   for (int i = (int)(threadIdx.x & 63); i < D * SLOT / 8; i += 64) reinterpret_cast<double*>(smem)[i] = 0.0;
   for (int i = (int)(threadIdx.x & 63); i < N; i += 64) xs[i] = 0.0;
@@ -944,7 +1022,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
     const double* gp = RHS ? (const double*)ka->rhs + p * ka->rhs_stride : nullptr;   // rho (or g), laid out as the state
 
     // The ring is filled FIRST: the J stream's memory latency then overlaps the address arithmetic and the small loads of P0.
-    JStream<NT, D, JMODE, NY> stream;
+    JStream<NT, D, JMODE, NY, true, DIAG4> stream;
     if (!QPL) {
       stream.init(Jp, rg, smem, ring_base, lane, g, j, m_r, nn, a.J_row_major ? (long long)a.J_ld : 1ll, a.J_row_major ? 1ll : (long long)a.J_ld);
       stream.prologue();
@@ -997,6 +1075,7 @@ __global__ __launch_bounds__(256 * WPS, WPS) void kkt_fused_f64_kernel(const Ker
       MO_STAMP(7);
 #endif
       stream.run(U, cpart);
+      if constexpr (DIAG4) stream.diag_tiles(U, smem, nn < N);
 #pragma unroll
       for (int c = 0; c < NT; ++c) cvec[c] = cross_row_sum(cpart[c]);
     }

@@ -1,4 +1,4 @@
-// microbench.hip -- gfx950 facts the fused kernel relies on: f64 MFMA fragment maps, MFMA f64 issue rate,
+// microbench.hip -- gfx950 facts the fused kernel relies on: f64 MFMA fragment maps (16x16x4 and the 4x4x4 block form), MFMA f64 issue rate,
 // DPP row_newbcast semantics, v_rcp_f64 + one Newton step accuracy.  Build: hipcc --offload-arch=gfx950 -O3.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -14,6 +14,47 @@ __global__ void mfma_layout(const double* A, const double* B, double* D) {
   // A is 16x4 row-major [i][k], B is 4x16 row-major [k][j]
   acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(l & 15) * 4 + (l >> 4)], B[(l >> 4) * 16 + (l & 15)], acc, 0, 0, 0);
   for (int r = 0; r < 4; ++r) D[((l >> 4) + 4 * r) * 16 + (l & 15)] = acc[r];
+}
+
+// v_mfma_f64_4x4x4_4b_f64: four independent 4x4x4 products per instruction, one f64 of A, B and D per lane.
+__global__ void mfma4_layout(const double* a, const double* b, double* d) {
+  const int l = threadIdx.x;
+  d[l] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[l], b[l], 0.0, 0, 0, 0);
+}
+
+// NACC accumulators round-robin; LDS: one conflict-free ds_read_b64 (lane-linear 8-byte words) per MFMA, read one
+// half-iteration ahead as a kernel would (row stride 264 doubles: no ds_read2 form fits, the reads stay single).
+template <int NACC, bool LDS>
+__global__ void mfma4_rate(double* out, int iters, long long* cycles) {
+  constexpr int RS = 264;
+  __shared__ double ring[2 * NACC * RS];
+  for (int i = threadIdx.x; i < 2 * NACC * RS; i += blockDim.x) ring[i] = 1e-3 * i;
+  __syncthreads();
+  double acc[NACC], a0[NACC], a1[NACC];
+  const double a = threadIdx.x * 1e-3, b = 1.0 + threadIdx.x * 1e-4;
+  for (int i = 0; i < NACC; ++i) { acc[i] = 0.0; a0[i] = LDS ? ring[i * RS + threadIdx.x] : a; a1[i] = a; }
+  long long t0 = __builtin_amdgcn_s_memtime();
+  for (int it = 0; it < iters; it += 2) {
+    if (LDS) {
+      asm volatile("" ::: "memory");  // the reads stay in the loop
+#pragma unroll
+      for (int i = 0; i < NACC; ++i) a1[i] = ring[(NACC + i) * RS + threadIdx.x];
+    }
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(a0[i], b, acc[i], 0, 0, 0);
+    if (LDS) {
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int i = 0; i < NACC; ++i) a0[i] = ring[i * RS + threadIdx.x];
+    }
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(a1[i], b, acc[i], 0, 0, 0);
+  }
+  long long t1 = __builtin_amdgcn_s_memtime();
+  double s = 0;
+  for (int i = 0; i < NACC; ++i) s += acc[i];
+  out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+  if (threadIdx.x == 0 && blockIdx.x == 0) *cycles = t1 - t0;
 }
 
 template <int NACC>
@@ -91,6 +132,35 @@ int main() {
   CK(hipMemcpy(D.data(), dD, 2048, hipMemcpyDeviceToHost));
   double err = 0; for (int i = 0; i < 256; ++i) err = fmax(err, fabs(D[i] - ref[i]));
   printf("mfma_f64_16x16x4 layout check: max err %.3e (%s)\n", err, err < 1e-14 ? "OK" : "MISMATCH");
+
+  {  // 4x4x4 block form: which 2-bit lane field is the block, which k, which i / j?  Assumed: block = lane >> 4,
+     // A(i,k) at 16 blk + 4k + i, B(k,j) at 16 blk + 4k + j, D(i,j) at 16 blk + 4i + j.  All 6^3 assignments are tried.
+    std::vector<double> a4(64), b4(64), d4o(64);
+    for (int l = 0; l < 64; ++l) { a4[l] = sin(2.0 + l * 0.53); b4[l] = cos(0.3 + l * 0.77); }
+    CK(hipMemcpy(dA, a4.data(), 512, hipMemcpyHostToDevice)); CK(hipMemcpy(dB, b4.data(), 512, hipMemcpyHostToDevice));
+    mfma4_layout<<<1, 64>>>(dA, dB, dD);
+    CK(hipMemcpy(d4o.data(), dD, 512, hipMemcpyDeviceToHost));
+    static const int perm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    // perm[p] = bit positions (in units of 2 bits) of (inner, middle, block): lane = x0 << 2 perm[0] | x1 << 2 perm[1] | x2 << 2 perm[2]
+    auto lane = [&](int p, int x0, int x1, int x2) { return (x0 << (2 * perm[p][0])) | (x1 << (2 * perm[p][1])) | (x2 << (2 * perm[p][2])); };
+    int found = 0; bool assumed = false;
+    for (int pa = 0; pa < 6; ++pa) for (int pb = 0; pb < 6; ++pb) for (int pd = 0; pd < 6; ++pd) {
+      double e = 0;  // A: (i, k, blk), B: (j, k, blk), D: (j, i, blk)
+      for (int blk = 0; blk < 4; ++blk) for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) {
+        double s = 0; for (int k = 0; k < 4; ++k) s = fma(a4[lane(pa, i, k, blk)], b4[lane(pb, j, k, blk)], s);
+        e = fmax(e, fabs(d4o[lane(pd, j, i, blk)] - s));
+      }
+      if (e < 1e-14) {
+        ++found; if (pa == 0 && pb == 0 && pd == 0) assumed = true;
+        auto nm = [&](int p, const char* n0, const char* n1, char* buf) { const char* f[3]; f[perm[p][0]] = n0; f[perm[p][1]] = n1; f[perm[p][2]] = "blk";
+                                                                           sprintf(buf, "lane = %s + 4 %s + 16 %s", f[0], f[1], f[2]); };
+        char sa[64], sb[64], sd[64]; nm(pa, "i", "k", sa); nm(pb, "j", "k", sb); nm(pd, "j", "i", sd);
+        printf("mfma_f64_4x4x4_4b layout match: A(i,k): %s | B(k,j): %s | D(i,j): %s (max err %.1e)\n", sa, sb, sd, e);
+      }
+    }
+    printf("mfma_f64_4x4x4_4b layout check: %d of 216 lane-field assignments match; assumed layout (block = lane >> 4) %s\n", found,
+           assumed ? "OK" : "MISMATCH");
+  }
   long long cyc; const int iters = 2000;
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   auto run = [&](auto kern, int nacc, int blocks, int threads, const char* name) {
@@ -105,6 +175,14 @@ int main() {
   run(mfma_rate<10>, 10, 1, 64, "mfma f64 10 acc 1 wave");
   run(mfma_rate<10>, 10, 1024, 256, "mfma f64 10 acc 1w/SIMD all");
   run(mfma_rate<10>, 10, 2048, 256, "mfma f64 10 acc 2w/SIMD all");
+  // the 4x4x4 block form beside the 16x16x4 one under the same loop (64 cycles = the 16x16x4 figure: scale by the wall ratio)
+  run(mfma_rate<5>, 5, 1, 64, "mfma f64 16x16x4 5 acc 1 wave");
+  run(mfma4_rate<1, false>, 1, 1, 64, "mfma f64 4x4x4_4b dep chain");
+  run(mfma4_rate<5, false>, 5, 1, 64, "mfma f64 4x4x4_4b 5 acc 1 wave");
+  run(mfma4_rate<5, true>, 5, 1, 64, "  + ds_read_b64 each, 1 wave");
+  run(mfma_rate<5>, 5, 256, 256, "mfma f64 16x16x4 5 acc 1w/SIMD");
+  run(mfma4_rate<5, false>, 5, 256, 256, "mfma f64 4x4x4_4b 5 acc 1w/SIMD");
+  run(mfma4_rate<5, true>, 5, 256, 256, "  + ds_read_b64 each, 1w/SIMD");
   run(fma_rate, 8, 1, 64, "v_fma_f64 8 acc 1 wave");
   run(fma_rate, 8, 1024, 256, "v_fma_f64 8 acc 1w/SIMD all");
   std::vector<double> x(64), o(128), rq(64);

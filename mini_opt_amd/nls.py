@@ -452,7 +452,7 @@ def qp_cost_derivative(problem: BatchedQP, dx: torch.Tensor):
     out = torch.empty(B, 2, dtype=ref.dtype, device=ref.device)
     quad = torch.empty(B, dtype=ref.dtype, device=ref.device)
     q = BatchedQP(n=n, k=problem.k, J=problem.J, r=problem.r, lam=problem.lam, lam_vec=problem.lam_vec, G=problem.G, c=problem.c,
-                  A_eq=problem.A_eq, b_eq=problem.b_eq)
+                  A_eq=problem.A_eq, b_eq=problem.b_eq, J_layout=problem.J_layout, J_rows=problem.J_rows)
     prob = q.as_struct()
     L.check(L.lib().mo_qp_cost_derivative(plan.h, C.byref(prob), B, _ptr(dx), n, _ptr(out), _ptr(quad), _stream()))
     return out, quad

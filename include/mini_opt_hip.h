@@ -38,7 +38,7 @@ extern "C" {
 #endif
 
 #define MO_VERSION_MAJOR 0
-#define MO_VERSION_MINOR 3
+#define MO_VERSION_MINOR 4
 
 /* return codes */
 #define MO_OK 0
@@ -491,6 +491,43 @@ int mo_qp_gradients_blocks(mo_plan* plan, const mo_residual_layout* cost_layout,
 int mo_qp_gradients_eq_blocks(mo_plan* plan, const mo_residual_layout* eq_layout, int64_t batch, const void* vars, int64_t vars_stride,
                               const void* u, int64_t u_stride, void* dJ_eq_blocks, int64_t dJ_eq_stride, void* dr_eq,
                               int64_t dr_eq_stride, void* stream);
+
+/* Forward mode: the directional derivative vdot = (dv* / dtheta) thetadot of the root of F(v; theta) = 0 along a direction thetadot in the
+ * problem's data.  From F(v*(theta); theta) = 0 follows K vdot = -rho with rho = F_theta thetadot; the call below forms rho at the state
+ * `vars` from the tangents (a NULL member is a zero tangent):
+ *   (G, c) input:   rho_d = sym(dG) x + dc - dA_eq^T y - sum_i dcons_a[i] z_i e_{var_i}
+ *   (J, r, lambda): rho_d = dJ^T w + J^T tdot + dlambda x - dA_eq^T y - sum_i dcons_a[i] z_i e_{var_i},   w = J x + r,  tdot = dJ x + dr
+ *   rho_comp = 0       rho_pe = dA_eq x + db_eq       rho_pi[i] = dcons_a[i] x[var_i] + dcons_b[i]   (NaN for a var_i outside [0, n))
+ * sym(dG) is the symmetric matrix whose lower triangle is that of dG: dG is read as G is read, lower triangle only; its strict upper
+ * triangle and the padding beyond any matrix (ld > rows) are never read into the result and may hold anything.  dlambda counts
+ * unconditionally, as the dlambda of mo_qp_gradients does.
+ * The two-call recipe:   mo_qp_tangent_rhs(..., t, rho, ...);   mo_kkt_solve(..., rhs = rho, flags = 0, out = vdot, ...).
+ * The map thetadot -> rho is the exact transpose of mo_qp_gradients' map u -> gradients (up to the sign of K delta = -rhs): for every g,
+ *   g . vdot = sum over the members of < gradient of the member from u = K^-T g,  tangent of the member >,
+ * with dG's tangent taken symmetric (a caller with an arbitrary Gdot passes 1/2 (Gdot + Gdot^T)).
+ * Layouts as the inputs: dG n x n and dA_eq k x n column-major with a leading dimension; dJ m_r x n in prob->J_layout with its OWN leading
+ * dimension and stride; strides per problem, in elements, 0 = one direction shared by the batch.  Only prob->J / r (for dJ, dr) and
+ * prob->cons_var are read from the problem; with k = 0 the equality members and with m = 0 the inequality members are ignored.
+ * rho: [batch][V], all V values written (rho_comp as zeros), nothing beyond V.
+ * MO_ERR_INVALID_ARGUMENT (judged before the plan is looked at): NULL prob / t / vars / rho; dG with J-level input; dJ / dr / dlambda
+ * with (G, c) input; dJ without prob->r; dcons_a without prob->cons_var.  MO_ERR_DIMENSION: dG_ld < n, dA_ld < k, dJ_ld below the layout's
+ * minimum.  MO_ERR_UNSUPPORTED if the vectors the kernel keeps in LDS -- (2 n + 2 k + m + 2 m_r) values, each block padded to 16 bytes,
+ * m 32-bit indices and 4 KiB of partial sums; m_r counts only with dJ or dr -- exceed 64 KiB.
+ * Pure data movement: one workgroup per problem in turn, every element of rho has one owner and a fixed order of operations (no atomics,
+ * also where several rows name one variable), so two launches give the same bits.  No allocation and no synchronisation on the launch
+ * path: one kernel. */
+typedef struct {                                   /* every member optional: NULL = zero tangent.  Strides per problem, in elements; 0 = one direction shared by the batch */
+  const void* dG;    int64_t dG_stride; int32_t dG_ld; int32_t reserved0;   /* n x n column-major, LOWER triangle read as a symmetric matrix */
+  const void* dc;    int64_t dc_stride;
+  const void* dA_eq; int64_t dA_stride; int32_t dA_ld; int32_t reserved1;   /* k x n column-major */
+  const void* db_eq; int64_t db_stride;
+  const void* dcons_a; const void* dcons_b; int64_t dcons_stride;
+  const void* dJ;    int64_t dJ_stride; int32_t dJ_ld; int32_t reserved2;   /* m_r x n in prob->J_layout */
+  const void* dr;    int64_t dr_stride;
+  const void* dlambda; int64_t dlambda_stride;
+} mo_qp_tangents;
+int mo_qp_tangent_rhs(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride,
+                      const mo_qp_tangents* t, void* rho, int64_t rho_stride, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,7 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_default_nls_params", "mo_nls_solve", "mo_nullspace_solve", "mo_residual_eval", "mo_qp_eigenvalue_stats",
            "mo_residual_layout_create", "mo_residual_layout_destroy", "mo_residual_layout_values", "mo_residual_layout_rows",
            "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks", "mo_kkt_solve", "mo_qp_gradients",
-           "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks"]
+           "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_tangent_rhs"]
 
 
 class PlanDesc(C.Structure):
@@ -98,6 +98,18 @@ class QPGrads(C.Structure):
                 ("dlambda", C.c_void_p), ("dlambda_stride", C.c_int64)]
 
 
+class QPTangents(C.Structure):
+    """mo_qp_tangents: optional device inputs of mo_qp_tangent_rhs (a NULL member is a zero tangent; stride 0 = shared by the batch)."""
+    _fields_ = [("dG", C.c_void_p), ("dG_stride", C.c_int64), ("dG_ld", C.c_int32), ("reserved0", C.c_int32),
+                ("dc", C.c_void_p), ("dc_stride", C.c_int64),
+                ("dA_eq", C.c_void_p), ("dA_stride", C.c_int64), ("dA_ld", C.c_int32), ("reserved1", C.c_int32),
+                ("db_eq", C.c_void_p), ("db_stride", C.c_int64),
+                ("dcons_a", C.c_void_p), ("dcons_b", C.c_void_p), ("dcons_stride", C.c_int64),
+                ("dJ", C.c_void_p), ("dJ_stride", C.c_int64), ("dJ_ld", C.c_int32), ("reserved2", C.c_int32),
+                ("dr", C.c_void_p), ("dr_stride", C.c_int64),
+                ("dlambda", C.c_void_p), ("dlambda_stride", C.c_int64)]
+
+
 class BlockGrads(C.Structure):
     """mo_block_grads: optional device outputs of mo_qp_gradients_blocks, in the packed layouts of the residual-block input."""
     _fields_ = [("dJ_blocks", C.c_void_p), ("dJ_stride", C.c_int64),
@@ -120,7 +132,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "tools", "isa_lint.py"))   # the build lints its own listings: a changed lint re-runs it
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
-        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (thirteen units, the longest 5.7 min)
+        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (fifteen units, the longest 5.7 min)
         subprocess.check_call(["make", "-C", CSRC, f"-j{jobs}"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
@@ -183,6 +195,7 @@ def lib() -> C.CDLL:
     L.mo_qp_gradients.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, C.POINTER(QPGrads), vp]
     L.mo_qp_gradients_blocks.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.POINTER(BlockGrads), vp]
     L.mo_qp_gradients_eq_blocks.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.mo_qp_tangent_rhs.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, C.POINTER(QPTangents), vp, i64, vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what the header declares
     _lib = L

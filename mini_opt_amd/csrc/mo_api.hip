@@ -206,7 +206,7 @@ struct NlsScratch {  // one allocation carved into 256-byte aligned pieces
 
 extern "C" {
 
-const char* mo_version_string(void) { return "mini_opt_hip 0.3 (gfx950)"; }
+const char* mo_version_string(void) { return "mini_opt_hip 0.4 (gfx950)"; }
 
 const char* mo_status_string(int32_t status) {
   switch (status) {
@@ -572,6 +572,50 @@ int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const 
   if (batch == 0) return MO_OK;
   MO_HIP_CHECK(hipSetDevice(d.device));
   MO_HIP_CHECK(mo::launch_qp_gradients(a, d.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+int mo_qp_tangent_rhs(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride,
+                      const mo_qp_tangents* t, void* rho, int64_t rho_stride, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (!prob) return fail(MO_ERR_INVALID_ARGUMENT, "Must pass a non-null problem");
+  if (!t) return fail(MO_ERR_INVALID_ARGUMENT, "t is NULL");
+  if (!vars || !rho) return fail(MO_ERR_INVALID_ARGUMENT, "vars / rho is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  const bool j_level = prob->J != nullptr;
+  if (j_level && t->dG) return fail(MO_ERR_INVALID_ARGUMENT, "dG given with J-level input: give dJ / dr / dlambda");
+  if (!j_level && (t->dJ || t->dr || t->dlambda))
+    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr / dlambda given with (G, c) input (prob->J is NULL): give dG / dc");
+  if (t->dJ && !prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "dJ given without prob->r");
+  if (t->dcons_a && !prob->cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a given but cons_var is NULL");
+  if (int rc = check_plan(plan)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  mo::TangentArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = d.n; a.k = d.k; a.m = d.m; a.batch = batch;
+  a.vars = vars; a.vars_stride = vars_stride; a.rho = rho; a.rho_stride = rho_stride;
+  a.t = *t;
+  if (d.k == 0) { a.t.dA_eq = nullptr; a.t.db_eq = nullptr; }
+  if (d.m == 0) { a.t.dcons_a = nullptr; a.t.dcons_b = nullptr; }
+  if (a.t.dJ || a.t.dr) {  // the only tangents that read J
+    if (d.m_r <= 0) return fail(MO_ERR_DIMENSION, "J given but the plan was created with m_r = 0");
+    if (prob->J_layout != MO_ROW_MAJOR && prob->J_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad J_layout");
+    const int min_ld = prob->J_layout == MO_ROW_MAJOR ? d.n : d.m_r;
+    if (prob->J_ld < min_ld) return fail(MO_ERR_DIMENSION, "J_ld %d < %d", prob->J_ld, min_ld);
+    if (a.t.dJ && a.t.dJ_ld < min_ld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a.t.dJ_ld, min_ld);
+    a.m_r = d.m_r;
+    a.J = prob->J; a.J_stride = prob->J_stride; a.J_ld = prob->J_ld; a.J_row_major = prob->J_layout == MO_ROW_MAJOR;
+    a.r = a.t.dJ ? prob->r : nullptr; a.r_stride = prob->r_stride;   // (w = J x + r is needed only against dJ)
+  }
+  if (a.t.dG && a.t.dG_ld < d.n) return fail(MO_ERR_DIMENSION, "dG_ld %d < n %d", a.t.dG_ld, d.n);
+  if (a.t.dA_eq && a.t.dA_ld < d.k) return fail(MO_ERR_DIMENSION, "dA_ld %d < k %d", a.t.dA_ld, d.k);
+  if (d.m > 0 && prob->cons_var) { a.cons_var = prob->cons_var; a.cons_stride = prob->cons_stride; }
+  if (mo::qp_tangent_lds_bytes(a, plan->elem) > 64 * 1024)
+    return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, m_r = %d: the vectors of one problem exceed the 64 KiB of LDS the tangent kernel uses", d.n, d.k, d.m, a.m_r);
+  if (batch == 0) return MO_OK;
+  MO_HIP_CHECK(hipSetDevice(d.device));
+  MO_HIP_CHECK(mo::launch_qp_tangent(a, d.dtype, plan->num_cus, (hipStream_t)stream));
   return MO_OK;
 }
 

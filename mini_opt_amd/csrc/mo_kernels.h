@@ -229,4 +229,19 @@ struct GradArgs {
 size_t qp_grad_lds_bytes(const GradArgs& a, int elem_size);
 hipError_t launch_qp_gradients(const GradArgs& a, int dtype, int num_cus, hipStream_t stream);
 
+// forward-mode right-hand side rho = F_theta thetadot of a QP (mo_qp_tangent_rhs), qp_tangent.hip: the transpose of the gradient kernel
+// above.  J, r are read only for the dJ / dr tangents (m_r = 0 otherwise), cons_var only when the problem has one.
+struct TangentArgs {
+  int n, k, m, m_r;
+  long long batch;
+  const void* vars; long long vars_stride;   // [batch][V]
+  const void* J; long long J_stride; int J_ld; int J_row_major;
+  const void* r; long long r_stride;
+  const int* cons_var; long long cons_stride;
+  mo_qp_tangents t;                          // NULL members are zero tangents
+  void* rho; long long rho_stride;           // [batch][V]
+};
+size_t qp_tangent_lds_bytes(const TangentArgs& a, int elem_size);
+hipError_t launch_qp_tangent(const TangentArgs& a, int dtype, int num_cus, hipStream_t stream);
+
 }  // namespace mo

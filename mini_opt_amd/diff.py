@@ -3,8 +3,11 @@
     kkt_solve       mo_kkt_solve     the KKT system of a state for the caller's right-hand side (direct or transposed)
     qp_gradients    mo_qp_gradients  gradients of a loss with respect to the QP's data from the state v and the adjoint u = K^-T g
     qp_gradients_blocks, qp_gradients_eq_blocks    the same for residual-block input: gradients of the PACKED local Jacobians
+    qp_tangent_rhs  mo_qp_tangent_rhs  forward mode: rho = F_theta thetadot from the state v and a direction in the QP's data
+    qp_jvp          qp_tangent_rhs + kkt_solve: the directional derivative vdot of the whole solution [x | s | y | z]
     solve_qp        the user-facing call: forward = Solve (the kernels of qp.QPInteriorPointSolver, fused where the shape allows),
-                    backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient
+                    backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient,
+                    jvp (torch.autograd.forward_ad) = ONE tangent launch + ONE KKT solve
 
 The mathematics is in include/mini_opt_hip.h (above mo_kkt_solve) and DESIGN.md section 4.8.  All arithmetic happens in the HIP library;
 torch owns memory, streams and the autograd graph.  Plans are created once per (shape, dtype, device, batch) and cached.
@@ -136,6 +139,78 @@ def qp_gradients(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor, want: 
     return out
 
 
+def qp_tangent_rhs(problem: BatchedQP, vars: torch.Tensor, tangents: Dict[str, torch.Tensor]) -> torch.Tensor:
+    """mo_qp_tangent_rhs: rho [B, V] = F_theta thetadot at the state `vars` [B, V] for the direction `tangents` in the problem's data, the
+    right-hand side of the forward-mode system K vdot = -rho.  `tangents` maps the keys of GRADIENTS to tensors in BatchedQP's layouts (the
+    layouts qp_gradients returns): "c" [B, n], "G" [B, n, n] (LOWER triangle read as a symmetric matrix, the rest ignored), "A_eq" [B, n, k],
+    "b_eq" [B, k], "cons_a", "cons_b" [B, m], "J" in the layout of problem.J (its own leading dimension allowed), "r" [B, m_r], "lam" [B].
+    A missing key is a zero tangent; a leading dimension of 1 is one direction shared by the batch."""
+    B = _check_state(problem, vars, "vars")
+    n, k, m = problem.n, problem.k, problem.m
+    j_level = problem.J is not None
+    t = L.QPTangents()
+    keep = []
+
+    def take(name, tail):
+        x = tangents[name]
+        if (x.dim() != 1 + len(tail) or tuple(int(d) for d in x.shape[1:]) != tuple(tail) or int(x.shape[0]) not in (1, B) or not x.is_contiguous()
+                or x.dtype != problem.dtype or x.device != problem.device):
+            raise ValueError(f"tangent {name!r}: expected a contiguous [{B} or 1, {', '.join(map(str, tail))}] {problem.dtype} tensor on "
+                             f"{problem.device}, got {tuple(x.shape)} {x.dtype}")
+        keep.append(x)
+        per = 1
+        for d in tail:
+            per *= int(d)
+        return _ptr(x), (0 if int(x.shape[0]) == 1 and B != 1 else per)
+
+    for w in tangents:
+        if w not in GRADIENTS:
+            raise ValueError(f"unknown tangent {w!r}: one of {GRADIENTS}")
+        if (w in ("A_eq", "b_eq") and k == 0) or (w in ("cons_a", "cons_b") and m == 0):
+            raise ValueError(f"tangent {w!r} of a problem without such rows")
+        if (w == "G" and j_level) or (w in ("J", "r", "lam") and not j_level):
+            raise ValueError(f"tangent {w!r} does not belong to this problem's input level ((J, r, lam) or (G, c))")
+    if "G" in tangents:
+        t.dG, t.dG_stride = take("G", (n, n))
+        t.dG_ld = n
+    if "c" in tangents:
+        t.dc, t.dc_stride = take("c", (n,))
+    if "A_eq" in tangents:
+        t.dA_eq, t.dA_stride = take("A_eq", (n, k))
+        t.dA_ld = k
+    if "b_eq" in tangents:
+        t.db_eq, t.db_stride = take("b_eq", (k,))
+    if "cons_a" in tangents:
+        t.dcons_a, t.dcons_stride = take("cons_a", (m,))
+    if "cons_b" in tangents:
+        t.dcons_b, stride_b = take("cons_b", (m,))
+        if "cons_a" in tangents and stride_b != t.dcons_stride:
+            raise ValueError("tangents 'cons_a' and 'cons_b' share one stride: give both per problem or both shared")
+        t.dcons_stride = stride_b
+    if "J" in tangents:
+        rows = int(problem.J.shape[1])
+        ld = int(tangents["J"].shape[-1]) if tangents["J"].dim() == 3 else 0
+        if ld < (problem.m_r if problem.J_layout == "col" else n):
+            raise ValueError(f"tangent 'J': leading dimension {ld} below the layout's minimum")
+        t.dJ, t.dJ_stride = take("J", (rows, ld))
+        t.dJ_ld = ld
+    if "r" in tangents:
+        t.dr, t.dr_stride = take("r", (problem.m_r,))
+    if "lam" in tangents:
+        t.dlambda, t.dlambda_stride = take("lam", ())
+    rho = torch.empty_like(vars)
+    prob = problem.as_struct()
+    L.check(L.lib().mo_qp_tangent_rhs(plan_for(problem, B), C.byref(prob), B, _ptr(vars), problem.V, C.byref(t), _ptr(rho), problem.V, _stream()))
+    return rho
+
+
+def qp_jvp(problem: BatchedQP, vars: torch.Tensor, tangents: Dict[str, torch.Tensor]):
+    """The directional derivative vdot [B, V] = (dv* / dtheta) thetadot of the solution [x | s | y | z] at `vars` along `tangents` (see
+    qp_tangent_rhs): one tangent launch and one KKT solve, K vdot = -rho.  Returns (vdot, status [B] int32 MO_STATUS_*); vdot is NaN for
+    problems whose status is not OK."""
+    return kkt_solve(problem, vars, qp_tangent_rhs(problem, vars, tangents), transpose=False)
+
+
 class QPSolveFunction(torch.autograd.Function):
     """v*(theta) = QPInteriorPointSolver::Solve with the adjoint of the KKT conditions as its backward.
 
@@ -165,13 +240,17 @@ class QPSolveFunction(torch.autograd.Function):
                                     _ptr(status), _stream()))
         ctx.problem, ctx.v, ctx.status = problem, v, status
         ctx.adjoint_status = None
+        ctx.tangent_status = None
         ctx.termination_state, ctx.num_iterations = term, nit
         ctx.mark_non_differentiable(status)
+        ctx.set_materialize_grads(False)   # jvp: an input without a tangent arrives as None, not as a tensor of zeros to be read
         return v.clone(), status
 
     @staticmethod
     def backward(ctx, g, _g_status):
         problem, v = ctx.problem, ctx.v
+        if g is None:
+            g = torch.zeros_like(v)
         u, adj = kkt_solve(problem, v, g.contiguous(), transpose=True)
         ctx.adjoint_status = adj
         names = ("G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b")
@@ -185,6 +264,37 @@ class QPSolveFunction(torch.autograd.Function):
                 t = torch.where(ok.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros((), dtype=t.dtype, device=t.device))
             out.append(t)
         return (*out, None, None)
+
+    @staticmethod
+    def jvp(ctx, dG, dc, dJ, dr, dlam, dA_eq, db_eq, dcons_a, dcons_b, _dcons_var, _dparams):
+        """torch.autograd.forward_ad: vdot = (dv* / dtheta) thetadot at the saved state, ONE tangent launch + ONE KKT solve.  The G tangent is
+        passed as 1/2 (Gdot + Gdot^T), so the JVP is the exact transpose of the backward for any Gdot.  A problem whose forward status or
+        tangent-solve status is not MO_STATUS_OK gets a ZERO tangent (the backward's rule); the solve's status words are kept
+        (`tangent_status`)."""
+        global _PENDING_TANGENT_STATUS
+        problem, v = ctx.problem, ctx.v
+        if dG is not None:
+            dG = 0.5 * (dG + dG.transpose(1, 2))
+        given = zip(GRADIENTS, (dG, dc, dJ, dr, dlam, dA_eq, db_eq, dcons_a, dcons_b))
+        tangents = {nm: t.detach().contiguous() for nm, t in given if t is not None}
+        vdot, st = qp_jvp(problem, v, tangents)
+        ctx.tangent_status = _PENDING_TANGENT_STATUS = st
+        ok = (ctx.status == L.MO_STATUS_OK) & (st == L.MO_STATUS_OK)
+        return _masked(vdot, ok), None
+
+
+_PENDING_TANGENT_STATUS: Optional[torch.Tensor] = None   # from QPSolveFunction.jvp to solve_qp, which hangs it on the tensors it returns
+
+
+def tangent_status(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """The [B] status words of the tangent solve behind a tensor solve_qp returned under torch.autograd.forward_ad (None if the call
+    carried no tangent)."""
+    while t is not None:
+        st = getattr(t, "_mo_tangent_status", None)
+        if st is not None:
+            return st
+        t = t._base
+    return None
 
 
 def _check_vu(layout: ResidualLayout, vars: torch.Tensor, u: torch.Tensor, k: int, m: int) -> int:
@@ -375,6 +485,11 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     m = 0 if cons_a is None else int(cons_a.shape[1])
     x = v[:, :n]
     res = (x, v[:, n:n + m], v[:, n + m:n + m + k], v[:, n + m + k:]) if return_all else (x,)
+    global _PENDING_TANGENT_STATUS
+    if _PENDING_TANGENT_STATUS is not None:   # the call ran under forward_ad: tangent_status() finds the words on what it returns
+        for t in (v, *res):
+            t._mo_tangent_status = _PENDING_TANGENT_STATUS
+        _PENDING_TANGENT_STATUS = None
     if return_status:
         res = res + (status,)
     return res[0] if len(res) == 1 else res

@@ -38,7 +38,7 @@ extern "C" {
 #endif
 
 #define MO_VERSION_MAJOR 0
-#define MO_VERSION_MINOR 4
+#define MO_VERSION_MINOR 5
 
 /* return codes */
 #define MO_OK 0
@@ -528,6 +528,56 @@ typedef struct {                                   /* every member optional: NUL
 } mo_qp_tangents;
 int mo_qp_tangent_rhs(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride,
                       const mo_qp_tangents* t, void* rho, int64_t rho_stride, void* stream);
+
+/* Forward mode for RESIDUAL-BLOCK input: the same rho from the PACKED tangents of the blocks, without forming an n x n or a rows x n
+ * matrix.  The (G, c) problem is the one mo_linearize_blocks / mo_jacobian_blocks produce, so rho is by definition what
+ * mo_qp_tangent_rhs gives for (G, c) input with dG, dc the directional derivatives of mo_linearize_blocks along (dJ_blocks, dr, dlambda)
+ * and dA_eq, db_eq those of mo_jacobian_blocks and r_eq along (dJ_eq_blocks, dr_eq).
+ * Cost blocks, with x_loc[p] = x[idx_b[p]], t_b = J_b x_loc + r_b and tdot_b = dJ_b x_loc + dr_b:
+ *   rho_d[i] += dJ_b[:, p] . t_b + J_b[:, p] . tdot_b                      for every local column p with idx_b[p] = i
+ *   rho_d[i] -= x_i (dJ_b[:, p] . J_b[:, q'])                              for every OTHER local column q' of block b on p's variable i
+ *   rho_d    += dlambda x
+ * The second line is the repeated-index rule of mo_qp_gradients_blocks seen from the other side: the pair (p, q') of one variable lands
+ * once, on the diagonal (w_b(p, q) = -u_i x_i above), so sym(G) lacks one J_p . J_q' against the dense J^T J of the gathered columns and the
+ * tangent lacks its derivative.  The partner lists are those of the backward and are empty for almost every layout.  dlambda counts
+ * unconditionally, as the dlambda of mo_qp_gradients_blocks does (a caller masks it where lambda <= 0).
+ * Equality blocks (mo_jacobian_blocks is linear in the packed values: no J_eq_blocks values are read), for a packed value e with stacked
+ * row `row` and global column g whose local column WINS g:
+ *   rho_pe[row] += dJeq[e] x[g]         rho_d[g] -= dJeq[e] y[row]         rho_pe += dr_eq
+ * A column that loses its global column contributes exactly nothing: its dJ_eq_blocks entries are never read into rho and may be NaN.
+ * Constraint rows as in mo_qp_tangent_rhs: rho_d[var_i] -= dcons_a[i] z_i, rho_pi[i] = dcons_a[i] x[var_i] + dcons_b[i] (NaN for a var_i
+ * outside [0, n)), rho_comp = 0.
+ * The transpose identity that ties the call to the merged backward: for every u and the same `vars`,
+ *   u . rho = - sum over the members of < gradient of the member from u,  tangent of the member >,
+ * the gradients being those of mo_qp_gradients_blocks (dJ_blocks, dr, dlambda), mo_qp_gradients_eq_blocks (dJ_eq_blocks, dr_eq) and
+ * mo_qp_gradients (dcons_a, dcons_b).  The two-call recipe:  mo_qp_tangent_rhs_blocks(..., t, rho, ...);  mo_kkt_solve on the (G, c)
+ * problem with rhs = rho, flags = 0, out = vdot.
+ * The plan is that of the (G, c) solve: it supplies n, k, m, dtype and device; no m_r requirement.  J_stride / r_stride and every tangent
+ * stride: per problem in elements, 0 = shared by the batch.  A NULL tangent member is a zero tangent and its inputs are not read:
+ * J_blocks is read only with dJ_blocks or dr, r only with dJ_blocks.  With k = 0 the equality members and eq_layout, with m = 0 the
+ * inequality members are ignored.  rho: [batch][V], all V values written, nothing beyond V.
+ * Arguments are judged before the plan is looked at.  MO_ERR_INVALID_ARGUMENT: NULL cost_layout / t / vars / rho; dJ_blocks or dr without
+ * J_blocks and r; dJ_eq_blocks or dr_eq without eq_layout; dcons_a without cons_var.  MO_ERR_DIMENSION: a layout's n differs from the
+ * plan's; eq_layout's rows differ from the plan's k.  MO_ERR_UNSUPPORTED, with nothing launched, if the vectors the kernel always keeps in
+ * LDS exceed 64 KiB:  (2 n + 2 k + m + 2 sum R_b) values (x, rho_d; y, rho_pe; dcons_a z; t, tdot) + 4 m bytes (the indices); partial
+ * sums live in registers.  Below that, J_blocks, dJ_blocks, r and dr go through LDS when 2 (sum R_b P_b + sum R_b) values fit 48 KiB and
+ * the total fits 64 KiB, and are read from global memory otherwise.
+ * One workgroup per problem in turn; every element of rho has one owner (a fixed-width group of lanes walks variable i's contribution
+ * list in the layout's order and adds its partial sums in a shuffle tree of fixed shape), products are rounded before they are added: no
+ * atomics, two launches give the same bits.  No allocation and no synchronisation on the launch path: the schedule is part of the
+ * layouts. */
+typedef struct {                      /* every member optional: NULL = zero tangent; strides per problem in elements, 0 = one direction shared by the batch */
+  const void* dJ_blocks;    int64_t dJ_stride;      /* packing of J_blocks */
+  const void* dr;           int64_t dr_stride;
+  const void* dlambda;      int64_t dlambda_stride;
+  const void* dJ_eq_blocks; int64_t dJ_eq_stride;   /* packing of J_eq_blocks */
+  const void* dr_eq;        int64_t dr_eq_stride;
+  const void* dcons_a; const void* dcons_b; int64_t dcons_stride;
+} mo_block_tangents;
+int mo_qp_tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride,
+                             const void* r, int64_t r_stride, const mo_residual_layout* eq_layout,
+                             const int32_t* cons_var, int64_t cons_stride, int64_t batch, const void* vars, int64_t vars_stride,
+                             const mo_block_tangents* t, void* rho, int64_t rho_stride, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@ from ._lib import MiniOptError, build  # noqa: F401
 
 
 _DIFF_EXPORTS = ("solve_qp", "kkt_solve", "qp_gradients", "qp_gradients_blocks", "qp_gradients_eq_blocks", "QPSolveFunction",
-                 "QPSolveBlocksFunction", "adjoint_status", "qp_tangent_rhs", "qp_jvp", "tangent_status")
+                 "QPSolveBlocksFunction", "adjoint_status", "qp_tangent_rhs", "qp_jvp", "tangent_status",
+                 "qp_tangent_rhs_blocks", "qp_jvp_blocks")
 
 
 def __getattr__(name):  # the differentiable front end needs torch: imported on first use, like qp

@@ -35,7 +35,7 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_default_nls_params", "mo_nls_solve", "mo_nullspace_solve", "mo_residual_eval", "mo_qp_eigenvalue_stats",
            "mo_residual_layout_create", "mo_residual_layout_destroy", "mo_residual_layout_values", "mo_residual_layout_rows",
            "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks", "mo_kkt_solve", "mo_qp_gradients",
-           "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_tangent_rhs"]
+           "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_tangent_rhs", "mo_qp_tangent_rhs_blocks"]
 
 
 class PlanDesc(C.Structure):
@@ -117,6 +117,17 @@ class BlockGrads(C.Structure):
                 ("dlambda", C.c_void_p), ("dlambda_stride", C.c_int64)]
 
 
+class BlockTangents(C.Structure):
+    """mo_block_tangents: optional device inputs of mo_qp_tangent_rhs_blocks, in the packed layouts of the residual-block input (a NULL member is
+    a zero tangent; stride 0 = shared by the batch)."""
+    _fields_ = [("dJ_blocks", C.c_void_p), ("dJ_stride", C.c_int64),
+                ("dr", C.c_void_p), ("dr_stride", C.c_int64),
+                ("dlambda", C.c_void_p), ("dlambda_stride", C.c_int64),
+                ("dJ_eq_blocks", C.c_void_p), ("dJ_eq_stride", C.c_int64),
+                ("dr_eq", C.c_void_p), ("dr_eq_stride", C.c_int64),
+                ("dcons_a", C.c_void_p), ("dcons_b", C.c_void_p), ("dcons_stride", C.c_int64)]
+
+
 NLS_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
 MO_NLS_EVAL_LINEARIZE, MO_NLS_EVAL_ERRORS, MO_NLS_EVAL_RETRACT, MO_NLS_EVAL_ITERATION_DONE = 0, 1, 2, 3
 MO_RETRACT_EUCLIDEAN, MO_RETRACT_WRAP_PI, MO_RETRACT_CALLBACK = 0, 1, 2
@@ -132,7 +143,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "tools", "isa_lint.py"))   # the build lints its own listings: a changed lint re-runs it
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
-        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (fifteen units, the longest 5.7 min)
+        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (sixteen units, the longest 5.7 min)
         subprocess.check_call(["make", "-C", CSRC, f"-j{jobs}"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
@@ -196,6 +207,7 @@ def lib() -> C.CDLL:
     L.mo_qp_gradients_blocks.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.POINTER(BlockGrads), vp]
     L.mo_qp_gradients_eq_blocks.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.mo_qp_tangent_rhs.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, C.POINTER(QPTangents), vp, i64, vp]
+    L.mo_qp_tangent_rhs_blocks.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, C.POINTER(BlockTangents), vp, i64, vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what the header declares
     _lib = L

@@ -59,6 +59,8 @@ struct mo_residual_layout {
   const int* g_ptr; const int4* g_ent; const int* c_ptr; const int4* c_ent; const int2* row_info; const int* win;
   // the backward schedule (mo_qp_gradients_blocks / mo_qp_gradients_eq_blocks, mo::BlockGradArgs)
   const int4* d_row; const int4* d_val; const int2* e_val; const int* d_idx; const int* d_dup;
+  // the forward-mode schedule of an equality layout (mo_qp_tangent_rhs_blocks, mo::BlockTangentArgs): c_ptr / c_ent filtered by winners
+  const int* w_ptr; const int4* w_ent;
 };
 
 namespace {
@@ -206,7 +208,7 @@ struct NlsScratch {  // one allocation carved into 256-byte aligned pieces
 
 extern "C" {
 
-const char* mo_version_string(void) { return "mini_opt_hip 0.4 (gfx950)"; }
+const char* mo_version_string(void) { return "mini_opt_hip 0.5 (gfx950)"; }
 
 const char* mo_status_string(int32_t status) {
   switch (status) {
@@ -1118,17 +1120,30 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
       ib += P; off += (long long)R * P; roff += R;
     }
   }
-  // one device allocation: [g_ent | c_ent | g_ptr | c_ptr | row_info | win | d_row | d_val | e_val | d_idx | d_dup], 16-byte aligned pieces
+  // the forward-mode schedule: every entry of a variable's list carries its column's partner list (mo_qp_tangent_rhs_blocks walks the list
+  // and needs no second look-up), and per variable, in the layout's order, the local columns that WIN it (the columns mo_jacobian_blocks copies)
+  for (size_t e = 0; e < c_ent.size(); ++e) c_ent[e].w = d_val[(size_t)c_ent[e].x].w;
+  std::vector<int> w_ptr((size_t)n + 1, 0);
+  std::vector<int4> w_ent;
+  {
+    for (int i = 0; i < n; ++i) {
+      for (int e = c_ptr[i]; e < c_ptr[i + 1]; ++e)
+        if (e_val[(size_t)c_ent[e].x].y >= 0) w_ent.push_back(c_ent[e]);
+      w_ptr[(size_t)i + 1] = (int)w_ent.size();
+    }
+  }
+  // one device allocation: [g_ent | c_ent | g_ptr | c_ptr | row_info | win | d_row | d_val | e_val | d_idx | d_dup | w_ent | w_ptr], 16-byte aligned pieces
   auto pad = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
   const size_t b_ge = pad(g_ent.size() * sizeof(int4)), b_ce = pad(c_ent.size() * sizeof(int4)), b_gp = pad(g_ptr.size() * sizeof(int)),
                b_cp = pad(c_ptr.size() * sizeof(int)), b_ri = pad(row_info.size() * sizeof(int2)), b_w = pad(win.size() * sizeof(int)),
                b_dr = pad(d_row.size() * sizeof(int4)), b_dv = pad(d_val.size() * sizeof(int4)), b_ev = pad(e_val.size() * sizeof(int2)),
-               b_di = pad(d_idx.size() * sizeof(int)), b_dd = pad(d_dup.size() * sizeof(int));
+               b_di = pad(d_idx.size() * sizeof(int)), b_dd = pad(d_dup.size() * sizeof(int)),
+               b_we = pad(w_ent.size() * sizeof(int4)), b_wp = pad(w_ptr.size() * sizeof(int));
   mo_residual_layout* L = new (std::nothrow) mo_residual_layout();
   if (!L) return fail(MO_ERR_HIP, "out of host memory");
   L->device = plan->desc.device; L->n = n; L->num_blocks = num_blocks; L->rows = (int)total_rows; L->values = values;
   L->dev = nullptr;
-  const size_t total = b_ge + b_ce + b_gp + b_cp + b_ri + b_w + b_dr + b_dv + b_ev + b_di + b_dd;
+  const size_t total = b_ge + b_ce + b_gp + b_cp + b_ri + b_w + b_dr + b_dv + b_ev + b_di + b_dd + b_we + b_wp;
   if (hipSetDevice(plan->desc.device) != hipSuccess || hipMalloc(&L->dev, total) != hipSuccess) {
     (void)hipGetLastError();
     delete L;
@@ -1141,10 +1156,11 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
       {row_info.data(), row_info.size() * sizeof(int2), b_ri}, {win.data(), win.size() * sizeof(int), b_w},
       {d_row.data(), d_row.size() * sizeof(int4), b_dr}, {d_val.data(), d_val.size() * sizeof(int4), b_dv},
       {e_val.data(), e_val.size() * sizeof(int2), b_ev}, {d_idx.data(), d_idx.size() * sizeof(int), b_di},
-      {d_dup.data(), d_dup.size() * sizeof(int), b_dd}};
+      {d_dup.data(), d_dup.size() * sizeof(int), b_dd},  {w_ent.data(), w_ent.size() * sizeof(int4), b_we},
+      {w_ptr.data(), w_ptr.size() * sizeof(int), b_wp}};
   size_t at = 0;
-  const void* dst[11];
-  for (int i = 0; i < 11; ++i) {
+  const void* dst[13];
+  for (int i = 0; i < 13; ++i) {
     dst[i] = base + at;
     if (pieces[i].bytes && hipMemcpy(base + at, pieces[i].src, pieces[i].bytes, hipMemcpyHostToDevice) != hipSuccess) {
       (void)hipGetLastError();
@@ -1158,6 +1174,7 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
   L->row_info = (const int2*)dst[4]; L->win = (const int*)dst[5];
   L->d_row = (const int4*)dst[6]; L->d_val = (const int4*)dst[7]; L->e_val = (const int2*)dst[8]; L->d_idx = (const int*)dst[9];
   L->d_dup = (const int*)dst[10];
+  L->w_ent = (const int4*)dst[11]; L->w_ptr = (const int*)dst[12];
   *out = L;
   return MO_OK;
 }
@@ -1260,6 +1277,50 @@ int mo_qp_gradients_eq_blocks(mo_plan* plan, const mo_residual_layout* eq_layout
   a.dJ = dJ_eq_blocks; a.dJ_stride = dJ_eq_stride; a.dr = dr_eq; a.dr_stride = dr_eq_stride;
   MO_HIP_CHECK(hipSetDevice(plan->desc.device));
   MO_HIP_CHECK(mo::launch_blocks_eq_grad(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+int mo_qp_tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride,
+                             const void* r, int64_t r_stride, const mo_residual_layout* eq_layout, const int32_t* cons_var,
+                             int64_t cons_stride, int64_t batch, const void* vars, int64_t vars_stride, const mo_block_tangents* t, void* rho,
+                             int64_t rho_stride, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
+  if (!t) return fail(MO_ERR_INVALID_ARGUMENT, "t is NULL");
+  if (!vars || !rho) return fail(MO_ERR_INVALID_ARGUMENT, "vars / rho is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if ((t->dJ_blocks || t->dr) && (!J_blocks || !r)) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_blocks / dr given but J_blocks / r is NULL");
+  if ((t->dJ_eq_blocks || t->dr_eq) && !eq_layout) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_eq_blocks / dr_eq given but eq_layout is NULL");
+  if (t->dcons_a && !cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a given but cons_var is NULL");
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, cost_layout)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  if (eq_layout && d.k > 0) {  // (with k = 0 the equality members and the layout are ignored)
+    if (int rc = check_layout(plan, eq_layout)) return rc;
+    if (eq_layout->rows != d.k) return fail(MO_ERR_DIMENSION, "eq_layout has %d rows, plan k = %d", eq_layout->rows, d.k);
+  }
+  if (!mo::blocks_tangent_fits(d.n, d.k, d.m, cost_layout->rows, plan->elem))
+    return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, %d residual rows: the vectors of one problem (%zu B) exceed the 64 KiB of LDS the block tangent kernel uses",
+                d.n, d.k, d.m, cost_layout->rows, mo::blocks_tangent_lds_bytes(d.n, d.k, d.m, cost_layout->rows, plan->elem));
+  if (batch == 0) return MO_OK;
+  mo::BlockTangentArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = d.n; a.k = d.k; a.m = d.m; a.rows = cost_layout->rows; a.values = cost_layout->values; a.batch = batch;
+  a.d_row = cost_layout->d_row; a.d_idx = cost_layout->d_idx; a.d_dup = cost_layout->d_dup;
+  a.c_ptr = cost_layout->c_ptr; a.c_ent = cost_layout->c_ent;
+  a.vars = vars; a.vars_stride = vars_stride; a.rho = rho; a.rho_stride = rho_stride;
+  a.t = *t;
+  if (d.k == 0 || !eq_layout) { a.t.dJ_eq_blocks = nullptr; a.t.dr_eq = nullptr; }
+  else { a.e_row = eq_layout->d_row; a.e_val = eq_layout->e_val; a.w_ptr = eq_layout->w_ptr; a.w_ent = eq_layout->w_ent; }
+  if (d.m == 0) { a.t.dcons_a = nullptr; a.t.dcons_b = nullptr; }
+  else if (cons_var) { a.cons_var = cons_var; a.cons_stride = cons_stride; }
+  if (a.t.dJ_blocks || a.t.dr) {  // the only tangents that read the blocks; r only against dJ_blocks
+    a.J = J_blocks; a.J_stride = J_stride;
+    if (a.t.dJ_blocks) { a.r = r; a.r_stride = r_stride; }
+  }
+  MO_HIP_CHECK(hipSetDevice(d.device));
+  MO_HIP_CHECK(mo::launch_blocks_tangent(a, d.dtype, plan->num_cus, (hipStream_t)stream));
   return MO_OK;
 }
 

@@ -176,7 +176,7 @@ struct BlocksArgs {
   const int* g_ptr;           // [n * n + 1] CSR over the cells of G in column-major order (strict upper cells: empty lists)
   const int4* g_ent;          // {offset of J col a, offset of J col b, R_b, 0}: G(i, j) += J_a . J_b, in the reference's order
   const int* c_ptr;           // [n + 1]
-  const int4* c_ent;          // {offset of J col a, offset of block b's rows in r, R_b, 0}: c(i) += J_a . r_b
+  const int4* c_ent;          // {offset of J col a, offset of block b's rows in r, R_b, a's partner list in d_dup or -1}: c(i) += J_a . r_b
   const int2* row_info;       // [rows] {b * n, row within block b}
   const int* win;             // [num_blocks * n] offset of the column block b assigns to global column j (last wins), -1: none
   const void* J; long long J_stride;
@@ -243,5 +243,31 @@ struct TangentArgs {
 };
 size_t qp_tangent_lds_bytes(const TangentArgs& a, int elem_size);
 hipError_t launch_qp_tangent(const TangentArgs& a, int dtype, int num_cus, hipStream_t stream);
+
+// the same right-hand side for residual-block input (mo_qp_tangent_rhs_blocks), qp_tangent_blocks.hip: the transpose of blocks_grad_kernel
+// and blocks_eq_grad_kernel, from the packed tangents alone.  The schedules are those of the two layouts (mo_residual_layout_create).
+struct BlockTangentArgs {
+  int n, k, m, rows;          // plan n, k, m; sum R_b of the cost layout
+  long long values;           // packed cost values per problem
+  long long batch;
+  const int4* d_row;          // cost layout: [rows] {offset of J_b[q, 0], R_b, P_b, start of idx_b in d_idx}
+  const int* d_idx;
+  const int* d_dup;           // partner lists: {count, count x offset of J_b[0, q']}
+  const int* c_ptr;           // [n + 1] per variable i, in the layout's order:
+  const int4* c_ent;          // {offset of J_b[0, p], first stacked row of block b, R_b, start of p's partner list in d_dup or -1} per local column p on i
+  const int4* e_row;          // equality layout (NULL without one): its d_row, [k]
+  const int2* e_val;          // its e_val: {stacked row, global index or -1 for a column that loses its global column}
+  const int* w_ptr;           // [n + 1] its c_ptr / c_ent filtered by winners: the columns that reach A_eq
+  const int4* w_ent;
+  const void* J; long long J_stride;   // read only with dJ_blocks or dr
+  const void* r; long long r_stride;   // read only with dJ_blocks
+  const void* vars; long long vars_stride;
+  const int* cons_var; long long cons_stride;
+  mo_block_tangents t;        // NULL members are zero tangents
+  void* rho; long long rho_stride;
+};
+size_t blocks_tangent_lds_bytes(int n, int k, int m, int rows, int elem_size);   // the vectors the kernel always keeps in LDS
+bool blocks_tangent_fits(int n, int k, int m, int rows, int elem_size);          // ... within 64 KiB
+hipError_t launch_blocks_tangent(const BlockTangentArgs& a, int dtype, int num_cus, hipStream_t stream);
 
 }  // namespace mo

@@ -5,9 +5,10 @@
     qp_gradients_blocks, qp_gradients_eq_blocks    the same for residual-block input: gradients of the PACKED local Jacobians
     qp_tangent_rhs  mo_qp_tangent_rhs  forward mode: rho = F_theta thetadot from the state v and a direction in the QP's data
     qp_jvp          qp_tangent_rhs + kkt_solve: the directional derivative vdot of the whole solution [x | s | y | z]
+    qp_tangent_rhs_blocks, qp_jvp_blocks    the same for residual-block input: rho from the PACKED tangents of the blocks
     solve_qp        the user-facing call: forward = Solve (the kernels of qp.QPInteriorPointSolver, fused where the shape allows),
                     backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient,
-                    jvp (torch.autograd.forward_ad) = ONE tangent launch + ONE KKT solve
+                    jvp (torch.autograd.forward_ad) = ONE tangent launch + ONE KKT solve, for all three input forms
 
 The mathematics is in include/mini_opt_hip.h (above mo_kkt_solve) and DESIGN.md section 4.8.  All arithmetic happens in the HIP library;
 torch owns memory, streams and the autograd graph.  Plans are created once per (shape, dtype, device, batch) and cached.
@@ -361,6 +362,92 @@ def qp_gradients_eq_blocks(eq_layout: ResidualLayout, vars: torch.Tensor, u: tor
     return out
 
 
+BLOCK_TANGENTS = ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq", "cons_a", "cons_b")
+
+
+def qp_tangent_rhs_blocks(layout: ResidualLayout, J_blocks: Optional[torch.Tensor], r: Optional[torch.Tensor], vars: torch.Tensor,
+                          tangents: Dict[str, torch.Tensor], k: int = 0, m: int = 0, eq_layout: Optional[ResidualLayout] = None,
+                          cons_var: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mo_qp_tangent_rhs_blocks: rho [B, V] = F_theta thetadot at the state `vars` [B, V] of the (G, c) problem the blocks were linearised
+    into, for a direction in the PACKED block data; no n x n or rows x n matrix is formed.  `tangents` maps "J_blocks" [B, layout.values],
+    "r" [B, layout.rows], "lam" [B], "J_eq_blocks" [B, eq_layout.values], "r_eq" [B, k], "cons_a", "cons_b" [B, m] to tensors; a missing key
+    is a zero tangent, a leading dimension of 1 is one direction shared by the batch.  J_blocks [B or 1, values] and r [B or 1, rows] are
+    needed (and read) only with the "J_blocks" / "r" tangents.  k, m: the problem's equality and inequality rows (k = eq_layout.rows when an
+    eq_layout is given); cons_var int32 [B or 1, m] with "cons_a"."""
+    if eq_layout is not None:
+        if eq_layout.n != layout.n or eq_layout.dtype != layout.dtype or eq_layout.device != layout.device:
+            raise ValueError("eq_layout must share n, dtype and device with layout")
+        k = eq_layout.rows
+    n, k, m = layout.n, int(k), int(m)
+    V = n + 2 * m + k
+    dt, dev = layout.dtype, layout.device
+    if vars.dim() != 2 or int(vars.shape[1]) != V or not vars.is_contiguous() or vars.dtype != dt or vars.device != dev:
+        raise ValueError(f"vars: expected a contiguous [B, {V}] {dt} tensor on {dev}, got {tuple(vars.shape)} {vars.dtype}")
+    B = int(vars.shape[0])
+    for w in tangents:
+        if w not in BLOCK_TANGENTS:
+            raise ValueError(f"unknown tangent {w!r}: one of {BLOCK_TANGENTS}")
+        if (w in ("J_eq_blocks", "r_eq") and (k == 0 or eq_layout is None)) or (w in ("cons_a", "cons_b") and m == 0):
+            raise ValueError(f"tangent {w!r} of a problem without such rows")
+    keep = []
+
+    def take(x, name, tail, dtype=dt):
+        if (x is None or x.dim() != 1 + len(tail) or tuple(int(d) for d in x.shape[1:]) != tuple(tail) or int(x.shape[0]) not in (1, B)
+                or not x.is_contiguous() or x.dtype != dtype or x.device != dev):
+            got = "None" if x is None else f"{tuple(x.shape)} {x.dtype}"
+            raise ValueError(f"{name}: expected a contiguous [{B} or 1, {', '.join(map(str, tail))}] {dtype} tensor on {dev}, got {got}")
+        keep.append(x)
+        per = 1
+        for d in tail:
+            per *= int(d)
+        return _ptr(x), (0 if int(x.shape[0]) == 1 and B != 1 else per)
+
+    t = L.BlockTangents()
+    J_ptr = r_ptr = None
+    J_stride = r_stride = 0
+    if "J_blocks" in tangents or "r" in tangents:
+        J_ptr, J_stride = take(J_blocks, "J_blocks", (layout.values,))
+        r_ptr, r_stride = take(r, "r", (layout.rows,))
+    if "J_blocks" in tangents:
+        t.dJ_blocks, t.dJ_stride = take(tangents["J_blocks"], "tangent 'J_blocks'", (layout.values,))
+    if "r" in tangents:
+        t.dr, t.dr_stride = take(tangents["r"], "tangent 'r'", (layout.rows,))
+    if "lam" in tangents:
+        t.dlambda, t.dlambda_stride = take(tangents["lam"], "tangent 'lam'", ())
+    if "J_eq_blocks" in tangents:
+        t.dJ_eq_blocks, t.dJ_eq_stride = take(tangents["J_eq_blocks"], "tangent 'J_eq_blocks'", (eq_layout.values,))
+    if "r_eq" in tangents:
+        t.dr_eq, t.dr_eq_stride = take(tangents["r_eq"], "tangent 'r_eq'", (k,))
+    if "cons_a" in tangents:
+        t.dcons_a, t.dcons_stride = take(tangents["cons_a"], "tangent 'cons_a'", (m,))
+    if "cons_b" in tangents:
+        t.dcons_b, stride_b = take(tangents["cons_b"], "tangent 'cons_b'", (m,))
+        if "cons_a" in tangents and stride_b != t.dcons_stride:
+            raise ValueError("tangents 'cons_a' and 'cons_b' share one stride: give both per problem or both shared")
+        t.dcons_stride = stride_b
+    cv_ptr, cv_stride = None, 0
+    if m and cons_var is not None:
+        cv_ptr, cv_stride = take(cons_var, "cons_var", (m,), torch.int32)
+    elif "cons_a" in tangents:
+        raise ValueError("tangent 'cons_a' needs cons_var")
+    rho = torch.empty_like(vars)
+    plan = _plan_of(n, k, m, 0, dt, dev, B)
+    L.check(L.lib().mo_qp_tangent_rhs_blocks(plan, layout.h, J_ptr, J_stride, r_ptr, r_stride, None if eq_layout is None else eq_layout.h,
+                                             cv_ptr, cv_stride, B, _ptr(vars), V, C.byref(t), _ptr(rho), V, _stream()))
+    return rho
+
+
+def qp_jvp_blocks(problem: BatchedQP, layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, vars: torch.Tensor,
+                  tangents: Dict[str, torch.Tensor], eq_layout: Optional[ResidualLayout] = None):
+    """The directional derivative vdot [B, V] of the solution of the (G, c) problem `problem` that linearize_blocks / jacobian_blocks built
+    from the blocks, along `tangents` in the packed block data (see qp_tangent_rhs_blocks): one tangent launch and one KKT solve on
+    `problem`, K vdot = -rho.  Returns (vdot, status [B] int32 MO_STATUS_*); vdot is NaN for problems whose status is not OK."""
+    if problem.n != layout.n or (eq_layout is not None and eq_layout.rows != problem.k):
+        raise ValueError("problem does not belong to these layouts (n / k differ)")
+    rho = qp_tangent_rhs_blocks(layout, J_blocks, r, vars, tangents, k=problem.k, m=problem.m, eq_layout=eq_layout, cons_var=problem.cons_var)
+    return kkt_solve(problem, vars, rho, transpose=False)
+
+
 def _masked(t: Optional[torch.Tensor], ok: torch.Tensor) -> Optional[torch.Tensor]:
     if t is None:
         return None
@@ -397,13 +484,17 @@ class QPSolveBlocksFunction(torch.autograd.Function):
         ctx.problem, ctx.v, ctx.status = problem, v, status
         ctx.layout, ctx.eq_layout, ctx.J_blocks, ctx.r, ctx.lam = layout, eq_layout, J_blocks, r, lam
         ctx.adjoint_status = None
+        ctx.tangent_status = None
         ctx.termination_state, ctx.num_iterations = term, nit
         ctx.mark_non_differentiable(status)
+        ctx.set_materialize_grads(False)   # jvp: an input without a tangent arrives as None, not as a tensor of zeros to be read
         return v.clone(), status
 
     @staticmethod
     def backward(ctx, g, _g_status):
         problem, v = ctx.problem, ctx.v
+        if g is None:
+            g = torch.zeros_like(v)
         u, adj = kkt_solve(problem, v, g.contiguous(), transpose=True)
         ctx.adjoint_status = adj
         need = ctx.needs_input_grad
@@ -418,6 +509,23 @@ class QPSolveBlocksFunction(torch.autograd.Function):
         cons = qp_gradients(problem, v, u, want) if want else {}
         out = [cost.get("J_blocks"), cost.get("r"), cost.get("lam"), eq.get("J_eq_blocks"), eq.get("r_eq"), cons.get("cons_a"), cons.get("cons_b")]
         return (*[_masked(t, ok) for t in out], None, None, None, None)
+
+    @staticmethod
+    def jvp(ctx, dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b, _dcons_var, _dlayout, _deq_layout, _dparams):
+        """torch.autograd.forward_ad: vdot at the saved state from the packed tangents, ONE mo_qp_tangent_rhs_blocks launch + ONE KKT solve on
+        the (G, c) problem the forward built.  lam's tangent counts only where lam was added (lam > 0), as its gradient does.  A problem whose
+        forward status or tangent-solve status is not MO_STATUS_OK gets a ZERO tangent (the backward's rule); the solve's status words are
+        kept (`tangent_status`)."""
+        global _PENDING_TANGENT_STATUS
+        problem, v = ctx.problem, ctx.v
+        if dlam is not None:
+            dlam = torch.where(ctx.lam > 0, dlam, torch.zeros((), dtype=v.dtype, device=v.device))
+        given = zip(BLOCK_TANGENTS, (dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b))
+        tangents = {nm: t.detach().contiguous() for nm, t in given if t is not None}
+        vdot, st = qp_jvp_blocks(problem, ctx.layout, ctx.J_blocks, ctx.r, v, tangents, eq_layout=ctx.eq_layout)
+        ctx.tangent_status = _PENDING_TANGENT_STATUS = st
+        ok = (ctx.status == L.MO_STATUS_OK) & (st == L.MO_STATUS_OK)
+        return _masked(vdot, ok), None
 
 
 def adjoint_status(t: torch.Tensor) -> Optional[torch.Tensor]:
@@ -518,6 +626,11 @@ def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, con
     n, k = layout.n, 0 if eq_layout is None else eq_layout.rows
     m = 0 if cons_a is None else int(cons_a.shape[1])
     res = (v[:, :n], v[:, n:n + m], v[:, n + m:n + m + k], v[:, n + m + k:]) if return_all else (v[:, :n],)
+    global _PENDING_TANGENT_STATUS
+    if _PENDING_TANGENT_STATUS is not None:   # the call ran under forward_ad: tangent_status() finds the words on what it returns
+        for t in (v, *res):
+            t._mo_tangent_status = _PENDING_TANGENT_STATUS
+        _PENDING_TANGENT_STATUS = None
     if return_status:
         res = res + (status,)
     return res[0] if len(res) == 1 else res

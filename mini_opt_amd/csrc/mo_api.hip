@@ -185,6 +185,36 @@ const char* plan_kernel_name(const mo_plan* plan, const mo_problem* prob, int mo
   return decide(plan, a).name;
 }
 
+// What mo_qp_gradients and mo_qp_tangent_rhs share once their own argument checks have passed: the plan, the shape, the state, and the rule
+// of who reads J.  `mem` is the caller's copy of its mo_qp_grads / mo_qp_tangents (the members named here carry the same names in both): the
+// members of rows the plan does not have are dropped, and J, r are checked and handed over only if dJ or dr is among the rest.
+template <typename Members>
+int sens_args(const mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, Members* mem, mo::SensArgs* a) {
+  if (int rc = check_plan(plan)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  a->n = d.n; a->k = d.k; a->m = d.m; a->batch = batch;
+  a->vars = vars; a->vars_stride = vars_stride;
+  if (d.k == 0) { mem->dA_eq = nullptr; mem->db_eq = nullptr; }
+  if (d.m == 0) { mem->dcons_a = nullptr; mem->dcons_b = nullptr; }
+  if (mem->dJ || mem->dr) {
+    if (d.m_r <= 0) return fail(MO_ERR_DIMENSION, "J given but the plan was created with m_r = 0");
+    if (prob->J_layout != MO_ROW_MAJOR && prob->J_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad J_layout");
+    const int min_ld = prob->J_layout == MO_ROW_MAJOR ? d.n : d.m_r;
+    if (prob->J_ld < min_ld) return fail(MO_ERR_DIMENSION, "J_ld %d < %d", prob->J_ld, min_ld);
+    a->m_r = d.m_r;
+    a->J = prob->J; a->J_stride = prob->J_stride; a->J_ld = prob->J_ld; a->J_row_major = prob->J_layout == MO_ROW_MAJOR;
+    a->r = prob->r; a->r_stride = prob->r_stride;
+  }
+  return MO_OK;
+}
+
+// ... and after their checks of dJ: the leading dimensions of the other two matrix members
+template <typename Members> int check_dG_dA_ld(const mo_plan_desc& d, const Members& mem) {
+  if (mem.dG && mem.dG_ld < d.n) return fail(MO_ERR_DIMENSION, "dG_ld %d < n %d", mem.dG_ld, d.n);
+  if (mem.dA_eq && mem.dA_ld < d.k) return fail(MO_ERR_DIMENSION, "dA_ld %d < k %d", mem.dA_ld, d.k);
+  return MO_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -539,32 +569,19 @@ int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const 
   if (!j_level && (out->dJ || out->dr || out->dlambda))
     return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr / dlambda asked for with (G, c) input: ask for dG / dc");
   if (!vars || !u) return fail(MO_ERR_INVALID_ARGUMENT, "vars / u is NULL");
-  if (int rc = check_plan(plan)) return rc;
-  const mo_plan_desc& d = plan->desc;
   mo::GradArgs a;
   memset(&a, 0, sizeof(a));
-  a.n = d.n; a.k = d.k; a.m = d.m; a.batch = batch;
-  a.vars = vars; a.vars_stride = vars_stride; a.u = u; a.u_stride = u_stride;
+  a.u = u; a.u_stride = u_stride;
   a.out = *out;
-  if (d.k == 0) { a.out.dA_eq = nullptr; a.out.db_eq = nullptr; }
-  if (d.m == 0) { a.out.dcons_a = nullptr; a.out.dcons_b = nullptr; }
-  if (a.out.dJ || a.out.dr) {  // the only outputs that read J
-    if (d.m_r <= 0) return fail(MO_ERR_DIMENSION, "J given but the plan was created with m_r = 0");
-    if (prob->J_layout != MO_ROW_MAJOR && prob->J_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad J_layout");
-    const int min_ld = prob->J_layout == MO_ROW_MAJOR ? d.n : d.m_r;
-    if (prob->J_ld < min_ld) return fail(MO_ERR_DIMENSION, "J_ld %d < %d", prob->J_ld, min_ld);
-    if (!prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "J given without r");
-    a.m_r = d.m_r;
-    a.J = prob->J; a.J_stride = prob->J_stride; a.J_ld = prob->J_ld; a.J_row_major = prob->J_layout == MO_ROW_MAJOR;
-    a.r = prob->r; a.r_stride = prob->r_stride;
-    if (a.out.dJ) {
-      if (a.out.dJ_layout != MO_ROW_MAJOR && a.out.dJ_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad dJ_layout");
-      const int min_dld = a.out.dJ_layout == MO_ROW_MAJOR ? d.n : d.m_r;
-      if (a.out.dJ_ld < min_dld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a.out.dJ_ld, min_dld);
-    }
+  if (int rc = sens_args(plan, prob, batch, vars, vars_stride, &a.out, &a)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  if (a.J && !prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "J given without r");   // (t, w = J x + r: both outputs that read J read r)
+  if (a.out.dJ) {
+    if (a.out.dJ_layout != MO_ROW_MAJOR && a.out.dJ_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad dJ_layout");
+    const int min_dld = a.out.dJ_layout == MO_ROW_MAJOR ? d.n : d.m_r;
+    if (a.out.dJ_ld < min_dld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a.out.dJ_ld, min_dld);
   }
-  if (a.out.dG && a.out.dG_ld < d.n) return fail(MO_ERR_DIMENSION, "dG_ld %d < n %d", a.out.dG_ld, d.n);
-  if (a.out.dA_eq && a.out.dA_ld < d.k) return fail(MO_ERR_DIMENSION, "dA_ld %d < k %d", a.out.dA_ld, d.k);
+  if (int rc = check_dG_dA_ld(d, a.out)) return rc;
   if (a.out.dcons_a) {
     if (!prob->cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a asked for but cons_var is NULL");
     a.cons_var = prob->cons_var; a.cons_stride = prob->cons_stride;
@@ -591,27 +608,19 @@ int mo_qp_tangent_rhs(mo_plan* plan, const mo_problem* prob, int64_t batch, cons
     return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr / dlambda given with (G, c) input (prob->J is NULL): give dG / dc");
   if (t->dJ && !prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "dJ given without prob->r");
   if (t->dcons_a && !prob->cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a given but cons_var is NULL");
-  if (int rc = check_plan(plan)) return rc;
-  const mo_plan_desc& d = plan->desc;
   mo::TangentArgs a;
   memset(&a, 0, sizeof(a));
-  a.n = d.n; a.k = d.k; a.m = d.m; a.batch = batch;
-  a.vars = vars; a.vars_stride = vars_stride; a.rho = rho; a.rho_stride = rho_stride;
+  a.rho = rho; a.rho_stride = rho_stride;
   a.t = *t;
-  if (d.k == 0) { a.t.dA_eq = nullptr; a.t.db_eq = nullptr; }
-  if (d.m == 0) { a.t.dcons_a = nullptr; a.t.dcons_b = nullptr; }
-  if (a.t.dJ || a.t.dr) {  // the only tangents that read J
-    if (d.m_r <= 0) return fail(MO_ERR_DIMENSION, "J given but the plan was created with m_r = 0");
-    if (prob->J_layout != MO_ROW_MAJOR && prob->J_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad J_layout");
-    const int min_ld = prob->J_layout == MO_ROW_MAJOR ? d.n : d.m_r;
-    if (prob->J_ld < min_ld) return fail(MO_ERR_DIMENSION, "J_ld %d < %d", prob->J_ld, min_ld);
-    if (a.t.dJ && a.t.dJ_ld < min_ld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a.t.dJ_ld, min_ld);
-    a.m_r = d.m_r;
-    a.J = prob->J; a.J_stride = prob->J_stride; a.J_ld = prob->J_ld; a.J_row_major = prob->J_layout == MO_ROW_MAJOR;
-    a.r = a.t.dJ ? prob->r : nullptr; a.r_stride = prob->r_stride;   // (w = J x + r is needed only against dJ)
+  if (int rc = sens_args(plan, prob, batch, vars, vars_stride, &a.t, &a)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  if (a.t.dJ) {   // (in J's layout)
+    const int min_ld = a.J_row_major ? d.n : d.m_r;
+    if (a.t.dJ_ld < min_ld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a.t.dJ_ld, min_ld);
+  } else {
+    a.r = nullptr;   // (w = J x + r is needed only against dJ)
   }
-  if (a.t.dG && a.t.dG_ld < d.n) return fail(MO_ERR_DIMENSION, "dG_ld %d < n %d", a.t.dG_ld, d.n);
-  if (a.t.dA_eq && a.t.dA_ld < d.k) return fail(MO_ERR_DIMENSION, "dA_ld %d < k %d", a.t.dA_ld, d.k);
+  if (int rc = check_dG_dA_ld(d, a.t)) return rc;
   if (d.m > 0 && prob->cons_var) { a.cons_var = prob->cons_var; a.cons_stride = prob->cons_stride; }
   if (mo::qp_tangent_lds_bytes(a, plan->elem) > 64 * 1024)
     return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, m_r = %d: the vectors of one problem exceed the 64 KiB of LDS the tangent kernel uses", d.n, d.k, d.m, a.m_r);

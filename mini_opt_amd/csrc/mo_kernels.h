@@ -214,30 +214,29 @@ bool blocks_grad_fits(int n, int rows, int elem_size);   // the vectors the kern
 hipError_t launch_blocks_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream);
 hipError_t launch_blocks_eq_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream);
 
-// gradients of a loss through the solution of a QP (mo_qp_gradients), qp_grad.hip: rank-2 updates of the state v = [x | s | y | z] and the
-// adjoint u = K^-T g.  Inputs that are not needed for the outputs asked for may be NULL (J, r only for dJ / dr).
-struct GradArgs {
+// what the two dense sensitivity kernels read of the plan and the problem (filled by sens_args of mo_api.hip).  Inputs that are not needed
+// may be NULL: J only for the dJ / dr members (m_r = 0 otherwise), r as each kernel says, cons_var only for the dcons_a member.
+struct SensArgs {
   int n, k, m, m_r;
   long long batch;
   const void* vars; long long vars_stride;   // [batch][V]
-  const void* u; long long u_stride;         // [batch][V]
   const void* J; long long J_stride; int J_ld; int J_row_major;
   const void* r; long long r_stride;
   const int* cons_var; long long cons_stride;
+};
+
+// gradients of a loss through the solution of a QP (mo_qp_gradients), qp_grad.hip: rank-2 updates of the state v = [x | s | y | z] and the
+// adjoint u = K^-T g.  r comes with J.
+struct GradArgs : SensArgs {
   mo_qp_grads out;                           // NULL members are neither computed nor written
+  const void* u; long long u_stride;         // [batch][V]  (behind `out`: the kernel's scalar loads stay closest to the ones it had)
 };
 size_t qp_grad_lds_bytes(const GradArgs& a, int elem_size);
 hipError_t launch_qp_gradients(const GradArgs& a, int dtype, int num_cus, hipStream_t stream);
 
 // forward-mode right-hand side rho = F_theta thetadot of a QP (mo_qp_tangent_rhs), qp_tangent.hip: the transpose of the gradient kernel
-// above.  J, r are read only for the dJ / dr tangents (m_r = 0 otherwise), cons_var only when the problem has one.
-struct TangentArgs {
-  int n, k, m, m_r;
-  long long batch;
-  const void* vars; long long vars_stride;   // [batch][V]
-  const void* J; long long J_stride; int J_ld; int J_row_major;
-  const void* r; long long r_stride;
-  const int* cons_var; long long cons_stride;
+// above.  r is read only against the dJ tangent, cons_var whenever the problem has one.
+struct TangentArgs : SensArgs {
   mo_qp_tangents t;                          // NULL members are zero tangents
   void* rho; long long rho_stride;           // [batch][V]
 };

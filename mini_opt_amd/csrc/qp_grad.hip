@@ -6,21 +6,11 @@
 // Pure data movement.  One workgroup takes one problem at a time: the vectors go to LDS, the two products with J read J ONCE, in its stored
 // layout, 16 bytes per lane, and every matrix output is a rank-2 update written 16 bytes per lane along its contiguous dimension, a whole
 // line per group of lanes.  Every output element has one owner and a fixed order of operations: no atomics, the same bits on every launch.
-#include "mo_kernels.h"
+// kThreads, Vec<T>, group_sum, pad16, vec_ok and grid_for are those of every sensitivity kernel: mo_sens_device.h.
+#include "mo_sens_device.h"
 
 namespace mo {
 namespace {
-
-constexpr int kThreads = 256;
-
-template <typename T> struct Vec;
-template <> struct Vec<double> { using type = double2; static constexpr int N = 2; };
-template <> struct Vec<float> { using type = float4; static constexpr int N = 4; };
-
-template <typename T> __device__ __forceinline__ T group_sum(T v, int width) {  // sum over aligned groups of `width` lanes (a power of two)
-  for (int off = width >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // out[c * ld + r] = s1 a1[r] b1[c] + s2 a2[r] b2[c] for r < R (the contiguous dimension), c < C.  The two products are rounded before they
 // are added (no contraction): with a1 = b2, a2 = b1 and s1 = s2 the element (r, c) and the element (c, r) are the same sum of the same two
@@ -69,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void qp_grad_kernel(const GradArgs a, con
   using V = typename Vec<T>::type;
   const int n = a.n, k = a.k, m = a.m, m_r = a.J ? a.m_r : 0;
   // every vector starts on a 16-byte boundary
-  const int n_p = (n + VN - 1) / VN * VN, k_p = (k + VN - 1) / VN * VN, m_p = (m + VN - 1) / VN * VN, r_p = (m_r + VN - 1) / VN * VN;
+  const int n_p = pad16<VN>(n), k_p = pad16<VN>(k), m_p = pad16<VN>(m), r_p = pad16<VN>(m_r);
   T* x = reinterpret_cast<T*>(smem);
   T* ux = x + n_p;
   T* y = ux + n_p;
@@ -191,31 +181,25 @@ __global__ __launch_bounds__(kThreads) void qp_grad_kernel(const GradArgs a, con
   }
 }
 
-// 16-byte accesses to a per-problem matrix: base, leading dimension and problem stride all multiples of 16 bytes
-bool vec_ok(const void* base, long long stride, int ld, int elem) {
-  const int vn = 16 / elem;
-  return base && ((uintptr_t)base & 15) == 0 && stride % vn == 0 && ld % vn == 0;
+template <typename T> size_t lds_bytes(const GradArgs& a) {
+  auto pad = [](int v) { return pad16<Vec<T>::N>((size_t)v); };
+  return (2 * pad(a.n) + 2 * pad(a.k) + 2 * pad(a.m) + 2 * pad(a.J ? a.m_r : 0)) * sizeof(T);
 }
 
 }  // namespace
 
-size_t qp_grad_lds_bytes(const GradArgs& a, int elem_size) {
-  const size_t vn = 16 / elem_size;
-  auto pad = [&](int v) { return ((size_t)v + vn - 1) / vn * vn; };
-  return (2 * pad(a.n) + 2 * pad(a.k) + 2 * pad(a.m) + 2 * pad(a.J ? a.m_r : 0)) * elem_size;
-}
+size_t qp_grad_lds_bytes(const GradArgs& a, int elem_size) { return elem_size == 8 ? lds_bytes<double>(a) : lds_bytes<float>(a); }
 
 hipError_t launch_qp_gradients(const GradArgs& a, int dtype, int num_cus, hipStream_t stream) {
   if (a.batch <= 0) return hipSuccess;
   const int elem = dtype == MO_F64 ? 8 : 4;
   const size_t lds = qp_grad_lds_bytes(a, elem);
   if (lds > 64 * 1024) return hipErrorInvalidValue;   // (mo_qp_gradients refuses such shapes with its own message)
-  long long grid = (long long)num_cus * 8;            // eight resident workgroups per CU (eight waves per SIMD) keep enough loads in flight
-  if (grid > a.batch) grid = a.batch;
+  const unsigned grid = grid_for(a.batch, num_cus, 0);   // eight resident workgroups per CU, whatever the LDS
   const int vJ = vec_ok(a.J, a.J_stride, a.J_ld, elem), vdJ = vec_ok(a.out.dJ, a.out.dJ_stride, a.out.dJ_ld, elem);
   const int vdG = vec_ok(a.out.dG, a.out.dG_stride, a.out.dG_ld, elem), vdA = vec_ok(a.out.dA_eq, a.out.dA_stride, a.out.dA_ld, elem);
-  if (dtype == MO_F64) hipLaunchKernelGGL(qp_grad_kernel<double>, dim3((unsigned)grid), dim3(kThreads), lds, stream, a, vJ, vdJ, vdG, vdA);
-  else hipLaunchKernelGGL(qp_grad_kernel<float>, dim3((unsigned)grid), dim3(kThreads), lds, stream, a, vJ, vdJ, vdG, vdA);
+  if (dtype == MO_F64) hipLaunchKernelGGL(qp_grad_kernel<double>, dim3(grid), dim3(kThreads), lds, stream, a, vJ, vdJ, vdG, vdA);
+  else hipLaunchKernelGGL(qp_grad_kernel<float>, dim3(grid), dim3(kThreads), lds, stream, a, vJ, vdJ, vdG, vdA);
   return hipGetLastError();
 }
 

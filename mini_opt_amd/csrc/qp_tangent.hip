@@ -9,21 +9,12 @@
 // 16 bytes of the contiguous dimension, row groups leave partial sums in LDS that ONE lane adds in a fixed order).  J and dJ are read twice
 // per problem, first for the row products (w, tdot), then for the column products; the second pass finds them in the cache hierarchy.
 // Every element of rho has one owner and a fixed order of operations: no atomics, the same bits on every launch.
-#include "mo_kernels.h"
+// kThreads, Vec<T>, group_sum, pad16, vec_ok, grid_for and the constraint rows of rho (cons_rows_load / _scatter / _write, shared with
+// qp_tangent_blocks.hip; here with the unit's contraction: one FMA per row of rho_pi) are in mo_sens_device.h.
+#include "mo_sens_device.h"
 
 namespace mo {
 namespace {
-
-constexpr int kThreads = 256;
-
-template <typename T> struct Vec;
-template <> struct Vec<double> { using type = double2; static constexpr int N = 2; };
-template <> struct Vec<float> { using type = float4; static constexpr int N = 4; };
-
-template <typename T> __device__ __forceinline__ T group_sum(T v, int width) {  // sum over aligned groups of `width` lanes (a power of two)
-  for (int off = width >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // Which elements (l, c) of a column-major matrix (l: the contiguous index, c: the vector) take part: all of it, the lower triangle with its
 // diagonal, or the strict lower triangle.  An element that takes no part is never multiplied: it may be NaN.
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void qp_tangent_kernel(const TangentArgs 
   constexpr int VN = Vec<T>::N;
   const int n = a.n, k = a.k, m = a.m, m_r = a.J ? a.m_r : 0;
   // every vector starts on a 16-byte boundary
-  const int n_p = (n + VN - 1) / VN * VN, k_p = (k + VN - 1) / VN * VN, m_p = (m + VN - 1) / VN * VN, r_p = (m_r + VN - 1) / VN * VN;
+  const int n_p = pad16<VN>(n), k_p = pad16<VN>(k), m_p = pad16<VN>(m), r_p = pad16<VN>(m_r);
   T* x = reinterpret_cast<T*>(smem);
   T* y = x + n_p;
   T* az = y + k_p;     // dcons_a[i] z_i
@@ -183,12 +174,7 @@ __global__ __launch_bounds__(kThreads) void qp_tangent_kernel(const TangentArgs 
       const T* db = t.db_eq ? (const T*)t.db_eq + p * t.db_stride : nullptr;
       for (int i = tid; i < k; i += kThreads) { y[i] = vp[n + m + i]; pe[i] = db ? db[i] : (T)0; }
     }
-    for (int i = tid; i < m; i += kThreads) {
-      int v = cvp ? cvp[i] : 0;
-      if (v < 0 || v >= n) v = -1;   // F_ASSERT qp.cc:70-72: never an index
-      cv[i] = v;
-      az[i] = dca ? dca[i] * vp[n + m + k + i] : (T)0;
-    }
+    cons_rows_load(cv, az, cvp, dca, vp, n + m + k, n, m, tid);
     if (m_r > 0) {
       const T* rp = a.r ? (const T*)a.r + p * a.r_stride : nullptr;
       const T* dr = t.dr ? (const T*)t.dr + p * t.dr_stride : nullptr;
@@ -235,50 +221,34 @@ __global__ __launch_bounds__(kThreads) void qp_tangent_kernel(const TangentArgs 
     }
     // rho_d[var_i] -= dcons_a[i] z_i: the owner of variable j walks the rows in their order, however many name j
     if (cons) {
-      for (int j = tid; j < n; j += kThreads) {
-        T s = rd[j];
-        for (int i = 0; i < m; ++i)
-          if (cv[i] == j) s -= az[i];
-        rd[j] = s;
-      }
+      cons_rows_scatter(rd, cv, az, n, m, tid);
       __syncthreads();
     }
     for (int i = tid; i < n; i += kThreads) rho[i] = rd[i];
-    for (int i = tid; i < m; i += kThreads) {
-      rho[n + i] = (T)0;
-      const int v = cv[i];
-      const T b = dcb ? dcb[i] : (T)0;
-      rho[n + m + k + i] = v < 0 ? (T)__builtin_nan("") : (dca ? dca[i] * x[v] + b : b);
-    }
+    cons_rows_write<T, true>(rho, n, n + m + k, cv, dca, dcb, x, m, tid);   // (one FMA per row: the unit's contraction)
     for (int i = tid; i < k; i += kThreads) rho[n + m + i] = pe[i];
   }
 }
 
-// 16-byte accesses to a per-problem matrix: base, leading dimension and problem stride all multiples of 16 bytes
-bool vec_ok(const void* base, long long stride, int ld, int elem) {
-  const int vn = 16 / elem;
-  return base && ((uintptr_t)base & 15) == 0 && stride % vn == 0 && ld % vn == 0;
+template <typename T> size_t lds_bytes(const TangentArgs& a) {
+  auto pad = [](int v) { return pad16<Vec<T>::N>((size_t)v); };
+  return (2 * pad(a.n) + 2 * pad(a.k) + pad(a.m) + 2 * pad(a.J ? a.m_r : 0) + kThreads * Vec<T>::N) * sizeof(T) + (size_t)a.m * sizeof(int);
 }
 
 }  // namespace
 
-size_t qp_tangent_lds_bytes(const TangentArgs& a, int elem_size) {
-  const size_t vn = 16 / elem_size;
-  auto pad = [&](int v) { return ((size_t)v + vn - 1) / vn * vn; };
-  return (2 * pad(a.n) + 2 * pad(a.k) + pad(a.m) + 2 * pad(a.J ? a.m_r : 0) + kThreads * vn) * elem_size + (size_t)a.m * sizeof(int);
-}
+size_t qp_tangent_lds_bytes(const TangentArgs& a, int elem_size) { return elem_size == 8 ? lds_bytes<double>(a) : lds_bytes<float>(a); }
 
 hipError_t launch_qp_tangent(const TangentArgs& a, int dtype, int num_cus, hipStream_t stream) {
   if (a.batch <= 0) return hipSuccess;
   const int elem = dtype == MO_F64 ? 8 : 4;
   const size_t lds = qp_tangent_lds_bytes(a, elem);
   if (lds > 64 * 1024) return hipErrorInvalidValue;   // (mo_qp_tangent_rhs refuses such shapes with its own message)
-  long long grid = (long long)num_cus * 8;            // eight resident workgroups per CU, as the gradient kernel
-  if (grid > a.batch) grid = a.batch;
+  const unsigned grid = grid_for(a.batch, num_cus, 0);   // eight resident workgroups per CU, as the gradient kernel
   const int vJ = vec_ok(a.J, a.J_stride, a.J_ld, elem), vdJ = vec_ok(a.t.dJ, a.t.dJ_stride, a.t.dJ_ld, elem);
   const int vdG = vec_ok(a.t.dG, a.t.dG_stride, a.t.dG_ld, elem), vdA = vec_ok(a.t.dA_eq, a.t.dA_stride, a.t.dA_ld, elem);
-  if (dtype == MO_F64) hipLaunchKernelGGL(qp_tangent_kernel<double>, dim3((unsigned)grid), dim3(kThreads), lds, stream, a, vJ, vdJ, vdG, vdA);
-  else hipLaunchKernelGGL(qp_tangent_kernel<float>, dim3((unsigned)grid), dim3(kThreads), lds, stream, a, vJ, vdJ, vdG, vdA);
+  if (dtype == MO_F64) hipLaunchKernelGGL(qp_tangent_kernel<double>, dim3(grid), dim3(kThreads), lds, stream, a, vJ, vdJ, vdG, vdA);
+  else hipLaunchKernelGGL(qp_tangent_kernel<float>, dim3(grid), dim3(kThreads), lds, stream, a, vJ, vdJ, vdG, vdA);
   return hipGetLastError();
 }
 

@@ -12,23 +12,17 @@
 // equality layout), lane l taking the entries l, l + kW, ...; the partial sums are added in a shuffle tree of fixed shape.  Phase 4: the owner
 // of rho_pe[row] walks the winners among its block's columns.  Phase 5: the owner of variable j walks the constraint rows in order.  Phase 6:
 // rho is written once, V contiguous values.  Every element has one owner and a fixed order of operations, every product is rounded before
-// it is added: no atomics, the same bits on every launch.
+// it is added: no atomics, the same bits on every launch.  Phases 1, 5 and 6 share their constraint rows with qp_tangent.hip (cons_rows_load /
+// _scatter / _write of mo_sens_device.h, here with kContract = false); kThreads, group_sum and grid_for come from there as well.
 #include <stdlib.h>
 
-#include "mo_kernels.h"
+#include "mo_sens_device.h"
 
 namespace mo {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr size_t kStageBudget = 48 * 1024;  // per workgroup: above it the packed values and tangents are read straight from global memory
 constexpr size_t kTangentLds = 64 * 1024;   // the vectors the kernel always keeps in LDS and, staged, the values on top
-
-// sum over aligned groups of `width` lanes (a power of two <= 64): the same tree on every launch
-template <typename T> __device__ __forceinline__ T group_sum(T v, int width) {
-  for (int off = width >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <typename T, bool kStaged>
 __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTangentArgs a, const int width) {
@@ -89,12 +83,7 @@ __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTan
       const T* dre = t.dr_eq ? (const T*)t.dr_eq + p * t.dr_eq_stride : nullptr;
       for (int i = tid; i < k; i += kThreads) { sy[i] = vp[n + m + i]; spe[i] = dre ? dre[i] : (T)0; }
     }
-    for (int i = tid; i < m; i += kThreads) {
-      int v = cvp ? cvp[i] : 0;
-      if (v < 0 || v >= n) v = -1;   // F_ASSERT qp.cc:70-72: never an index
-      scv[i] = v;
-      saz[i] = dca ? dca[i] * vp[n + m + k + i] : (T)0;
-    }
+    cons_rows_load(scv, saz, cvp, dca, vp, n + m + k, n, m, tid);
     if (kStaged && cost) {
       for (long long i = tid; i < a.values; i += kThreads) sJ[i] = Jv[i];
       Jv = sJ;
@@ -207,41 +196,14 @@ __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTan
     __syncthreads();
     // phase 5: rho_d[var_i] -= dcons_a[i] z_i: the owner of variable j walks the rows in their order, however many name j
     if (cons) {
-      for (int j = tid; j < n; j += kThreads) {
-        T s = srd[j];
-        for (int i = 0; i < m; ++i)
-          if (scv[i] == j) s -= saz[i];
-        srd[j] = s;
-      }
+      cons_rows_scatter(srd, scv, saz, n, m, tid);
       __syncthreads();
     }
     // phase 6
     for (int i = tid; i < n; i += kThreads) rho[i] = srd[i];
-    for (int i = tid; i < m; i += kThreads) {
-      rho[n + i] = (T)0;
-      const int v = scv[i];
-      const T b = dcb ? dcb[i] : (T)0;
-      T out = b;
-      if (dca) {
-        const T pa = dca[i] * sx[v < 0 ? 0 : v];
-        out = pa + b;
-      }
-      rho[n + m + k + i] = v < 0 ? (T)__builtin_nan("") : out;
-    }
+    cons_rows_write<T, false>(rho, n, n + m + k, scv, dca, dcb, sx, m, tid);   // (the product rounded before the sum, as everywhere here)
     for (int i = tid; i < k; i += kThreads) rho[n + m + i] = spe[i];
   }
-}
-
-// a workgroup per problem in turn: as many resident workgroups as the LDS allows, at most eight per CU (grid_for of residual_blocks.hip)
-unsigned grid_for(long long batch, int num_cus, size_t lds_bytes) {
-  long long per_cu = 8;
-  if (lds_bytes > 0) {
-    const long long fit = (long long)((160 * 1024) / (lds_bytes + 64));
-    per_cu = fit < per_cu ? (fit < 1 ? 1 : fit) : per_cu;
-  }
-  long long g = (long long)num_cus * per_cu;
-  if (g > batch) g = batch;
-  return (unsigned)(g < 1 ? 1 : g);
 }
 
 // lanes per variable in phase 3: the largest power of two that keeps the whole workgroup busy in one pass, at most 16 (the lists are short)

@@ -8,12 +8,12 @@
 // in the reference's order (blocks in order, then row_local / col_local).  A lane owns one cell at a time and sums its list in that order,
 // so there are no atomics, no G accumulator and the result is the same on every launch.  The schedule is shared by the batch: it stays in
 // L2 while the workgroups stream their problems' packed J and r (through LDS when they fit) and write whole lines of G.
-#include "mo_kernels.h"
+// kThreads and grid_for (the grid of the persistent workgroups) are those of every sensitivity kernel: mo_sens_device.h.
+#include "mo_sens_device.h"
 
 namespace mo {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr size_t kStageBudget = 48 * 1024;  // per workgroup: above it the packed values are read straight from global memory
 constexpr size_t kGradLds = 63 * 1024;      // blocks_grad_kernel: the vectors it always keeps in LDS (x, u_x, t, w) and, staged, the values on top
 
@@ -228,18 +228,6 @@ __global__ __launch_bounds__(kThreads) void blocks_eq_grad_kernel(const BlockGra
       for (int i = tid; i < a.rows; i += kThreads) dr[i] = -up[yo + i];
     }
   }
-}
-
-// a workgroup per problem in turn: as many resident workgroups as the LDS allows, at most eight per CU (eight waves per SIMD)
-unsigned grid_for(long long batch, int num_cus, size_t lds_bytes) {
-  long long per_cu = 8;
-  if (lds_bytes > 0) {
-    const long long fit = (long long)((160 * 1024) / (lds_bytes + 64));
-    per_cu = fit < per_cu ? (fit < 1 ? 1 : fit) : per_cu;
-  }
-  long long g = (long long)num_cus * per_cu;
-  if (g > batch) g = batch;
-  return (unsigned)(g < 1 ? 1 : g);
 }
 
 template <typename T> hipError_t launch_linearize_t(const BlocksArgs& a, int num_cus, hipStream_t stream) {

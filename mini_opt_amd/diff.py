@@ -49,19 +49,55 @@ def clear_plan_cache() -> None:
     _PLANS.clear()
 
 
-def _check_state(problem: BatchedQP, t: torch.Tensor, name: str) -> int:
-    if t.dim() != 2 or int(t.shape[1]) != problem.V or not t.is_contiguous() or t.dtype != problem.dtype or t.device != problem.device:
-        raise ValueError(f"{name}: expected a contiguous [B, {problem.V}] {problem.dtype} tensor on {problem.device}, got {tuple(t.shape)} {t.dtype}")
+def _check_state(t: torch.Tensor, name: str, V: int, like) -> int:
+    """The one check of a [B, V] state-sized tensor (vars, rhs, u); `like` carries the dtype and device (a BatchedQP or a ResidualLayout)."""
+    if t.dim() != 2 or int(t.shape[1]) != V or not t.is_contiguous() or t.dtype != like.dtype or t.device != like.device:
+        raise ValueError(f"{name}: expected a contiguous [B, {V}] {like.dtype} tensor on {like.device}, got {tuple(t.shape)} {t.dtype}")
     return int(t.shape[0])
+
+
+def _check_state_pair(vars: torch.Tensor, other: torch.Tensor, name: str, V: int, like) -> int:
+    B = _check_state(vars, "vars", V, like)
+    if _check_state(other, name, V, like) != B:
+        raise ValueError(f"vars and {name} must have the same batch")
+    return B
+
+
+def _take(x: Optional[torch.Tensor], name: str, tail, B: int, dtype, device, keep: list):
+    """(pointer, problem stride) of an input [B or 1, *tail]; stride 0 -- one direction or value shared by the batch -- iff the leading
+    dimension is 1 and B is not.  `keep` holds the tensor until the launch."""
+    if (x is None or x.dim() != 1 + len(tail) or tuple(int(d) for d in x.shape[1:]) != tuple(tail) or int(x.shape[0]) not in (1, B)
+            or not x.is_contiguous() or x.dtype != dtype or x.device != device):
+        got = "None" if x is None else f"{tuple(x.shape)} {x.dtype}"
+        raise ValueError(f"{name}: expected a contiguous [{B} or 1, {', '.join(map(str, tail))}] {dtype} tensor on {device}, got {got}")
+    keep.append(x)
+    per = 1
+    for d in tail:
+        per *= int(d)
+    return _ptr(x), (0 if int(x.shape[0]) == 1 and B != 1 else per)
+
+
+def _check_names(names, kind: str, allowed, no_rows=(), other_level=()) -> None:
+    """The names of a `want` list or a tangent dict (kind: "gradient" or "tangent"): known, of rows the problem has, of its input level."""
+    for w in names:
+        if w not in allowed:
+            raise ValueError(f"unknown {kind} {w!r}: one of {allowed}")
+        if w in no_rows:
+            raise ValueError(f"{kind} {w!r} of a problem without such rows")
+        if w in other_level:
+            raise ValueError(f"{kind} {w!r} does not belong to this problem's input level ((J, r, lam) or (G, c))")
+
+
+def _check_dense_names(problem: BatchedQP, names, kind: str) -> None:
+    no_rows = (("A_eq", "b_eq") if problem.k == 0 else ()) + (("cons_a", "cons_b") if problem.m == 0 else ())
+    _check_names(names, kind, GRADIENTS, no_rows, ("G",) if problem.J is not None else ("J", "r", "lam"))
 
 
 def kkt_solve(problem: BatchedQP, vars: torch.Tensor, rhs: torch.Tensor, transpose: bool = False, include_inequalities: bool = True):
     """mo_kkt_solve: factorise the KKT matrix K of every problem at `vars` [B, V] (s > 0 required) and solve for `rhs` [B, V].
     transpose=False: out = delta with K delta = -rhs (SolveForUpdate with r_ := rhs, mu = 0); transpose=True: out = u with K^T u = rhs.
     Returns (out [B, V], status [B] int32 MO_STATUS_*); out is NaN for problems whose status is not OK."""
-    B = _check_state(problem, vars, "vars")
-    if _check_state(problem, rhs, "rhs") != B:
-        raise ValueError("vars and rhs must have the same batch")
+    B = _check_state_pair(vars, rhs, "rhs", problem.V, problem)
     out = torch.empty_like(vars)
     status = torch.empty(B, dtype=torch.int32, device=vars.device)
     flags = (L.MO_KKT_TRANSPOSE if transpose else 0) | (0 if include_inequalities else L.MO_STEP_NO_INEQUALITIES)
@@ -84,21 +120,13 @@ def qp_gradients(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor, want: 
       "c" [B, n]    "G" [B, n, n] (symmetric)    "A_eq" [B, n, k]    "b_eq" [B, k]    "cons_a", "cons_b" [B, m]
       "J" (the shape and layout of problem.J)    "r" [B, m_r]    "lam" [B]
     "G" is the gradient with respect to a symmetric G; "G" with J-level input and "J" / "r" / "lam" with (G, c) input raise."""
-    B = _check_state(problem, vars, "vars")
-    if _check_state(problem, u, "u") != B:
-        raise ValueError("vars and u must have the same batch")
+    B = _check_state_pair(vars, u, "u", problem.V, problem)
     n, k, m = problem.n, problem.k, problem.m
     j_level = problem.J is not None
     if want is None:
         want = (("J", "r", "lam") if j_level else ("G", "c")) + (("A_eq", "b_eq") if k else ()) + (("cons_a", "cons_b") if m else ())
     want = tuple(want)
-    for w in want:
-        if w not in GRADIENTS:
-            raise ValueError(f"unknown gradient {w!r}: one of {GRADIENTS}")
-        if (w in ("A_eq", "b_eq") and k == 0) or (w in ("cons_a", "cons_b") and m == 0):
-            raise ValueError(f"gradient {w!r} of a problem without such rows")
-        if (w == "G" and j_level) or (w in ("J", "r", "lam") and not j_level):
-            raise ValueError(f"gradient {w!r} does not belong to this problem's input level ((J, r, lam) or (G, c))")
+    _check_dense_names(problem, want, "gradient")
     dt, dev = problem.dtype, problem.device
     new = lambda *shape: torch.empty(*shape, dtype=dt, device=dev)
     out: Dict[str, torch.Tensor] = {}
@@ -146,31 +174,12 @@ def qp_tangent_rhs(problem: BatchedQP, vars: torch.Tensor, tangents: Dict[str, t
     layouts qp_gradients returns): "c" [B, n], "G" [B, n, n] (LOWER triangle read as a symmetric matrix, the rest ignored), "A_eq" [B, n, k],
     "b_eq" [B, k], "cons_a", "cons_b" [B, m], "J" in the layout of problem.J (its own leading dimension allowed), "r" [B, m_r], "lam" [B].
     A missing key is a zero tangent; a leading dimension of 1 is one direction shared by the batch."""
-    B = _check_state(problem, vars, "vars")
+    B = _check_state(vars, "vars", problem.V, problem)
     n, k, m = problem.n, problem.k, problem.m
-    j_level = problem.J is not None
     t = L.QPTangents()
     keep = []
-
-    def take(name, tail):
-        x = tangents[name]
-        if (x.dim() != 1 + len(tail) or tuple(int(d) for d in x.shape[1:]) != tuple(tail) or int(x.shape[0]) not in (1, B) or not x.is_contiguous()
-                or x.dtype != problem.dtype or x.device != problem.device):
-            raise ValueError(f"tangent {name!r}: expected a contiguous [{B} or 1, {', '.join(map(str, tail))}] {problem.dtype} tensor on "
-                             f"{problem.device}, got {tuple(x.shape)} {x.dtype}")
-        keep.append(x)
-        per = 1
-        for d in tail:
-            per *= int(d)
-        return _ptr(x), (0 if int(x.shape[0]) == 1 and B != 1 else per)
-
-    for w in tangents:
-        if w not in GRADIENTS:
-            raise ValueError(f"unknown tangent {w!r}: one of {GRADIENTS}")
-        if (w in ("A_eq", "b_eq") and k == 0) or (w in ("cons_a", "cons_b") and m == 0):
-            raise ValueError(f"tangent {w!r} of a problem without such rows")
-        if (w == "G" and j_level) or (w in ("J", "r", "lam") and not j_level):
-            raise ValueError(f"tangent {w!r} does not belong to this problem's input level ((J, r, lam) or (G, c))")
+    take = lambda name, tail: _take(tangents[name], f"tangent {name!r}", tail, B, problem.dtype, problem.device, keep)
+    _check_dense_names(problem, tangents, "tangent")
     if "G" in tangents:
         t.dG, t.dG_stride = take("G", (n, n))
         t.dG_ld = n
@@ -212,6 +221,56 @@ def qp_jvp(problem: BatchedQP, vars: torch.Tensor, tangents: Dict[str, torch.Ten
     return kkt_solve(problem, vars, qp_tangent_rhs(problem, vars, tangents), transpose=False)
 
 
+_PENDING_TANGENT_STATUS: Optional[torch.Tensor] = None   # from a Function's jvp to solve_qp, which hangs it on the tensors it returns
+
+
+def _masked(t: Optional[torch.Tensor], ok: torch.Tensor) -> Optional[torch.Tensor]:
+    """The zero-masking rule: a problem whose forward status or adjoint / tangent-solve status is not MO_STATUS_OK gets ZERO."""
+    if t is None:
+        return None
+    return torch.where(ok.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros((), dtype=t.dtype, device=t.device))
+
+
+def _solve_forward(ctx, problem: BatchedQP, B: int, params: Params):
+    """The forward of both Functions: mo_qp_solve from a zero state; what backward and jvp need goes on ctx."""
+    dev = problem.device
+    v = torch.zeros(B, problem.V, dtype=problem.dtype, device=dev)
+    term = torch.empty(B, dtype=torch.int32, device=dev)
+    nit = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    prob, sp = problem.as_struct(), params.as_struct()
+    L.check(L.lib().mo_qp_solve(plan_for(problem, B), C.byref(prob), B, C.byref(sp), _ptr(v), problem.V, _ptr(term), _ptr(nit), None, None,
+                                _ptr(status), _stream()))
+    ctx.problem, ctx.v, ctx.status = problem, v, status
+    ctx.adjoint_status = None
+    ctx.tangent_status = None
+    ctx.termination_state, ctx.num_iterations = term, nit
+    ctx.mark_non_differentiable(status)
+    ctx.set_materialize_grads(False)   # jvp: an input without a tangent arrives as None, not as a tensor of zeros to be read
+    return v.clone(), status
+
+
+def _adjoint(ctx, g):
+    """The backward of both Functions begins here: K(v)^T u = g once; returns (problem, v, u, ok [B]: forward and adjoint status OK)."""
+    problem, v = ctx.problem, ctx.v
+    if g is None:
+        g = torch.zeros_like(v)
+    u, adj = kkt_solve(problem, v, g.contiguous(), transpose=True)
+    ctx.adjoint_status = adj
+    return problem, v, u, (ctx.status == L.MO_STATUS_OK) & (adj == L.MO_STATUS_OK)
+
+
+def _given(names, tangents) -> Dict[str, torch.Tensor]:
+    return {nm: t.detach().contiguous() for nm, t in zip(names, tangents) if t is not None}
+
+
+def _jvp_result(ctx, vdot, st):
+    """The jvp of both Functions ends here: the solve's status words are kept and handed to solve_qp, failed problems get a zero tangent."""
+    global _PENDING_TANGENT_STATUS
+    ctx.tangent_status = _PENDING_TANGENT_STATUS = st
+    return _masked(vdot, (ctx.status == L.MO_STATUS_OK) & (st == L.MO_STATUS_OK)), None
+
+
 class QPSolveFunction(torch.autograd.Function):
     """v*(theta) = QPInteriorPointSolver::Solve with the adjoint of the KKT conditions as its backward.
 
@@ -230,41 +289,14 @@ class QPSolveFunction(torch.autograd.Function):
         m = 0 if cons_a is None else int(cons_a.shape[1])
         problem = BatchedQP(n=n, k=k, m=m, J=det(J), r=det(r), lam=0.0, lam_vec=det(lam), G=det(G), c=det(c), A_eq=det(A_eq), b_eq=det(b_eq),
                             cons_var=cons_var, cons_a=det(cons_a), cons_b=det(cons_b))
-        B = int(ref.shape[0])
-        dev, dt = ref.device, ref.dtype
-        v = torch.zeros(B, problem.V, dtype=dt, device=dev)
-        term = torch.empty(B, dtype=torch.int32, device=dev)
-        nit = torch.empty(B, dtype=torch.int32, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        prob, sp = problem.as_struct(), params.as_struct()
-        L.check(L.lib().mo_qp_solve(plan_for(problem, B), C.byref(prob), B, C.byref(sp), _ptr(v), problem.V, _ptr(term), _ptr(nit), None, None,
-                                    _ptr(status), _stream()))
-        ctx.problem, ctx.v, ctx.status = problem, v, status
-        ctx.adjoint_status = None
-        ctx.tangent_status = None
-        ctx.termination_state, ctx.num_iterations = term, nit
-        ctx.mark_non_differentiable(status)
-        ctx.set_materialize_grads(False)   # jvp: an input without a tangent arrives as None, not as a tensor of zeros to be read
-        return v.clone(), status
+        return _solve_forward(ctx, problem, int(ref.shape[0]), params)
 
     @staticmethod
     def backward(ctx, g, _g_status):
-        problem, v = ctx.problem, ctx.v
-        if g is None:
-            g = torch.zeros_like(v)
-        u, adj = kkt_solve(problem, v, g.contiguous(), transpose=True)
-        ctx.adjoint_status = adj
-        names = ("G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b")
-        want = [nm for nm, need in zip(names, ctx.needs_input_grad[:9]) if need]
+        problem, v, u, ok = _adjoint(ctx, g)
+        want = [nm for nm, need in zip(GRADIENTS, ctx.needs_input_grad[:9]) if need]
         grads = qp_gradients(problem, v, u, want) if want else {}
-        ok = (ctx.status == L.MO_STATUS_OK) & (adj == L.MO_STATUS_OK)
-        out = []
-        for nm in names:
-            t = grads.get(nm)
-            if t is not None:
-                t = torch.where(ok.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros((), dtype=t.dtype, device=t.device))
-            out.append(t)
-        return (*out, None, None)
+        return (*[_masked(grads.get(nm), ok) for nm in GRADIENTS], None, None)
 
     @staticmethod
     def jvp(ctx, dG, dc, dJ, dr, dlam, dA_eq, db_eq, dcons_a, dcons_b, _dcons_var, _dparams):
@@ -272,19 +304,10 @@ class QPSolveFunction(torch.autograd.Function):
         passed as 1/2 (Gdot + Gdot^T), so the JVP is the exact transpose of the backward for any Gdot.  A problem whose forward status or
         tangent-solve status is not MO_STATUS_OK gets a ZERO tangent (the backward's rule); the solve's status words are kept
         (`tangent_status`)."""
-        global _PENDING_TANGENT_STATUS
-        problem, v = ctx.problem, ctx.v
         if dG is not None:
             dG = 0.5 * (dG + dG.transpose(1, 2))
-        given = zip(GRADIENTS, (dG, dc, dJ, dr, dlam, dA_eq, db_eq, dcons_a, dcons_b))
-        tangents = {nm: t.detach().contiguous() for nm, t in given if t is not None}
-        vdot, st = qp_jvp(problem, v, tangents)
-        ctx.tangent_status = _PENDING_TANGENT_STATUS = st
-        ok = (ctx.status == L.MO_STATUS_OK) & (st == L.MO_STATUS_OK)
-        return _masked(vdot, ok), None
-
-
-_PENDING_TANGENT_STATUS: Optional[torch.Tensor] = None   # from QPSolveFunction.jvp to solve_qp, which hangs it on the tensors it returns
+        tangents = _given(GRADIENTS, (dG, dc, dJ, dr, dlam, dA_eq, db_eq, dcons_a, dcons_b))
+        return _jvp_result(ctx, *qp_jvp(ctx.problem, ctx.v, tangents))
 
 
 def tangent_status(t: torch.Tensor) -> Optional[torch.Tensor]:
@@ -298,16 +321,6 @@ def tangent_status(t: torch.Tensor) -> Optional[torch.Tensor]:
     return None
 
 
-def _check_vu(layout: ResidualLayout, vars: torch.Tensor, u: torch.Tensor, k: int, m: int) -> int:
-    V = layout.n + 2 * int(m) + int(k)
-    for t, name in ((vars, "vars"), (u, "u")):
-        if t.dim() != 2 or int(t.shape[1]) != V or not t.is_contiguous() or t.dtype != layout.dtype or t.device != layout.device:
-            raise ValueError(f"{name}: expected a contiguous [B, {V}] {layout.dtype} tensor on {layout.device}, got {tuple(t.shape)} {t.dtype}")
-    if vars.shape[0] != u.shape[0]:
-        raise ValueError("vars and u must have the same batch")
-    return int(vars.shape[0])
-
-
 def qp_gradients_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, vars: torch.Tensor, u: torch.Tensor, k: int = 0,
                         m: int = 0, want: Iterable[str] = ("J_blocks", "r", "lam")) -> Dict[str, torch.Tensor]:
     """mo_qp_gradients_blocks: gradients of a loss with respect to the packed cost blocks of `layout` (the inputs of linearize_blocks) from the
@@ -315,13 +328,11 @@ def qp_gradients_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch
     inequality rows (V = n + 2 m + k).  J_blocks [B or 1, values], r [B or 1, rows] (1: shared by the batch; the outputs are per problem).
     Returns the ones named in `want`: "J_blocks" [B, values] (the packing of J_blocks), "r" [B, rows], "lam" [B]."""
     want = tuple(want)
-    for w in want:
-        if w not in ("J_blocks", "r", "lam"):
-            raise ValueError(f"unknown gradient {w!r}: one of ('J_blocks', 'r', 'lam')")
-    B = _check_vu(layout, vars, u, k, m)
-    for t, w, name in ((J_blocks, layout.values, "J_blocks"), (r, layout.rows, "r")):
-        if t.dim() != 2 or int(t.shape[1]) != w or int(t.shape[0]) not in (1, B) or not t.is_contiguous() or t.dtype != layout.dtype or t.device != layout.device:
-            raise ValueError(f"{name}: expected a contiguous [{B} or 1, {w}] {layout.dtype} tensor on {layout.device}, got {tuple(t.shape)} {t.dtype}")
+    _check_names(want, "gradient", ("J_blocks", "r", "lam"))
+    B = _check_state_pair(vars, u, "u", layout.n + 2 * int(m) + int(k), layout)
+    keep = []
+    J_ptr, J_stride = _take(J_blocks, "J_blocks", (layout.values,), B, layout.dtype, layout.device, keep)
+    r_ptr, r_stride = _take(r, "r", (layout.rows,), B, layout.dtype, layout.device, keep)
     new = lambda *shape: torch.empty(*shape, dtype=layout.dtype, device=layout.device)
     out: Dict[str, torch.Tensor] = {}
     g = L.BlockGrads()
@@ -335,9 +346,8 @@ def qp_gradients_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch
         out["lam"] = new(B)
         g.dlambda, g.dlambda_stride = _ptr(out["lam"]), 1
     plan = _plan_of(layout.n, int(k), int(m), 0, layout.dtype, layout.device, B)
-    L.check(L.lib().mo_qp_gradients_blocks(plan, layout.h, _ptr(J_blocks), 0 if J_blocks.shape[0] == 1 else layout.values, _ptr(r),
-                                           0 if r.shape[0] == 1 else layout.rows, B, _ptr(vars), int(vars.shape[1]), _ptr(u), int(u.shape[1]),
-                                           C.byref(g), _stream()))
+    L.check(L.lib().mo_qp_gradients_blocks(plan, layout.h, J_ptr, J_stride, r_ptr, r_stride, B, _ptr(vars), int(vars.shape[1]), _ptr(u),
+                                           int(u.shape[1]), C.byref(g), _stream()))
     return out
 
 
@@ -346,11 +356,9 @@ def qp_gradients_eq_blocks(eq_layout: ResidualLayout, vars: torch.Tensor, u: tor
     """mo_qp_gradients_eq_blocks: gradients with respect to the packed equality blocks of `eq_layout` (the inputs of jacobian_blocks; k = its
     rows) from `vars`, `u` [B, n + 2 m + k]: "J_eq_blocks" [B, values] (exactly 0 for a column that loses its global column), "r_eq" [B, k]."""
     want = tuple(want)
-    for w in want:
-        if w not in ("J_eq_blocks", "r_eq"):
-            raise ValueError(f"unknown gradient {w!r}: one of ('J_eq_blocks', 'r_eq')")
+    _check_names(want, "gradient", ("J_eq_blocks", "r_eq"))
     k = eq_layout.rows
-    B = _check_vu(eq_layout, vars, u, k, m)
+    B = _check_state_pair(vars, u, "u", eq_layout.n + 2 * int(m) + k, eq_layout)
     out: Dict[str, torch.Tensor] = {}
     if "J_eq_blocks" in want:
         out["J_eq_blocks"] = torch.empty(B, eq_layout.values, dtype=eq_layout.dtype, device=eq_layout.device)
@@ -381,27 +389,11 @@ def qp_tangent_rhs_blocks(layout: ResidualLayout, J_blocks: Optional[torch.Tenso
     n, k, m = layout.n, int(k), int(m)
     V = n + 2 * m + k
     dt, dev = layout.dtype, layout.device
-    if vars.dim() != 2 or int(vars.shape[1]) != V or not vars.is_contiguous() or vars.dtype != dt or vars.device != dev:
-        raise ValueError(f"vars: expected a contiguous [B, {V}] {dt} tensor on {dev}, got {tuple(vars.shape)} {vars.dtype}")
-    B = int(vars.shape[0])
-    for w in tangents:
-        if w not in BLOCK_TANGENTS:
-            raise ValueError(f"unknown tangent {w!r}: one of {BLOCK_TANGENTS}")
-        if (w in ("J_eq_blocks", "r_eq") and (k == 0 or eq_layout is None)) or (w in ("cons_a", "cons_b") and m == 0):
-            raise ValueError(f"tangent {w!r} of a problem without such rows")
+    B = _check_state(vars, "vars", V, layout)
+    no_rows = (("J_eq_blocks", "r_eq") if k == 0 or eq_layout is None else ()) + (("cons_a", "cons_b") if m == 0 else ())
+    _check_names(tangents, "tangent", BLOCK_TANGENTS, no_rows)
     keep = []
-
-    def take(x, name, tail, dtype=dt):
-        if (x is None or x.dim() != 1 + len(tail) or tuple(int(d) for d in x.shape[1:]) != tuple(tail) or int(x.shape[0]) not in (1, B)
-                or not x.is_contiguous() or x.dtype != dtype or x.device != dev):
-            got = "None" if x is None else f"{tuple(x.shape)} {x.dtype}"
-            raise ValueError(f"{name}: expected a contiguous [{B} or 1, {', '.join(map(str, tail))}] {dtype} tensor on {dev}, got {got}")
-        keep.append(x)
-        per = 1
-        for d in tail:
-            per *= int(d)
-        return _ptr(x), (0 if int(x.shape[0]) == 1 and B != 1 else per)
-
+    take = lambda x, name, tail, dtype=dt: _take(x, name, tail, B, dtype, dev, keep)
     t = L.BlockTangents()
     J_ptr = r_ptr = None
     J_stride = r_stride = 0
@@ -448,12 +440,6 @@ def qp_jvp_blocks(problem: BatchedQP, layout: ResidualLayout, J_blocks: torch.Te
     return kkt_solve(problem, vars, rho, transpose=False)
 
 
-def _masked(t: Optional[torch.Tensor], ok: torch.Tensor) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    return torch.where(ok.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros((), dtype=t.dtype, device=t.device))
-
-
 class QPSolveBlocksFunction(torch.autograd.Function):
     """QPSolveFunction for residual-block input.  forward(J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, cons_var, layout, eq_layout,
     params) -> (v, status): linearize_blocks gives (G, c), jacobian_blocks gives A_eq (b_eq = r_eq), mo_qp_solve runs on the (G, c) problem --
@@ -474,31 +460,13 @@ class QPSolveBlocksFunction(torch.autograd.Function):
         if eq_layout is not None:
             A_eq, _ = jacobian_blocks(eq_layout, J_eq_blocks, r_eq)       # [B, n, k]: memory = k x n column-major, BatchedQP's layout
         problem = BatchedQP(n=n, k=k, m=m, G=G, c=c, A_eq=A_eq, b_eq=r_eq if k else None, cons_var=cons_var, cons_a=cons_a, cons_b=cons_b)
-        v = torch.zeros(B, problem.V, dtype=G.dtype, device=G.device)
-        term = torch.empty(B, dtype=torch.int32, device=G.device)
-        nit = torch.empty(B, dtype=torch.int32, device=G.device)
-        status = torch.empty(B, dtype=torch.int32, device=G.device)
-        prob, sp = problem.as_struct(), params.as_struct()
-        L.check(L.lib().mo_qp_solve(plan_for(problem, B), C.byref(prob), B, C.byref(sp), _ptr(v), problem.V, _ptr(term), _ptr(nit), None, None,
-                                    _ptr(status), _stream()))
-        ctx.problem, ctx.v, ctx.status = problem, v, status
         ctx.layout, ctx.eq_layout, ctx.J_blocks, ctx.r, ctx.lam = layout, eq_layout, J_blocks, r, lam
-        ctx.adjoint_status = None
-        ctx.tangent_status = None
-        ctx.termination_state, ctx.num_iterations = term, nit
-        ctx.mark_non_differentiable(status)
-        ctx.set_materialize_grads(False)   # jvp: an input without a tangent arrives as None, not as a tensor of zeros to be read
-        return v.clone(), status
+        return _solve_forward(ctx, problem, B, params)
 
     @staticmethod
     def backward(ctx, g, _g_status):
-        problem, v = ctx.problem, ctx.v
-        if g is None:
-            g = torch.zeros_like(v)
-        u, adj = kkt_solve(problem, v, g.contiguous(), transpose=True)
-        ctx.adjoint_status = adj
+        problem, v, u, ok = _adjoint(ctx, g)
         need = ctx.needs_input_grad
-        ok = (ctx.status == L.MO_STATUS_OK) & (adj == L.MO_STATUS_OK)
         want = [nm for nm, nd in zip(("J_blocks", "r", "lam"), need[:3]) if nd]
         cost = qp_gradients_blocks(ctx.layout, ctx.J_blocks, ctx.r, v, u, k=problem.k, m=problem.m, want=want) if want else {}
         if "lam" in cost:
@@ -516,16 +484,10 @@ class QPSolveBlocksFunction(torch.autograd.Function):
         the (G, c) problem the forward built.  lam's tangent counts only where lam was added (lam > 0), as its gradient does.  A problem whose
         forward status or tangent-solve status is not MO_STATUS_OK gets a ZERO tangent (the backward's rule); the solve's status words are
         kept (`tangent_status`)."""
-        global _PENDING_TANGENT_STATUS
-        problem, v = ctx.problem, ctx.v
         if dlam is not None:
-            dlam = torch.where(ctx.lam > 0, dlam, torch.zeros((), dtype=v.dtype, device=v.device))
-        given = zip(BLOCK_TANGENTS, (dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b))
-        tangents = {nm: t.detach().contiguous() for nm, t in given if t is not None}
-        vdot, st = qp_jvp_blocks(problem, ctx.layout, ctx.J_blocks, ctx.r, v, tangents, eq_layout=ctx.eq_layout)
-        ctx.tangent_status = _PENDING_TANGENT_STATUS = st
-        ok = (ctx.status == L.MO_STATUS_OK) & (st == L.MO_STATUS_OK)
-        return _masked(vdot, ok), None
+            dlam = torch.where(ctx.lam > 0, dlam, torch.zeros((), dtype=ctx.v.dtype, device=ctx.v.device))
+        tangents = _given(BLOCK_TANGENTS, (dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b))
+        return _jvp_result(ctx, *qp_jvp_blocks(ctx.problem, ctx.layout, ctx.J_blocks, ctx.r, ctx.v, tangents, eq_layout=ctx.eq_layout))
 
 
 def adjoint_status(t: torch.Tensor) -> Optional[torch.Tensor]:
@@ -540,6 +502,32 @@ def adjoint_status(t: torch.Tensor) -> Optional[torch.Tensor]:
             return node.adjoint_status
         todo.extend(fn for fn, _ in node.next_functions)
     return None
+
+
+def _check_cons(cons_var, cons_a, cons_b) -> None:
+    if (cons_var is None) != (cons_a is None) or (cons_a is None) != (cons_b is None):
+        raise ValueError("cons_var, cons_a and cons_b come together")
+    if cons_var is not None and cons_var.dtype != torch.int32:
+        raise ValueError("cons_var must be int32")
+
+
+def _full(t: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
+    """An input of solve_qp with its leading dimension of 1 broadcast over the batch, contiguous."""
+    return None if t is None else (t.expand(B, *t.shape[1:]) if t.shape[0] != B else t).contiguous()
+
+
+def _result(v: torch.Tensor, status: torch.Tensor, n: int, m: int, k: int, return_all: bool, return_status: bool):
+    """What solve_qp returns from v = [x | s | y | z]: x or all four slices, the status if asked for, a single result bare."""
+    global _PENDING_TANGENT_STATUS
+    x = v[:, :n]
+    res = (x, v[:, n:n + m], v[:, n + m:n + m + k], v[:, n + m + k:]) if return_all else (x,)
+    if _PENDING_TANGENT_STATUS is not None:   # the call ran under forward_ad: tangent_status() finds the words on what it returns
+        for t in (v, *res):
+            t._mo_tangent_status = _PENDING_TANGENT_STATUS
+        _PENDING_TANGENT_STATUS = None
+    if return_status:
+        res = res + (status,)
+    return res[0] if len(res) == 1 else res
 
 
 def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons_var=None, cons_a=None, cons_b=None,
@@ -571,7 +559,7 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     if ref.dim() != 3:
         raise ValueError("G / J must be [B, rows, n]")
     B = max(int(t.shape[0]) for t in (G, c, J, r, A_eq, b_eq, cons_a, cons_b) if t is not None)
-    full = lambda t: None if t is None else (t.expand(B, *t.shape[1:]) if t.shape[0] != B else t).contiguous()
+    full = lambda t: _full(t, B)
     lam_t = None
     if isinstance(lam, torch.Tensor):
         if J is None:
@@ -581,26 +569,13 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
         if J is None:
             raise ValueError("lam belongs to the (J, r) form")
         lam_t = torch.full((B,), float(lam), dtype=ref.dtype, device=ref.device)
-    if (cons_var is None) != (cons_a is None) or (cons_a is None) != (cons_b is None):
-        raise ValueError("cons_var, cons_a and cons_b come together")
-    if cons_var is not None and cons_var.dtype != torch.int32:
-        raise ValueError("cons_var must be int32")
+    _check_cons(cons_var, cons_a, cons_b)
     A_t = None if A_eq is None else full(A_eq).transpose(1, 2).contiguous()   # BatchedQP's layout: memory = k x n column-major
     v, status = QPSolveFunction.apply(full(G), full(c), full(J), full(r), lam_t, A_t, full(b_eq), full(cons_a), full(cons_b),
                                       full(cons_var), params)
-    n = int(ref.shape[2])
     k = 0 if A_eq is None else int(A_eq.shape[1])
     m = 0 if cons_a is None else int(cons_a.shape[1])
-    x = v[:, :n]
-    res = (x, v[:, n:n + m], v[:, n + m:n + m + k], v[:, n + m + k:]) if return_all else (x,)
-    global _PENDING_TANGENT_STATUS
-    if _PENDING_TANGENT_STATUS is not None:   # the call ran under forward_ad: tangent_status() finds the words on what it returns
-        for t in (v, *res):
-            t._mo_tangent_status = _PENDING_TANGENT_STATUS
-        _PENDING_TANGENT_STATUS = None
-    if return_status:
-        res = res + (status,)
-    return res[0] if len(res) == 1 else res
+    return _result(v, status, int(ref.shape[2]), m, k, return_all, return_status)
 
 
 def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status):
@@ -610,27 +585,16 @@ def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, con
         raise ValueError("eq_layout, J_eq_blocks and r_eq come together")
     if eq_layout is not None and (eq_layout.n != layout.n or eq_layout.dtype != layout.dtype or eq_layout.device != layout.device):
         raise ValueError("eq_layout must share n, dtype and device with layout")
-    if (cons_var is None) != (cons_a is None) or (cons_a is None) != (cons_b is None):
-        raise ValueError("cons_var, cons_a and cons_b come together")
-    if cons_var is not None and cons_var.dtype != torch.int32:
-        raise ValueError("cons_var must be int32")
+    _check_cons(cons_var, cons_a, cons_b)
     tensors = [t for t in (J_blocks, r, J_eq_blocks, r_eq, cons_a, cons_b) if t is not None]
     if isinstance(lam, torch.Tensor):
         lam = lam.reshape(-1)
         tensors.append(lam)
     B = max(int(t.shape[0]) for t in tensors)
-    full = lambda t: None if t is None else (t.expand(B, *t.shape[1:]) if t.shape[0] != B else t).contiguous()
+    full = lambda t: _full(t, B)
     lam_t = full(lam) if isinstance(lam, torch.Tensor) else torch.full((B,), float(lam), dtype=layout.dtype, device=layout.device)
     v, status = QPSolveBlocksFunction.apply(full(J_blocks), full(r), lam_t, full(J_eq_blocks), full(r_eq), full(cons_a), full(cons_b),
                                             full(cons_var), layout, eq_layout, params)
-    n, k = layout.n, 0 if eq_layout is None else eq_layout.rows
+    k = 0 if eq_layout is None else eq_layout.rows
     m = 0 if cons_a is None else int(cons_a.shape[1])
-    res = (v[:, :n], v[:, n:n + m], v[:, n + m:n + m + k], v[:, n + m + k:]) if return_all else (v[:, :n],)
-    global _PENDING_TANGENT_STATUS
-    if _PENDING_TANGENT_STATUS is not None:   # the call ran under forward_ad: tangent_status() finds the words on what it returns
-        for t in (v, *res):
-            t._mo_tangent_status = _PENDING_TANGENT_STATUS
-        _PENDING_TANGENT_STATUS = None
-    if return_status:
-        res = res + (status,)
-    return res[0] if len(res) == 1 else res
+    return _result(v, status, layout.n, m, k, return_all, return_status)

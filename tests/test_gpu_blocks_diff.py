@@ -17,29 +17,9 @@ from mini_opt_amd import qp as Q
 from oracle import oracle as orc
 from tests import blocks_diff_reference as BR
 from tests import diff_reference as R
+from tests.sens_fixtures import DEV, LAM, N7_COST, PARAMS, UNIT, T, autograd_layout, bound_factor, oracle_kkt_solves, random_layout, rel_inf_rows
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-N7_COST = [((3, 0, 5, 3), 3), ((6,), 2), ((1, 2, 4, 0, 6), 4), ((2, 2), 1), ((5, 4, 1), 6)]
-UNIT = {torch.float64: 2.0 ** -53, torch.float32: 2.0 ** -24}
-
-
-def T(a, dt=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=DEV).contiguous()
-
-
-def random_layout(rng, n, count, repeats=False):
-    blocks = []
-    for _ in range(count):
-        R_ = int(rng.integers(1, 7))
-        Pn = int(rng.integers(1, min(n, 8) + 1))
-        if repeats and Pn >= 2 and rng.random() < 0.5:
-            idx = list(rng.integers(0, n, Pn))
-            idx[-1] = idx[0]         # a repeated variable inside the block
-        else:
-            idx = list(rng.permutation(n)[:Pn])   # out of order
-        blocks.append((tuple(int(i) for i in idx), R_))
-    return blocks
 
 
 def draw(rng, blocks, B, n, V, dt, shared=False):
@@ -50,13 +30,6 @@ def draw(rng, blocks, B, n, V, dt, shared=False):
     if dt == torch.float32:
         arrs = [a.astype(np.float32).astype(np.float64) for a in arrs]
     return arrs
-
-
-def bound_factor(blocks):
-    """(2 R_b P_b + 8) per packed value and per stacked row."""
-    per_val = np.concatenate([np.full(R_ * len(idx), 2 * R_ * len(idx) + 8.0) for idx, R_ in blocks])
-    per_row = np.concatenate([np.full(R_, 2 * R_ * len(idx) + 8.0) for idx, R_ in blocks])
-    return per_val, per_row
 
 
 def check_cost_problem(n, blocks, Jp, rp, v, u, got, dt, tag):
@@ -299,29 +272,14 @@ def test_eq_blocks_grad_against_restatement_and_dense_dA(dt):
 
 
 # ---- 7. autograd end to end ------------------------------------------------------------------------------------------------------------------
-PARAMS = dict(initial_mu=1.0, sigma=0.1, termination_kkt_tol=1e-9, termination_complementarity_tol=1e-9, max_iterations=30)
-LAM = 0.1
-
-
-def rel_inf_rows(got, ref):
-    return np.max(np.abs(got - ref), axis=1) / np.max(np.abs(ref), axis=1)
-
-
 def oracle_u_pair(G, c, A, b_eq, var, a, b, g):
     """u at the ORACLE's Solve output, by LU on its full system and from the reduced system in numpy (the D of test_gpu_diff.py)."""
-    from tests.test_gpu_diff import oracle_kkt_solves
     n, k, m = len(c), len(b_eq), len(var)
     o = orc.Solver(orc.QP(G=np.tril(G), c=c, A_eq=A if k else None, b_eq=b_eq if k else None, cons_var=var, cons_a=a, cons_b=b))
     o.solve(**PARAMS)
     vo = np.array(o.variables)
     _, u_lu = oracle_kkt_solves(o, n, k, m, g, g)
     return u_lu, R.transposed_through_reduced(G, A, var, a, vo, g)
-
-
-def autograd_layout(n, rng):
-    if n == 64:
-        return [(tuple(int(i) for i in rng.permutation(n)[:4]), 2) for _ in range(96)]
-    return [(tuple(int(i) for i in rng.permutation(n)[:4]), 2) for _ in range(11)] + [((3, 0, 5, 3), 3)]     # one repeated variable
 
 
 @pytest.mark.parametrize("case", ["unconstrained", "equalities", "bounds"])

@@ -21,10 +21,9 @@ from tests import blocks_diff_reference as BR
 from tests import blocks_tangent_reference as BT
 from tests import diff_reference as R
 from tests import tangent_reference as TR
-from tests.test_gpu_blocks_diff import LAM, N7_COST, PARAMS, UNIT, T, autograd_layout, bound_factor, random_layout, rel_inf_rows
+from tests.sens_fixtures import DEV, LAM, N7_COST, PARAMS, UNIT, T, autograd_layout, bound_factor, random_layout, rel_inf_rows
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 DTYPES = pytest.mark.parametrize("dt", [torch.float64, torch.float32], ids=["f64", "f32"])
 N7_EQ = [((0, 4, 0), 1), ((2, 6, 1), 1)]          # the first local column of block 0 loses variable 0 to the last
 KEYS = ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq", "cons_a", "cons_b")

@@ -10,9 +10,10 @@ import torch
 from mini_opt_amd import _lib as L
 from mini_opt_amd import diff as D
 from mini_opt_amd import qp as Q
-from mini_opt_amd import synth
 from oracle import oracle as orc
 from tests import diff_reference as R
+from tests.sens_fixtures import (ACTIVE_SEED, PARAMS, T, active_set_problems, dev, device_problem, host_batch, oracle_kkt_solves,
+                                 oracle_solver, rel_inf_rows)
 
 pytestmark = pytest.mark.gpu
 TOL64 = 1e-10
@@ -20,75 +21,6 @@ TOL32 = 2e-3
 SHAPES = [(8, 2, 5, 12), (8, 0, 0, 12), (12, 3, 0, 20), (64, 8, 32, 128), (96, 40, 20, 128)]   # (n, k, m, m_r); the last two run LARGE
 CASES = [(s, lvl, torch.float64) for s in SHAPES for lvl in ("J", "G")] + [(s, "J", torch.float32) for s in (SHAPES[0], SHAPES[3])]
 IDS = [f"n{s[0]}k{s[1]}m{s[2]}-{lvl}-{'f64' if dt == torch.float64 else 'f32'}" for s, lvl, dt in CASES]
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def T(a, dt=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev()).contiguous()
-
-
-def rel_inf_rows(got, ref):
-    return np.max(np.abs(got - ref), axis=1) / np.max(np.abs(ref), axis=1)
-
-
-def host_batch(n, k, m, m_r, B, stream, f32=False):
-    """Interior states from mini_opt_amd.synth; an odd m drops the last constraint of the next even one."""
-    mm = m + (m & 1)
-    hb = synth.make_batch(n, k, mm, m_r, B, stream=stream)
-    if mm != m:
-        keep = np.r_[0:n + m, n + mm:n + mm + k + m]
-        hb.vars = np.ascontiguousarray(hb.vars[:, keep])
-        hb.cons_var, hb.cons_a, hb.cons_b = (np.ascontiguousarray(a[:, :m]) for a in (hb.cons_var, hb.cons_a, hb.cons_b))
-        hb.m = m
-    if f32:
-        for key in ("J", "r", "A_eq", "b_eq", "cons_a", "cons_b", "vars", "mu"):
-            setattr(hb, key, getattr(hb, key).astype(np.float32).astype(np.float64))
-        hb.lam = float(np.float32(hb.lam))
-    hb.G = np.einsum("bqi,bqj->bij", hb.J, hb.J) + hb.lam * np.eye(n)
-    hb.c = np.einsum("bqi,bq->bi", hb.J, hb.r)
-    return hb
-
-
-def device_problem(hb, level, dt=torch.float64, J_layout="row", J_ld=None):
-    kw = dict(n=hb.n, k=hb.k, m=hb.m)
-    if hb.k:
-        kw.update(A_eq=T(hb.A_eq, dt), b_eq=T(hb.b_eq, dt))
-    if hb.m:
-        kw.update(cons_var=T(hb.cons_var, torch.int32), cons_a=T(hb.cons_a, dt), cons_b=T(hb.cons_b, dt))
-    if level == "G":
-        return Q.BatchedQP(G=T(hb.G, dt), c=T(hb.c, dt), **kw)
-    B, m_r, n = hb.J.shape
-    if J_layout == "col":
-        ld = J_ld or m_r
-        J = np.zeros((B, n, ld)); J[:, :, :m_r] = hb.J.transpose(0, 2, 1)
-        return Q.BatchedQP(J=T(J, dt), r=T(hb.r, dt), lam=hb.lam, J_layout="col", J_rows=m_r, **kw)
-    ld = J_ld or n
-    J = np.zeros((B, m_r, ld)); J[:, :, :n] = hb.J
-    return Q.BatchedQP(J=T(J, dt), r=T(hb.r, dt), lam=hb.lam, **kw)
-
-
-def oracle_solver(hb, p, state=None):
-    o = orc.Solver(orc.QP(G=np.tril(hb.G[p]), c=hb.c[p], A_eq=hb.A_eq[p].T if hb.k else None, b_eq=hb.b_eq[p] if hb.k else None,
-                          cons_var=hb.cons_var[p], cons_a=hb.cons_a[p], cons_b=hb.cons_b[p]))
-    if state is not None:
-        o.variables[:] = state
-    return o
-
-
-def oracle_kkt_solves(o, n, k, m, rhs, g):
-    """delta with K delta = -rhs and u with K^T u = g by LU on the oracle's full_system() matrix Hf at its current state.  Hf is the
-    reference's BuildFullSystem: the row of r_comp divided by s, and the y and z unknowns negated, i.e. K = D_r Hf D_c with
-    D_r = diag(1, s, 1, 1), D_c = diag(1, 1, -1, -1)."""
-    Hf, _ = o.full_system()
-    s = np.array(o.variables[n:n + m])
-    d_r = np.concatenate([np.ones(n), s, np.ones(k + m)])
-    d_c = np.concatenate([np.ones(n + m), -np.ones(k + m)])
-    delta = d_c * np.linalg.solve(Hf, -rhs / d_r)
-    u = np.linalg.solve(Hf.T, d_c * g) / d_r
-    return delta, u
 
 
 # ---- 1. the Newton direction through mo_kkt_solve -------------------------------------------------------------------------------------------
@@ -276,9 +208,6 @@ def test_qp_gradients_strides_and_null_members():
 
 
 # ---- 5. autograd end to end ------------------------------------------------------------------------------------------------------------------
-PARAMS = dict(initial_mu=1.0, sigma=0.1, termination_kkt_tol=1e-9, termination_complementarity_tol=1e-9, max_iterations=30)
-
-
 def test_autograd_unconstrained_against_torch_linalg_solve():
     """(a) m = 0, k = 0, G = M M^T / n + I (cond(G) <= ~10): gradients with respect to M and c through solve_qp against autograd through
     torch.linalg.solve(G, -c), TOL64."""
@@ -323,28 +252,6 @@ def test_autograd_equality_only_against_the_dense_kkt_solve_in_torch():
         err = rel_inf_rows(a.reshape(B, -1).cpu().numpy(), b_.reshape(B, -1).cpu().numpy())
         print(f"equality-only {tag}: {err.max():.3e}")
         assert err.max() < TOL64, tag
-
-
-ACTIVE_SEED, ACTIVE_COUNT = 2024, 200
-
-
-def active_set_problems():
-    """n = 8, G = U U^T / n + I with U ~ U(-1, 1), c ~ 2 N(0, 1), 1 ... n single-variable rows on distinct variables with a = +-1,
-    b ~ U(0.1, 1); g non-zero on the x block only.  Grouped by the number of rows (a batch has one shape): 25 problems for each m = 1 ... 8."""
-    rng = np.random.default_rng(ACTIVE_SEED)
-    n = 8
-    groups = []
-    for m in range(1, n + 1):
-        cnt = ACTIVE_COUNT // n
-        U = rng.uniform(-1, 1, (cnt, n, n))
-        G = np.einsum("bik,bjk->bij", U, U) / n + np.eye(n)
-        c = 2 * rng.normal(size=(cnt, n))
-        var = np.stack([rng.permutation(n)[:m] for _ in range(cnt)]).astype(np.int32)
-        a = rng.choice([-1.0, 1.0], (cnt, m))
-        b = rng.uniform(0.1, 1.0, (cnt, m))
-        gx = rng.normal(size=(cnt, n))
-        groups.append(dict(n=n, m=m, G=G, c=c, var=var, a=a, b=b, gx=gx))
-    return groups
 
 
 def test_autograd_with_active_inequalities():

@@ -50,8 +50,7 @@ from oracle import nls_oracle as N
 from oracle import oracle as orc
 from tests import blocks_diff_reference as BR
 from tests import diff_reference as R
-from tests.test_gpu_blocks_diff import UNIT, random_layout
-from tests.test_gpu_diff import device_problem, host_batch, oracle_kkt_solves, oracle_solver
+from tests.sens_fixtures import UNIT, device_problem, host_batch, oracle_kkt_solves, oracle_solver, random_layout
 from tests.test_gpu_parity import TOL32, TOL64, T, rel_inf_rows, solves_agree_or_knife_edge
 from tests.test_gpu_residual_blocks import bound_terms, oracle_hessian, oracle_jacobian, pack_np
 from tests.test_gpu_residual_blocks import draw as draw_blocks

@@ -11,9 +11,9 @@ import torch.autograd.forward_ad as fwAD
 from mini_opt_amd import _lib as L
 from mini_opt_amd import diff as D
 from mini_opt_amd import qp as Q
-from mini_opt_amd import synth
 from tests import diff_reference as R
 from tests import tangent_reference as TR
+from tests.sens_fixtures import ACTIVE_SEED, PARAMS, T, active_set_problems, dev, device_problem, host_batch, padded, rel_inf_rows
 
 pytestmark = pytest.mark.gpu
 TOL64 = 1e-10
@@ -24,57 +24,6 @@ SHAPES = [(5, 0, 0, 7), (8, 2, 5, 12), (7, 3, 4, 9), (33, 3, 66, 35), (64, 8, 32
 SID = lambda s: f"n{s[0]}k{s[1]}m{s[2]}r{s[3]}"
 DTYPES = [torch.float64, torch.float32]
 DID = lambda dt: "f64" if dt == torch.float64 else "f32"
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def T(a, dt=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev()).contiguous()
-
-
-def rel_inf_rows(got, ref):
-    return np.max(np.abs(got - ref), axis=1) / np.max(np.abs(ref), axis=1)
-
-
-def host_batch(n, k, m, m_r, B, stream, f32=False):
-    """Interior states from mini_opt_amd.synth; an odd m drops the last constraint of the next even one."""
-    mm = m + (m & 1)
-    hb = synth.make_batch(n, k, mm, m_r, B, stream=stream)
-    if mm != m:
-        keep = np.r_[0:n + m, n + mm:n + mm + k + m]
-        hb.vars = np.ascontiguousarray(hb.vars[:, keep])
-        hb.cons_var, hb.cons_a, hb.cons_b = (np.ascontiguousarray(a[:, :m]) for a in (hb.cons_var, hb.cons_a, hb.cons_b))
-        hb.m = m
-    if f32:
-        for key in ("J", "r", "A_eq", "b_eq", "cons_a", "cons_b", "vars", "mu"):
-            setattr(hb, key, getattr(hb, key).astype(np.float32).astype(np.float64))
-        hb.lam = float(np.float32(hb.lam))
-    hb.G = np.einsum("bqi,bqj->bij", hb.J, hb.J) + hb.lam * np.eye(n)
-    hb.c = np.einsum("bqi,bq->bi", hb.J, hb.r)
-    return hb
-
-
-def padded(a, ld, fill=0.0):
-    """[B, rows, cols] -> [B, rows, ld] with `fill` beyond cols."""
-    out = np.full(a.shape[:2] + (ld,), fill)
-    out[:, :, :a.shape[2]] = a
-    return out
-
-
-def device_problem(hb, level, dt=torch.float64, J_layout="row", J_ld=None):
-    kw = dict(n=hb.n, k=hb.k, m=hb.m)
-    if hb.k:
-        kw.update(A_eq=T(hb.A_eq, dt), b_eq=T(hb.b_eq, dt))
-    if hb.m:
-        kw.update(cons_var=T(hb.cons_var, torch.int32), cons_a=T(hb.cons_a, dt), cons_b=T(hb.cons_b, dt))
-    if level == "G":
-        return Q.BatchedQP(G=T(hb.G, dt), c=T(hb.c, dt), **kw)
-    B, m_r, n = hb.J.shape
-    if J_layout == "col":
-        return Q.BatchedQP(J=T(padded(hb.J.transpose(0, 2, 1), J_ld or m_r), dt), r=T(hb.r, dt), lam=hb.lam, J_layout="col", J_rows=m_r, **kw)
-    return Q.BatchedQP(J=T(padded(hb.J, J_ld or n), dt), r=T(hb.r, dt), lam=hb.lam, **kw)
 
 
 def directions(hb, seed, f32=False, shared=False):
@@ -367,8 +316,7 @@ def test_device_adjoint_identity(shape, level):
 
 # ---- 6. torch.autograd.forward_ad through solve_qp -----------------------------------------------------------------------------------------
 def params():
-    from tests import test_gpu_diff as GD
-    return Q.Params(**GD.PARAMS)
+    return Q.Params(**PARAMS)
 
 
 def test_forward_ad_unconstrained_against_torch_linalg_solve():
@@ -432,8 +380,7 @@ def test_forward_ad_with_active_inequalities():
     makes rho_pi non-zero, and at a slack of 1e-11 the two factorisations agree no better), 150 of 200 problems with an active row, the
     device's worst rel-inf of vdot 1.4e-5."""
     from oracle import oracle as orc
-    from tests import test_gpu_diff as GD
-    groups = GD.active_set_problems()
+    groups = active_set_problems()
     n = 8
     rng = np.random.default_rng(28)
     D_cpu, active, total, worst = 0.0, 0, 0, 0.0
@@ -445,7 +392,7 @@ def test_forward_ad_with_active_inequalities():
         # the CPU measurement of D at the oracle's optimum
         for p in range(cnt):
             o = orc.Solver(orc.QP(G=np.tril(grp["G"][p]), c=grp["c"][p], cons_var=grp["var"][p], cons_a=grp["a"][p], cons_b=grp["b"][p]))
-            o.solve(**GD.PARAMS)
+            o.solve(**PARAMS)
             vo = np.array(o.variables)
             rho = TR.rho(n, 0, m, grp["var"][p], vo, {key: val[p] for key, val in dsym.items()})
             lu = TR.vdot(grp["G"][p], none, grp["var"][p], grp["a"][p], vo, rho)
@@ -464,7 +411,7 @@ def test_forward_ad_with_active_inequalities():
                                 TR.rho(n, 0, m, grp["var"][p], v[p], {key: val[p] for key, val in dsym.items()})) for p in range(cnt)])
         worst = max(worst, float(rel_inf_rows(vdot, ref).max()))
     bound = max(TOL64, 10 * D_cpu)
-    print(f"active-set forward_ad: D = {D_cpu:.3e} (seed {GD.ACTIVE_SEED}, {total} problems), bound {bound:.3e}, "
+    print(f"active-set forward_ad: D = {D_cpu:.3e} (seed {ACTIVE_SEED}, {total} problems), bound {bound:.3e}, "
           f"{active} of {total} problems with an active row, worst rel-inf of vdot {worst:.3e}")
     assert 2 * active >= total, (active, total)
     assert worst < bound, (worst, bound)

@@ -10,7 +10,7 @@ import pytest
 
 from tests import diff_reference as R
 from tests import tangent_reference as T
-from tests import test_diff_cpu as D
+from tests import sens_fixed_problem as D
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 N, K, M, MR = D.N, D.K, D.M, D.MR

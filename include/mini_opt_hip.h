@@ -455,6 +455,29 @@ typedef struct {
 int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* u,
                     int64_t u_stride, const mo_qp_grads* out, void* stream);
 
+/* The same gradients SUMMED over the batch, for data the whole batch shares (a learned layer: one G, A_eq, constraint set or J for every
+ * sample).  With ok_p = "problem p counts" and M = sum ok_p u_x,p x_p^T, s_u = sum ok_p u_x,p, s_uy = sum ok_p u_y,p, s_uz = sum ok_p u_z,p:
+ *   dG = -1/2 (M + M^T)       dc = -s_u       dA_eq = sum ok_p (y_p u_x,p^T - u_y,p x_p^T)       db_eq = -s_uy
+ *   dcons_a[i] = sum ok_p (z_p,i u_x,p[var_i] - u_z,p,i x_p[var_i])       dcons_b = -s_uz
+ *   dJ = -J (M + M^T) - Q,  Q = sum ok_p r_p u_x,p^T (r s_u^T when r_stride is 0 too)       dr = -J s_u       dlambda = -trace(M)
+ * No per-problem matrix is written or read: the inputs are the two [batch][V] arrays.  `out` is the struct of mo_qp_gradients holding ONE
+ * instance per member: the *_stride fields are ignored, the leading dimensions honoured, a NULL member neither computed nor written.
+ * status_fwd / status_adj ([batch] MO_STATUS_* words, either may be NULL): problem p counts iff every given word is MO_STATUS_OK; a problem
+ * that does not count contributes exactly nothing, whatever its rows of vars / u hold (mo_kkt_solve leaves NaN there).
+ * MO_ERR_INVALID_ARGUMENT, with nothing written: dJ or dr unless prob->J_stride == 0; dcons_a / dcons_b unless prob->cons_stride == 0; dG
+ * with J-level input, dJ / dr / dlambda with (G, c) input (mo_qp_gradients' rules); a workspace smaller than
+ * mo_qp_gradients_shared_workspace reports for the same (plan, prob, batch, out), or not 16-byte aligned.  MO_ERR_DIMENSION as
+ * mo_qp_gradients.  Shapes, dtypes and J layouts: those of mo_qp_gradients; any vars_stride, u_stride >= V.  batch == 0 writes zeros.
+ * The batch is cut into chunks of consecutive problems, their number a function of (batch, CU count) alone; the moments of a chunk are
+ * accumulated on the matrix cores (v_mfma_*_16x16x4, four problems per instruction), the chunk partials are summed in chunk order in
+ * double, the outputs are formed in double and rounded once.  Every workspace and output element has one owner: no atomics, no memset, the
+ * same bits on every launch of one device; dG is symmetric to the bit.  No allocation and no synchronisation on the launch path: three
+ * kernels on `stream`.  The workspace's contents are scratch. */
+int mo_qp_gradients_shared_workspace(const mo_plan* plan, const mo_problem* prob, int64_t batch, const mo_qp_grads* out, int64_t* bytes);
+int mo_qp_gradients_shared(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* u,
+                           int64_t u_stride, const int32_t* status_fwd, const int32_t* status_adj, const mo_qp_grads* out, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 /* The same gradients for RESIDUAL-BLOCK input (the packed local Jacobians of a mo_residual_layout), without forming an n x n or an
  * m_r x n matrix: the transpose of the gather mo_linearize_blocks / mo_jacobian_blocks perform, applied to the pair (x, u_x).
  * mo_linearize_blocks forms, per block b and local pair q <= p, G_low[max(i, j), min(i, j)] += J_b[:, p] . J_b[:, q] with i = idx_b[p],

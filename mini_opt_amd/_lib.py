@@ -35,6 +35,7 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_default_nls_params", "mo_nls_solve", "mo_nullspace_solve", "mo_residual_eval", "mo_qp_eigenvalue_stats",
            "mo_residual_layout_create", "mo_residual_layout_destroy", "mo_residual_layout_values", "mo_residual_layout_rows",
            "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks", "mo_kkt_solve", "mo_qp_gradients",
+           "mo_qp_gradients_shared_workspace", "mo_qp_gradients_shared",
            "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_tangent_rhs", "mo_qp_tangent_rhs_blocks"]
 
 
@@ -143,7 +144,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "tools", "isa_lint.py"))   # the build lints its own listings: a changed lint re-runs it
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
-        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (sixteen units, the longest 5.7 min)
+        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (seventeen units, the longest 5.7 min)
         subprocess.check_call(["make", "-C", CSRC, f"-j{jobs}"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
@@ -204,6 +205,8 @@ def lib() -> C.CDLL:
     L.mo_nls_solve_blocks.argtypes = [vp, C.POINTER(NlsProblem), vp, vp, i64, C.POINTER(NlsParams), NLS_EVAL_FN, vp, vp, vp, vp, vp, vp]
     L.mo_kkt_solve.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, u32, vp, i64, vp, vp]
     L.mo_qp_gradients.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, C.POINTER(QPGrads), vp]
+    L.mo_qp_gradients_shared_workspace.argtypes = [vp, C.POINTER(Problem), i64, C.POINTER(QPGrads), C.POINTER(i64)]
+    L.mo_qp_gradients_shared.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, vp, vp, C.POINTER(QPGrads), vp, i64, vp]
     L.mo_qp_gradients_blocks.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.POINTER(BlockGrads), vp]
     L.mo_qp_gradients_eq_blocks.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.mo_qp_tangent_rhs.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, C.POINTER(QPTangents), vp, i64, vp]

@@ -594,6 +594,78 @@ int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const 
   return MO_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// What mo_qp_gradients_shared and its workspace query judge alike: the members against the input level and against what the batch shares,
+// then the plan and the leading dimensions (sens_args, check_dG_dA_ld: those of mo_qp_gradients).  vars / u are not looked at here.
+int shared_grad_args(const mo_plan* plan, const mo_problem* prob, int64_t batch, const mo_qp_grads* out, mo::SharedGradArgs* a) {
+  if (!prob) return fail(MO_ERR_INVALID_ARGUMENT, "Must pass a non-null problem");
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  const bool j_level = prob->J != nullptr;
+  if (j_level && out->dG) return fail(MO_ERR_INVALID_ARGUMENT, "dG asked for with J-level input: ask for dJ / dr / dlambda");
+  if (!j_level && (out->dJ || out->dr || out->dlambda))
+    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr / dlambda asked for with (G, c) input: ask for dG / dc");
+  if ((out->dJ || out->dr) && prob->J_stride != 0)
+    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr summed over the batch need one J for the batch: J_stride is %lld, not 0", (long long)prob->J_stride);
+  memset(a, 0, sizeof(*a));
+  a->out = *out;
+  if (int rc = sens_args(plan, prob, batch, nullptr, 0, &a->out, a)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  if ((a->out.dcons_a || a->out.dcons_b) && prob->cons_stride != 0)
+    return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a / dcons_b summed over the batch need one constraint set for the batch: cons_stride is %lld, not 0",
+                (long long)prob->cons_stride);
+  if (a->J && !prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "J given without r");
+  if (a->out.dJ) {
+    if (a->out.dJ_layout != MO_ROW_MAJOR && a->out.dJ_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad dJ_layout");
+    const int min_dld = a->out.dJ_layout == MO_ROW_MAJOR ? d.n : d.m_r;
+    if (a->out.dJ_ld < min_dld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a->out.dJ_ld, min_dld);
+  }
+  if (int rc = check_dG_dA_ld(d, a->out)) return rc;
+  if (a->out.dcons_a) {
+    if (!prob->cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a asked for but cons_var is NULL");
+    a->cons_var = prob->cons_var; a->cons_stride = 0;
+  }
+  if (mo::shared_grad_lds_bytes(*a, plan->elem) > 64 * 1024)
+    return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, m_r = %d: four problems' vectors exceed the 64 KiB of LDS the moment kernel uses", d.n, d.k, d.m, a->m_r);
+  return MO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mo_qp_gradients_shared_workspace(const mo_plan* plan, const mo_problem* prob, int64_t batch, const mo_qp_grads* out, int64_t* bytes) {
+  g_err[0] = 0;
+  if (!bytes) return fail(MO_ERR_INVALID_ARGUMENT, "bytes is NULL");
+  mo::SharedGradArgs a;
+  if (int rc = shared_grad_args(plan, prob, batch, out, &a)) return rc;
+  *bytes = (int64_t)mo::shared_grad_workspace_bytes(a, plan->elem, plan->num_cus);
+  return MO_OK;
+}
+
+int mo_qp_gradients_shared(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const void* u,
+                           int64_t u_stride, const int32_t* status_fwd, const int32_t* status_adj, const mo_qp_grads* out, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
+  g_err[0] = 0;
+  mo::SharedGradArgs a;
+  if (int rc = shared_grad_args(plan, prob, batch, out, &a)) return rc;
+  if (batch > 0 && (!vars || !u)) return fail(MO_ERR_INVALID_ARGUMENT, "vars / u is NULL");
+  const int V = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
+  if (batch > 1 && (vars_stride < V || u_stride < V)) return fail(MO_ERR_DIMENSION, "vars_stride %lld / u_stride %lld < V = %d", (long long)vars_stride, (long long)u_stride, V);
+  const int64_t need = (int64_t)mo::shared_grad_workspace_bytes(a, plan->elem, plan->num_cus);
+  if (!workspace || workspace_bytes < need)
+    return fail(MO_ERR_INVALID_ARGUMENT, "workspace too small: %lld bytes given, %lld needed (mo_qp_gradients_shared_workspace)", (long long)(workspace ? workspace_bytes : 0), (long long)need);
+  if ((uintptr_t)workspace & 15) return fail(MO_ERR_INVALID_ARGUMENT, "workspace is not 16-byte aligned");
+  a.vars = vars; a.vars_stride = vars_stride;
+  a.u = u; a.u_stride = u_stride;
+  a.status_fwd = status_fwd; a.status_adj = status_adj;
+  a.workspace = workspace;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_qp_gradients_shared(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
 int mo_qp_tangent_rhs(mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride,
                       const mo_qp_tangents* t, void* rho, int64_t rho_stride, void* stream) {
   g_err[0] = 0;

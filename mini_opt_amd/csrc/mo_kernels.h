@@ -234,6 +234,30 @@ struct GradArgs : SensArgs {
 size_t qp_grad_lds_bytes(const GradArgs& a, int elem_size);
 hipError_t launch_qp_gradients(const GradArgs& a, int dtype, int num_cus, hipStream_t stream);
 
+// the same gradients SUMMED over the batch, for data the whole batch shares (mo_qp_gradients_shared), qp_grad_shared.hip: moments of
+// (x, u_x), (y, u_x), (u_y, x), (r, u_x) per chunk of problems on the matrix cores, then one pass over the chunk partials.  `out` is one
+// instance per member (its strides are not read).  J only for dJ / dr (stride 0), r only for dJ, cons_var only for dcons_a (stride 0).
+struct SharedGradArgs : GradArgs {
+  const int* status_fwd; const int* status_adj;   // either may be NULL; a problem counts iff every given word is MO_STATUS_OK
+  void* workspace;                                // shared_grad_workspace_bytes, 16-byte aligned
+};
+// chunks of consecutive problems, each summed by its own workgroups: a function of (batch, CU count) alone, so that the order of every sum --
+// and with it every bit of the result -- is the same on every launch of one device
+inline long long shared_grad_chunk_len(long long batch, int num_cus) {   // problems per chunk (the last chunk may be shorter)
+  long long c = (batch + 31) / 32;                  // at least 32 problems a chunk, at most one chunk per CU
+  if (c > num_cus) c = num_cus;
+  if (c < 1) c = 1;
+  const long long len = (batch + c - 1) / c;
+  return len < 1 ? 1 : len;
+}
+inline long long shared_grad_chunks(long long batch, int num_cus) {
+  const long long len = shared_grad_chunk_len(batch, num_cus);
+  return (batch + len - 1) / len;                   // 0 for an empty batch
+}
+size_t shared_grad_workspace_bytes(const SharedGradArgs& a, int elem_size, int num_cus);
+size_t shared_grad_lds_bytes(const SharedGradArgs& a, int elem_size);
+hipError_t launch_qp_gradients_shared(const SharedGradArgs& a, int dtype, int num_cus, hipStream_t stream);
+
 // forward-mode right-hand side rho = F_theta thetadot of a QP (mo_qp_tangent_rhs), qp_tangent.hip: the transpose of the gradient kernel
 // above.  r is read only against the dJ tangent, cons_var whenever the problem has one.
 struct TangentArgs : SensArgs {

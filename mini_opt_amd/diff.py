@@ -2,12 +2,14 @@
 
     kkt_solve       mo_kkt_solve     the KKT system of a state for the caller's right-hand side (direct or transposed)
     qp_gradients    mo_qp_gradients  gradients of a loss with respect to the QP's data from the state v and the adjoint u = K^-T g
+    qp_gradients_shared    mo_qp_gradients_shared  the same gradients SUMMED over the batch, for data the whole batch shares
     qp_gradients_blocks, qp_gradients_eq_blocks    the same for residual-block input: gradients of the PACKED local Jacobians
     qp_tangent_rhs  mo_qp_tangent_rhs  forward mode: rho = F_theta thetadot from the state v and a direction in the QP's data
     qp_jvp          qp_tangent_rhs + kkt_solve: the directional derivative vdot of the whole solution [x | s | y | z]
     qp_tangent_rhs_blocks, qp_jvp_blocks    the same for residual-block input: rho from the PACKED tangents of the blocks
     solve_qp        the user-facing call: forward = Solve (the kernels of qp.QPInteriorPointSolver, fused where the shape allows),
-                    backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient,
+                    backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient
+                    (+ ONE batch-reduced launch for the inputs given once for the batch, leading dimension 1),
                     jvp (torch.autograd.forward_ad) = ONE tangent launch + ONE KKT solve, for all three input forms
 
 The mathematics is in include/mini_opt_hip.h (above mo_kkt_solve) and DESIGN.md section 4.8.  All arithmetic happens in the HIP library;
@@ -168,6 +170,64 @@ def qp_gradients(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor, want: 
     return out
 
 
+def qp_gradients_shared(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor, want: Iterable[str], status_fwd: Optional[torch.Tensor] = None,
+                        status_adj: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """mo_qp_gradients_shared: the gradients named in `want`, SUMMED over the batch, for data the whole batch shares.  Keys and layouts are
+    those of qp_gradients with a leading dimension of 1: "G" [1, n, n], "c" [1, n], "A_eq" [1, n, k], "J" [1, rows, ld], "lam" [1], ...
+    status_fwd / status_adj: [B] int32 status words; a problem counts iff every given word is MO_STATUS_OK (its rows of `vars` / `u` may
+    then hold anything, NaN included).  "J" and "r" need problem.J with a leading dimension of 1, "cons_a" / "cons_b" a constraint set with
+    one.  No [B, ...] matrix is formed: the workspace (chunk partials, from torch's allocator) is a few tiles per CU."""
+    B = _check_state_pair(vars, u, "u", problem.V, problem)
+    n, k, m = problem.n, problem.k, problem.m
+    want = tuple(want)
+    _check_dense_names(problem, want, "gradient")
+    dt, dev = problem.dtype, problem.device
+    for name, st in (("status_fwd", status_fwd), ("status_adj", status_adj)):
+        if st is not None and (st.dtype != torch.int32 or tuple(st.shape) != (B,) or not st.is_contiguous() or st.device != dev):
+            raise ValueError(f"{name}: expected a contiguous [{B}] int32 tensor on {dev}")
+    new = lambda *shape: torch.empty(1, *shape, dtype=dt, device=dev)
+    out: Dict[str, torch.Tensor] = {}
+    g = L.QPGrads()
+    if "G" in want:
+        out["G"] = new(n, n)
+        g.dG, g.dG_ld = _ptr(out["G"]), n
+    if "c" in want:
+        out["c"] = new(n)
+        g.dc = _ptr(out["c"])
+    if "A_eq" in want:
+        out["A_eq"] = new(n, k)
+        g.dA_eq, g.dA_ld = _ptr(out["A_eq"]), k
+    if "b_eq" in want:
+        out["b_eq"] = new(k)
+        g.db_eq = _ptr(out["b_eq"])
+    if "cons_a" in want:
+        out["cons_a"] = new(m)
+        g.dcons_a = _ptr(out["cons_a"])
+    if "cons_b" in want:
+        out["cons_b"] = new(m)
+        g.dcons_b = _ptr(out["cons_b"])
+    if "J" in want:
+        rows, ld = int(problem.J.shape[1]), int(problem.J.shape[2])
+        padded = ld > (problem.m_r if problem.J_layout == "col" else n)   # (the padding beyond the matrix is not written: define it)
+        out["J"] = torch.zeros(1, rows, ld, dtype=dt, device=dev) if padded else new(rows, ld)
+        g.dJ, g.dJ_ld = _ptr(out["J"]), ld
+        g.dJ_layout = L.MO_COL_MAJOR if problem.J_layout == "col" else L.MO_ROW_MAJOR
+    if "r" in want:
+        out["r"] = new(problem.m_r)
+        g.dr = _ptr(out["r"])
+    if "lam" in want:
+        out["lam"] = new()
+        g.dlambda = _ptr(out["lam"])
+    prob = problem.as_struct()
+    plan = plan_for(problem, B)
+    nbytes = C.c_int64()
+    L.check(L.lib().mo_qp_gradients_shared_workspace(plan, C.byref(prob), B, C.byref(g), C.byref(nbytes)))
+    work = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
+    L.check(L.lib().mo_qp_gradients_shared(plan, C.byref(prob), B, _ptr(vars), problem.V, _ptr(u), problem.V, _ptr(status_fwd), _ptr(status_adj),
+                                           C.byref(g), _ptr(work), int(work.numel()), _stream()))
+    return out
+
+
 def qp_tangent_rhs(problem: BatchedQP, vars: torch.Tensor, tangents: Dict[str, torch.Tensor]) -> torch.Tensor:
     """mo_qp_tangent_rhs: rho [B, V] = F_theta thetadot at the state `vars` [B, V] for the direction `tangents` in the problem's data, the
     right-hand side of the forward-mode system K vdot = -rho.  `tangents` maps the keys of GRADIENTS to tensors in BatchedQP's layouts (the
@@ -275,8 +335,10 @@ class QPSolveFunction(torch.autograd.Function):
     """v*(theta) = QPInteriorPointSolver::Solve with the adjoint of the KKT conditions as its backward.
 
     forward(G, c, J, r, lam, A_eq, b_eq, cons_a, cons_b, cons_var, params) -> (v [B, V] = [x | s | y | z], status [B]); tensors in BatchedQP's
-    layouts, full batch, contiguous; `lam` a [B] tensor or None.  The backward solves K(v)^T u = g once and launches mo_qp_gradients once, for
-    the inputs whose needs_input_grad is set.  A problem whose forward status or adjoint status is not MO_STATUS_OK gets ZERO gradients: one
+    layouts, contiguous, each with a leading dimension of B or of 1 (given once for the batch: read with stride 0, never expanded; the
+    constraint triple all three or none); `lam` a [B] or [1] tensor or None.  The backward solves K(v)^T u = g once and launches
+    mo_qp_gradients once, for the per-problem inputs whose needs_input_grad is set, and mo_qp_gradients_shared once, for the shared ones:
+    their gradients are summed over the batch by the kernel and arrive as [1, ...].  A problem whose forward status or adjoint status is not MO_STATUS_OK gets ZERO gradients: one
     infeasible problem must not poison the reduction over a batch with NaN.  The adjoint's status words stay on the node
     (`adjoint_status`, None before the first backward)."""
 
@@ -289,14 +351,26 @@ class QPSolveFunction(torch.autograd.Function):
         m = 0 if cons_a is None else int(cons_a.shape[1])
         problem = BatchedQP(n=n, k=k, m=m, J=det(J), r=det(r), lam=0.0, lam_vec=det(lam), G=det(G), c=det(c), A_eq=det(A_eq), b_eq=det(b_eq),
                             cons_var=cons_var, cons_a=det(cons_a), cons_b=det(cons_b))
-        return _solve_forward(ctx, problem, int(ref.shape[0]), params)
+        inputs = (G, c, J, r, lam, A_eq, b_eq, cons_a, cons_b)
+        B = max(int(t.shape[0]) for t in inputs if t is not None)
+        ctx.shared = frozenset(nm for nm, t in zip(GRADIENTS, inputs) if t is not None and int(t.shape[0]) == 1 and B > 1)
+        return _solve_forward(ctx, problem, B, params)
 
     @staticmethod
     def backward(ctx, g, _g_status):
         problem, v, u, ok = _adjoint(ctx, g)
         want = [nm for nm, need in zip(GRADIENTS, ctx.needs_input_grad[:9]) if need]
-        grads = qp_gradients(problem, v, u, want) if want else {}
-        return (*[_masked(grads.get(nm), ok) for nm in GRADIENTS], None, None)
+        # summed by the kernel: what the batch shares -- but "r" given once against a J per problem, which mo_qp_gradients_shared refuses
+        # (dr = -J s_u needs one J): that one is formed per problem and summed here
+        summed = [nm for nm in want if nm in ctx.shared and not (nm == "r" and "J" not in ctx.shared)]
+        each = [nm for nm in want if nm not in summed]
+        grads = {nm: _masked(t, ok) for nm, t in qp_gradients(problem, v, u, each).items()} if each else {}
+        for nm in each:
+            if nm in ctx.shared:
+                grads[nm] = grads[nm].sum(0, keepdim=True)
+        if summed:
+            grads.update(qp_gradients_shared(problem, v, u, summed, status_fwd=ctx.status, status_adj=ctx.adjoint_status))
+        return (*[grads.get(nm) for nm in GRADIENTS], None, None)
 
     @staticmethod
     def jvp(ctx, dG, dc, dJ, dr, dlam, dA_eq, db_eq, dcons_a, dcons_b, _dcons_var, _dparams):
@@ -536,7 +610,10 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     """Solve a batch of QPs   min 1/2 x^T G x + c^T x   s.t.  A_eq x + b_eq = 0,  cons_a[i] x[cons_var[i]] + cons_b[i] >= 0   on the GPU and
     keep the result on the autograd graph.  Give EITHER (G [B, n, n] SYMMETRIC, c [B, n]) OR the least-squares form (J [B, m_r, n], r [B, m_r],
     lam: float or [B] tensor; G = J^T J + lam I, c = J^T r, lam added where > 0).  A_eq [B, k, n] (rows = constraints), b_eq [B, k];
-    cons_var int32 [B, m] (never differentiable), cons_a, cons_b [B, m]; a leading dimension of 1 is broadcast over the batch.
+    cons_var int32 [B, m] (never differentiable), cons_a, cons_b [B, m]; a leading dimension of 1 is ONE instance for the whole batch (a
+    learned layer's parameters): it is read with stride 0, never copied B times, and its gradient arrives summed over the batch, [1, ...],
+    from one batch-reduced launch (mo_qp_gradients_shared).  The constraint triple is shared only if all three have a leading dimension
+    of 1; the residual-block form below still broadcasts by copying.
     OR the residual-block form (the reference's own cost model): layout = a qp.ResidualLayout, J_blocks [B, layout.values] the packed local
     Jacobians, r [B, layout.rows], lam as above; equalities, if any, as eq_layout, J_eq_blocks [B, eq_layout.values], r_eq [B, k] (A_eq = the
     stacked UpdateJacobian, b_eq = r_eq) instead of A_eq / b_eq.  Its gradients arrive in the packed layouts and are computed from the
@@ -559,20 +636,24 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     if ref.dim() != 3:
         raise ValueError("G / J must be [B, rows, n]")
     B = max(int(t.shape[0]) for t in (G, c, J, r, A_eq, b_eq, cons_a, cons_b) if t is not None)
+    if isinstance(lam, torch.Tensor):
+        B = max(B, int(lam.numel()))
     full = lambda t: _full(t, B)
+    one = lambda t: None if t is None else (t.contiguous() if int(t.shape[0]) == 1 else _full(t, B))   # given once: passed through
     lam_t = None
     if isinstance(lam, torch.Tensor):
         if J is None:
             raise ValueError("lam belongs to the (J, r) form")
-        lam_t = full(lam.reshape(-1))
+        lam_t = one(lam.reshape(-1))
     elif float(lam) != 0.0:
         if J is None:
             raise ValueError("lam belongs to the (J, r) form")
         lam_t = torch.full((B,), float(lam), dtype=ref.dtype, device=ref.device)
     _check_cons(cons_var, cons_a, cons_b)
-    A_t = None if A_eq is None else full(A_eq).transpose(1, 2).contiguous()   # BatchedQP's layout: memory = k x n column-major
-    v, status = QPSolveFunction.apply(full(G), full(c), full(J), full(r), lam_t, A_t, full(b_eq), full(cons_a), full(cons_b),
-                                      full(cons_var), params)
+    A_t = None if A_eq is None else one(A_eq).transpose(1, 2).contiguous()   # BatchedQP's layout: memory = k x n column-major
+    cons = one if cons_var is not None and all(int(t.shape[0]) == 1 for t in (cons_var, cons_a, cons_b)) else full
+    v, status = QPSolveFunction.apply(one(G), one(c), one(J), one(r), lam_t, A_t, one(b_eq), cons(cons_a), cons(cons_b),
+                                      cons(cons_var), params)
     k = 0 if A_eq is None else int(A_eq.shape[1])
     m = 0 if cons_a is None else int(cons_a.shape[1])
     return _result(v, status, int(ref.shape[2]), m, k, return_all, return_status)

@@ -15,7 +15,13 @@ read and write once).
 Residual-block input: mo_qp_gradients_blocks (dJ_blocks + dr + dlambda) against its yardstick in the same run, mo_qp_gradients (dJ + dr +
 dlambda) on the dense scattered stack of the same problems; the forward mo_linearize_blocks; solve_qp(layout=...) forward and backward as
 the user calls them (autograd and Python included).  The block launch moves 2 (values + rows) + 2 n elements per problem, the dense one
-2 m_r n."""
+2 m_r n.
+
+  shared_cfg3  n = 64, m = 32 box rows, (G, c) input, ONE G for the batch        shared_n128  n = 128, m = 64, m_r = 256, ONE J for the batch
+Data the batch shares: mo_qp_gradients_shared (dG, or dJ + dlambda) against the route without it, mo_qp_gradients
+per problem + a sum over the batch; solve_qp's forward with the shared input given once against the same input expanded by the caller;
+the whole backward of both.  Both routes in one process, alternating, best of the rounds, every timing around a synchronise.  The
+reduced launch reads 2 n (+ m_r for r) elements per problem; the per-problem route writes and reads back n^2 (m_r n) per problem."""
 import argparse
 import ctypes as C
 import json
@@ -219,6 +225,98 @@ def run_blocks(shape, dtype, batch, reps, warmup, rounds):
     return res
 
 
+SHARED_SHAPES = {"shared_cfg3": (64, 32, 0), "shared_n128": (128, 64, 256)}   # n, m box rows, m_r (0: (G, c) input)
+
+
+def wall(fn, reps):
+    torch.cuda.synchronize()
+    import time
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps
+
+
+def run_shared(shape, dtype, batch, reps, warmup, rounds):
+    n, m, m_r = SHARED_SHAPES[shape]
+    dev = torch.device("cuda:0")
+    elem = 8 if dtype == torch.float64 else 4
+    gen = torch.Generator(device=dev).manual_seed(49)
+    rnd = lambda *shape_: torch.rand(*shape_, dtype=dtype, device=dev, generator=gen) * 2 - 1   # noqa: E731
+    half = m // 2
+    var = torch.arange(half, dtype=torch.int32, device=dev).repeat(2)[None].contiguous()
+    a = torch.cat([torch.ones(half, dtype=dtype, device=dev), -torch.ones(half, dtype=dtype, device=dev)])[None].contiguous()
+    b = torch.full((1, m), 0.5, dtype=dtype, device=dev)                      # -0.5 <= x_i <= 0.5 for i < m / 2
+    cons = dict(cons_var=var, cons_a=a, cons_b=b)
+    if m_r:
+        one = dict(J=rnd(1, m_r, n))
+        per = dict(r=rnd(batch, m_r))
+        extra = dict(lam=1e-3)
+        name, members = "J", ("J", "lam")
+    else:
+        U = rnd(n, n)
+        one = dict(G=(U @ U.T / n + torch.eye(n, dtype=dtype, device=dev))[None].contiguous())
+        per = dict(c=rnd(batch, n))
+        extra = {}
+        name, members = "G", ("G",)
+    prm = Q.Params(max_iterations=10)
+    V = n + 2 * m
+    v = torch.randn(batch, V, dtype=dtype, device=dev, generator=gen)
+    u = torch.randn(batch, V, dtype=dtype, device=dev, generator=gen)
+    prob = Q.BatchedQP(n=n, m=m, lam=extra.get("lam", 0.0), **one, **per, **cons)
+    graphs = {}
+
+    def forward(key, expanded):
+        leaf = (one[name].expand(batch, *one[name].shape[1:]).contiguous() if expanded else one[name].clone()).requires_grad_(True)
+
+        def fn():
+            graphs[key] = (leaf, D.solve_qp(**{name: leaf}, **per, **extra, **cons, params=prm))
+        return fn
+
+    def backward(key):
+        def fn():
+            leaf, x = graphs[key]
+            leaf.grad = None
+            x.backward(torch.ones_like(x), retain_graph=True)
+        return fn
+
+    calls = {
+        "gradients_shared": lambda: D.qp_gradients_shared(prob, v, u, members),
+        "gradients_per_problem_then_sum": lambda: {key: t.sum(0, keepdim=True) for key, t in D.qp_gradients(prob, v, u, members).items()},
+        "solve_qp_forward_shared": forward("shared", False),
+        "solve_qp_forward_expanded": forward("expanded", True),
+        "solve_qp_backward_shared": backward("shared"),
+        "solve_qp_backward_expanded": backward("expanded"),
+    }
+    for fn in calls.values():
+        for _ in range(warmup):
+            fn()
+    best = {key: float("inf") for key in calls}
+    for _ in range(rounds):  # alternating rounds, best of
+        for key, fn in calls.items():
+            best[key] = min(best[key], wall(fn, reps if key.startswith("gradients") else 1))
+    mat = (m_r if m_r else n) * n
+    res = {"shape": shape, "n": n, "m": m, "m_r": m_r, "dtype": str(dtype).split(".")[-1], "batch": batch,
+           "chunks": S_chunks(batch, torch.cuda.get_device_properties(dev).multi_processor_count),
+           "forward_bit_equal": bool(torch.equal(graphs["shared"][1], graphs["expanded"][1]))}
+    res.update({key + "_s": t for key, t in best.items()})
+    res["shared_speedup_gradients"] = best["gradients_per_problem_then_sum"] / best["gradients_shared"]
+    res["shared_speedup_forward"] = best["solve_qp_forward_expanded"] / best["solve_qp_forward_shared"]
+    res["shared_speedup_backward"] = best["solve_qp_backward_expanded"] / best["solve_qp_backward_shared"]
+    res["gradients_shared_bytes"] = elem * (batch * (2 * n + m_r) + mat)                       # x, u_x (and r) of every problem in, one matrix out
+    res["gradients_per_problem_then_sum_bytes"] = elem * (batch * (2 * n + 2 * mat) + (mat if m_r else 0) + mat)   # ... + the matrix per problem out and in again
+    for key in ("gradients_shared", "gradients_per_problem_then_sum"):
+        res[key + "_TBps"] = res[key + "_bytes"] / best[key] / 1e12
+    return res
+
+
+def S_chunks(batch, cus):
+    c = max(1, min(cus, (batch + 31) // 32))
+    length = max(1, -(-batch // c))
+    return -(-batch // length)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="cfg3,ref8")
@@ -232,7 +330,7 @@ def main():
     L.build()
     lines = []
     for sh in a.shapes.split(","):
-        res = (run_blocks if sh in BLOCK_SHAPES else run)(sh, torch.float64 if a.dtype == "f64" else torch.float32, a.batch, a.reps, a.warmup, a.rounds)
+        res = (run_blocks if sh in BLOCK_SHAPES else run_shared if sh in SHARED_SHAPES else run)(sh, torch.float64 if a.dtype == "f64" else torch.float32, a.batch, a.reps, a.warmup, a.rounds)
         print(json.dumps(res), flush=True)
         lines.append(res)
         torch.cuda.empty_cache()

@@ -383,7 +383,9 @@ int32_t mo_residual_layout_rows(const mo_residual_layout* layout);     /* sum R_
 /* The cost half of LinearizeAndFillQP (nonlinear.cc:182-189) for block input: G_out (n x n col-major, lower written, strict upper written
  * as 0) = sum_b UpdateHessian (residual.hpp:186-226, the reference's summation order) + lambda I after the sum (lambda[_vec] added iff
  * > 0; lambda_vec NULL = the scalar), c_out = sum_b J_b^T r_b, half_sq_out[p] (may be NULL) = sum_b 0.5 |r_b|^2.  Requires sum R_b ==
- * plan m_r.  Deterministic: every cell is summed by one lane in a fixed order. */
+ * plan m_r.  Deterministic: every cell is summed by one lane in a fixed order.  G_out == NULL: only c_out and half_sq_out are formed (G_stride
+ * and G_ld are ignored), in the same order, so the bits of c are those of the full call -- for a caller whose G comes from elsewhere (one
+ * G for the whole batch, formed by a batch-1 call). */
 int mo_linearize_blocks(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
                         int64_t r_stride, double lambda, const void* lambda_vec, int64_t lambda_stride, int64_t batch, void* G_out,
                         int64_t G_stride, int32_t G_ld, void* c_out, int64_t c_stride, void* half_sq_out, void* stream);
@@ -514,6 +516,45 @@ int mo_qp_gradients_blocks(mo_plan* plan, const mo_residual_layout* cost_layout,
 int mo_qp_gradients_eq_blocks(mo_plan* plan, const mo_residual_layout* eq_layout, int64_t batch, const void* vars, int64_t vars_stride,
                               const void* u, int64_t u_stride, void* dJ_eq_blocks, int64_t dJ_eq_stride, void* dr_eq,
                               int64_t dr_eq_stride, void* stream);
+
+/* The block gradients SUMMED over the batch, for blocks the whole batch shares (a learned structured cost: the factor structure is fixed,
+ * the local Jacobians are the parameters of every sample, the residual values differ per sample).  J_blocks is ONE instance; r is per
+ * problem (r_stride != 0) or one instance too (r_stride == 0).  With the moments of mo_qp_gradients_shared, all sums over the problems
+ * that count -- M = sum u_x x^T, s_u = sum u_x, A1 = sum y u_x^T, A2 = sum u_y x^T, s_uy = sum u_y -- and i_p = idx_b[p]:
+ *   dJ_b[q, p] = -sum_p' J_b[q, p'] (M[i_p][i_p'] + M[i_p'][i_p]) - Q_b[q, p] + M[i_p][i_p] sum over the OTHER local columns q' on p's variable of J_b[q, q']
+ *   Q_b[q, p]  = sum over the problems of r[row_b + q] u_x[i_p]       (r[row_b + q] s_u[i_p] when r is shared too)
+ *   dr_b       = -sum_p' s_u[i_p'] J_b[:, p']       (only with r_stride == 0)       dlambda = -trace(M)   (ONE value: the caller masks it where lambda <= 0)
+ *   dJeq_b[q, a] = A1[row, i_a] - A2[row, i_a] if local column a wins its global column, else exactly 0       dr_eq = -s_uy
+ * that is mo_qp_gradients_blocks' and mo_qp_gradients_eq_blocks' outputs summed over the problems that count.  No per-problem matrix or
+ * packed gradient is written or read: the inputs are the two [batch][V] arrays, one instance of the blocks, and r.  Q is formed only at
+ * the packed positions, never as a rows x n matrix.
+ * The plan is that of the (G, c) solve (n, k, m, dtype, device), as for mo_qp_gradients_blocks; status_fwd / status_adj as for
+ * mo_qp_gradients_shared: a problem that does not count contributes exactly nothing, whatever its rows of vars / u / r hold.
+ * Arguments are judged before the plan is looked at.  MO_ERR_INVALID_ARGUMENT, with nothing written: NULL cost_layout / out; dr with
+ * r_stride != 0; dJ_blocks or dr without J_blocks and r; dJ_eq_blocks or dr_eq without eq_layout; a workspace smaller than the workspace
+ * query reports for the same arguments, or not 16-byte aligned.  MO_ERR_DIMENSION: a layout's n differs from the plan's, eq_layout's rows
+ * from the plan's k, vars_stride / u_stride < V.  With k = 0 the equality members are ignored.  MO_ERR_UNSUPPORTED: four problems' moment rows (x, u_x and,
+ * with an equality member, y, u_y; every vector padded to 16 values) exceed 64 KiB of LDS, or -- dJ_blocks with r_stride != 0 -- the
+ * (n + sum R_b) values of one problem (r and u_x, staged for the packed Q) exceed 64 KiB less the 64 bytes of that kernel's flags.  batch == 0 writes zeros.
+ * Stage 1 is mo_qp_gradients_shared's: the same chunks (a function of batch and CU count alone), the moments on the matrix cores, masked
+ * problems selected to zero.  The packed Q partials use the same chunks: one owner per packed value, r and u_x rows staged through LDS,
+ * summed in problem order, products rounded before they are added.  The finish sums the chunk partials in chunk order in double, forms
+ * every output from the totals in double through the layouts' schedules and rounds once.  Every workspace and output element has one
+ * owner: no atomics, no memset, the same bits on every launch of one device, and each member alone gets the bits it gets beside the
+ * others.  No allocation and no synchronisation on the launch path: at most four kernels on `stream`.  The workspace's contents are scratch. */
+typedef struct {            /* ONE instance per member; NULL = neither computed nor written */
+  void* dJ_blocks;          /* cost_layout values, the packing of J_blocks */
+  void* dr;                 /* cost_layout rows; only with r_stride == 0 */
+  void* dlambda;            /* 1 */
+  void* dJ_eq_blocks;       /* eq_layout values */
+  void* dr_eq;              /* k */
+} mo_block_shared_grads;
+int mo_qp_gradients_blocks_shared_workspace(const mo_plan* plan, const mo_residual_layout* cost_layout, const mo_residual_layout* eq_layout,
+                                            int64_t r_stride, int64_t batch, const mo_block_shared_grads* out, int64_t* bytes);
+int mo_qp_gradients_blocks_shared(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks /* one instance */, const void* r,
+                                  int64_t r_stride, const mo_residual_layout* eq_layout, int64_t batch, const void* vars, int64_t vars_stride,
+                                  const void* u, int64_t u_stride, const int32_t* status_fwd, const int32_t* status_adj,
+                                  const mo_block_shared_grads* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Forward mode: the directional derivative vdot = (dv* / dtheta) thetadot of the root of F(v; theta) = 0 along a direction thetadot in the
  * problem's data.  From F(v*(theta); theta) = 0 follows K vdot = -rho with rho = F_theta thetadot; the call below forms rho at the state

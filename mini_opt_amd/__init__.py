@@ -8,7 +8,8 @@ from . import _lib  # noqa: F401
 from ._lib import MiniOptError, build  # noqa: F401
 
 
-_DIFF_EXPORTS = ("solve_qp", "kkt_solve", "qp_gradients", "qp_gradients_shared", "qp_gradients_blocks", "qp_gradients_eq_blocks", "QPSolveFunction",
+_DIFF_EXPORTS = ("solve_qp", "kkt_solve", "qp_gradients", "qp_gradients_shared", "qp_gradients_blocks", "qp_gradients_eq_blocks",
+                 "qp_gradients_blocks_shared", "QPSolveFunction",
                  "QPSolveBlocksFunction", "adjoint_status", "qp_tangent_rhs", "qp_jvp", "tangent_status",
                  "qp_tangent_rhs_blocks", "qp_jvp_blocks")
 

@@ -36,7 +36,8 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_residual_layout_create", "mo_residual_layout_destroy", "mo_residual_layout_values", "mo_residual_layout_rows",
            "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks", "mo_kkt_solve", "mo_qp_gradients",
            "mo_qp_gradients_shared_workspace", "mo_qp_gradients_shared",
-           "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_tangent_rhs", "mo_qp_tangent_rhs_blocks"]
+           "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_gradients_blocks_shared_workspace", "mo_qp_gradients_blocks_shared",
+           "mo_qp_tangent_rhs", "mo_qp_tangent_rhs_blocks"]
 
 
 class PlanDesc(C.Structure):
@@ -118,6 +119,11 @@ class BlockGrads(C.Structure):
                 ("dlambda", C.c_void_p), ("dlambda_stride", C.c_int64)]
 
 
+class BlockSharedGrads(C.Structure):
+    """mo_block_shared_grads: optional device outputs of mo_qp_gradients_blocks_shared, ONE instance per member."""
+    _fields_ = [("dJ_blocks", C.c_void_p), ("dr", C.c_void_p), ("dlambda", C.c_void_p), ("dJ_eq_blocks", C.c_void_p), ("dr_eq", C.c_void_p)]
+
+
 class BlockTangents(C.Structure):
     """mo_block_tangents: optional device inputs of mo_qp_tangent_rhs_blocks, in the packed layouts of the residual-block input (a NULL member is
     a zero tangent; stride 0 = shared by the batch)."""
@@ -144,7 +150,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "tools", "isa_lint.py"))   # the build lints its own listings: a changed lint re-runs it
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
-        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (seventeen units, the longest 5.7 min)
+        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (eighteen units, the longest 5.7 min)
         subprocess.check_call(["make", "-C", CSRC, f"-j{jobs}"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
@@ -209,6 +215,8 @@ def lib() -> C.CDLL:
     L.mo_qp_gradients_shared.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, i64, vp, vp, C.POINTER(QPGrads), vp, i64, vp]
     L.mo_qp_gradients_blocks.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.POINTER(BlockGrads), vp]
     L.mo_qp_gradients_eq_blocks.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.mo_qp_gradients_blocks_shared_workspace.argtypes = [vp, vp, vp, i64, i64, C.POINTER(BlockSharedGrads), C.POINTER(i64)]
+    L.mo_qp_gradients_blocks_shared.argtypes = [vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, C.POINTER(BlockSharedGrads), vp, i64, vp]
     L.mo_qp_tangent_rhs.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, C.POINTER(QPTangents), vp, i64, vp]
     L.mo_qp_tangent_rhs_blocks.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, C.POINTER(BlockTangents), vp, i64, vp]
     for name in EXPORTS:

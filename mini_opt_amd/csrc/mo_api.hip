@@ -1282,8 +1282,8 @@ int mo_linearize_blocks(mo_plan* plan, const mo_residual_layout* layout, const v
   if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
   if (layout->rows != plan->desc.m_r) return fail(MO_ERR_DIMENSION, "layout has %d rows, plan m_r = %d", layout->rows, plan->desc.m_r);
   if (!J_blocks || !r) return fail(MO_ERR_INVALID_ARGUMENT, "J_blocks / r is NULL");
-  if (!G_out || !c_out) return fail(MO_ERR_INVALID_ARGUMENT, "G_out / c_out is NULL");
-  if (G_ld < plan->desc.n) return fail(MO_ERR_DIMENSION, "G_ld %d < n", G_ld);
+  if (!c_out) return fail(MO_ERR_INVALID_ARGUMENT, "c_out is NULL");
+  if (G_out && G_ld < plan->desc.n) return fail(MO_ERR_DIMENSION, "G_ld %d < n", G_ld);   // (G_out NULL: c_out and half_sq_out only)
   if (batch == 0) return MO_OK;
   mo::BlocksArgs a = blocks_args(layout, batch);
   a.J = J_blocks; a.J_stride = J_stride; a.r = r; a.r_stride = r_stride;
@@ -1358,6 +1358,79 @@ int mo_qp_gradients_eq_blocks(mo_plan* plan, const mo_residual_layout* eq_layout
   a.dJ = dJ_eq_blocks; a.dJ_stride = dJ_eq_stride; a.dr = dr_eq; a.dr_stride = dr_eq_stride;
   MO_HIP_CHECK(hipSetDevice(plan->desc.device));
   MO_HIP_CHECK(mo::launch_blocks_eq_grad(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// What mo_qp_gradients_blocks_shared and its workspace query judge alike: first what the arguments alone tell, then the plan, the layouts
+// and the LDS rule.  J_blocks / r / vars / u / the workspace are not looked at here.
+int block_shared_args(const mo_plan* plan, const mo_residual_layout* cost_layout, const mo_residual_layout* eq_layout, int64_t r_stride,
+                      int64_t batch, const mo_block_shared_grads* out, mo::BlockSharedArgs* a) {
+  if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (out->dr && r_stride != 0)
+    return fail(MO_ERR_INVALID_ARGUMENT, "dr summed over the batch needs one r for the batch: r_stride is %lld, not 0", (long long)r_stride);
+  if ((out->dJ_eq_blocks || out->dr_eq) && !eq_layout) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_eq_blocks / dr_eq asked for but eq_layout is NULL");
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, cost_layout)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  memset(a, 0, sizeof(*a));
+  a->out = *out;
+  if (d.k == 0) { a->out.dJ_eq_blocks = nullptr; a->out.dr_eq = nullptr; }   // (with k = 0 the equality members and the layout are ignored)
+  if (eq_layout && d.k > 0) {
+    if (int rc = check_layout(plan, eq_layout)) return rc;
+    if (eq_layout->rows != d.k) return fail(MO_ERR_DIMENSION, "eq_layout has %d rows, plan k = %d", eq_layout->rows, d.k);
+    a->e_val = eq_layout->e_val; a->eq_values = eq_layout->values;
+  }
+  a->n = d.n; a->k = d.k; a->m = d.m; a->rows = cost_layout->rows; a->values = cost_layout->values; a->batch = batch;
+  a->d_row = cost_layout->d_row; a->d_idx = cost_layout->d_idx; a->d_val = cost_layout->d_val; a->d_dup = cost_layout->d_dup;
+  a->r_stride = r_stride;
+  if (!mo::blocks_shared_fits(*a, plan->elem))
+    return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, %d residual rows: four problems' moment rows, or the r and u_x of one problem beside 64 bytes of flags, exceed the 64 KiB of LDS the batch-reduced block gradient uses",
+                d.n, d.k, cost_layout->rows);
+  return MO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mo_qp_gradients_blocks_shared_workspace(const mo_plan* plan, const mo_residual_layout* cost_layout, const mo_residual_layout* eq_layout,
+                                            int64_t r_stride, int64_t batch, const mo_block_shared_grads* out, int64_t* bytes) {
+  g_err[0] = 0;
+  if (!bytes) return fail(MO_ERR_INVALID_ARGUMENT, "bytes is NULL");
+  mo::BlockSharedArgs a;
+  if (int rc = block_shared_args(plan, cost_layout, eq_layout, r_stride, batch, out, &a)) return rc;
+  *bytes = (int64_t)mo::blocks_shared_workspace_bytes(a, plan->elem, plan->num_cus);
+  return MO_OK;
+}
+
+int mo_qp_gradients_blocks_shared(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, const void* r, int64_t r_stride,
+                                  const mo_residual_layout* eq_layout, int64_t batch, const void* vars, int64_t vars_stride, const void* u,
+                                  int64_t u_stride, const int32_t* status_fwd, const int32_t* status_adj, const mo_block_shared_grads* out,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (out && (out->dJ_blocks || out->dr) && (!J_blocks || !r)) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_blocks / dr asked for but J_blocks / r is NULL");
+  if (batch > 0 && (!vars || !u)) return fail(MO_ERR_INVALID_ARGUMENT, "vars / u is NULL");
+  mo::BlockSharedArgs a;
+  if (int rc = block_shared_args(plan, cost_layout, eq_layout, r_stride, batch, out, &a)) return rc;
+  const int V = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
+  if (batch > 1 && (vars_stride < V || u_stride < V)) return fail(MO_ERR_DIMENSION, "vars_stride %lld / u_stride %lld < V = %d", (long long)vars_stride, (long long)u_stride, V);
+  const int64_t need = (int64_t)mo::blocks_shared_workspace_bytes(a, plan->elem, plan->num_cus);
+  if (!workspace || workspace_bytes < need)
+    return fail(MO_ERR_INVALID_ARGUMENT, "workspace too small: %lld bytes given, %lld needed (mo_qp_gradients_blocks_shared_workspace)", (long long)(workspace ? workspace_bytes : 0), (long long)need);
+  if ((uintptr_t)workspace & 15) return fail(MO_ERR_INVALID_ARGUMENT, "workspace is not 16-byte aligned");
+  const mo_block_shared_grads& o = a.out;
+  if (!o.dJ_blocks && !o.dr && !o.dlambda && !o.dJ_eq_blocks && !o.dr_eq) return MO_OK;
+  a.J = J_blocks; a.r = r;
+  a.vars = vars; a.vars_stride = vars_stride; a.u = u; a.u_stride = u_stride;
+  a.status_fwd = status_fwd; a.status_adj = status_adj;
+  a.workspace = workspace;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_blocks_shared_grad(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
   return MO_OK;
 }
 

@@ -258,6 +258,40 @@ size_t shared_grad_workspace_bytes(const SharedGradArgs& a, int elem_size, int n
 size_t shared_grad_lds_bytes(const SharedGradArgs& a, int elem_size);
 hipError_t launch_qp_gradients_shared(const SharedGradArgs& a, int dtype, int num_cus, hipStream_t stream);
 
+// stage 1 alone -- qp_moment_kernel -- for a caller with a finish of its own (the block form below).  MomentNeeds names the tile families and
+// vector sums to accumulate instead of deriving them from `out`; Q (with r, r_stride and m_r of the args) is the dense form's.
+struct MomentNeeds { int M, A, Q, y, z; };   // M = u_x x^T; A1 = y u_x^T and A2 = u_y x^T; Q = r u_x^T; s_uy; s_uz and dcons_a
+// how the chunk partials lie at `workspace`: chunk c's block of chunk_elems values = `tiles` row-major 16 x 16 tiles -- M (ntn x ntn of them,
+// row-major over (tile row, tile column)), then A1, then A2 (a_tiles each) -- and the vector sums [s_u n | s_uy k | s_uz m | dcons_a m]
+struct MomentLayout {
+  int ntn, m_tiles, a_tiles, tiles, vec_pad;
+  long long chunks, chunk_elems;
+};
+MomentLayout shared_moment_layout(const SharedGradArgs& a, const MomentNeeds& needs, int elem_size, int num_cus);
+size_t shared_moment_lds_bytes(const SharedGradArgs& a, const MomentNeeds& needs, int elem_size);
+hipError_t launch_qp_moments(const SharedGradArgs& a, const MomentNeeds& needs, int dtype, int num_cus, hipStream_t stream);
+
+// the gradients of the packed blocks SUMMED over the batch, for blocks the whole batch shares (mo_qp_gradients_blocks_shared),
+// qp_grad_blocks_shared.hip: the moments above, the packed Q = sum r_p[row] u_x,p[index] per chunk, and a finish that gathers through the
+// layouts' backward schedules.  J is ONE instance; r is per problem (r_stride != 0: read by the Q kernel) or one instance too.
+struct BlockSharedArgs {
+  int n, k, m, rows;          // plan n, k, m; sum R_b of the cost layout
+  long long values, eq_values;
+  long long batch;
+  const int4* d_row; const int* d_idx; const int4* d_val; const int* d_dup;   // cost layout (BlockGradArgs)
+  const int2* e_val;          // equality layout: {stacked row, global index or -1}
+  const void* J;
+  const void* r; long long r_stride;
+  const void* vars; long long vars_stride;
+  const void* u; long long u_stride;
+  const int* status_fwd; const int* status_adj;
+  mo_block_shared_grads out;  // NULL members are neither computed nor written
+  void* workspace;            // blocks_shared_workspace_bytes, 16-byte aligned
+};
+size_t blocks_shared_workspace_bytes(const BlockSharedArgs& a, int elem_size, int num_cus);
+bool blocks_shared_fits(const BlockSharedArgs& a, int elem_size);   // the LDS rule of mo_qp_gradients_blocks_shared
+hipError_t launch_blocks_shared_grad(const BlockSharedArgs& a, int dtype, int num_cus, hipStream_t stream);
+
 // forward-mode right-hand side rho = F_theta thetadot of a QP (mo_qp_tangent_rhs), qp_tangent.hip: the transpose of the gradient kernel
 // above.  r is read only against the dJ tangent, cons_var whenever the problem has one.
 struct TangentArgs : SensArgs {

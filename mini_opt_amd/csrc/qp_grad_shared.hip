@@ -13,6 +13,7 @@
 // partial tiles once: one owner per workspace element, no atomics, no memset.
 // Stage 2, qp_moment_finish_kernel: pass 0 sums the chunk partials of every element in chunk order, in double; pass 1 forms the outputs from
 // those totals in double (the products with J on the VALU, ascending index) and rounds once.
+// Stage 1 alone is also what mo_qp_gradients_blocks_shared starts with (launch_qp_moments; its finish is in qp_grad_blocks_shared.hip).
 #include <string.h>
 
 #include "mo_sens_device.h"
@@ -311,17 +312,28 @@ int row_stride(int width, int elem) {
   return S;
 }
 
-MomentArgs plan_of(const SharedGradArgs& g, int elem, int num_cus) {
+// the moments the members of mo_qp_gradients_shared ask for
+MomentNeeds needs_of(const SharedGradArgs& g) {
+  const mo_qp_grads& o = g.out;
+  MomentNeeds nd;
+  nd.M = o.dG || o.dJ || o.dlambda;
+  nd.A = o.dA_eq && g.k > 0;
+  nd.Q = o.dJ && g.r_stride != 0;   // a shared r: Q = r s_u^T, formed by the finish kernel
+  nd.y = g.k > 0 && (o.dA_eq || o.db_eq);
+  nd.z = g.m > 0 && (o.dcons_a || o.dcons_b);
+  return nd;
+}
+
+MomentArgs plan_of(const SharedGradArgs& g, const MomentNeeds& nd, int elem, int num_cus) {
   MomentArgs a;
   memset(&a, 0, sizeof(a));
   a.g = g;
   const mo_qp_grads& o = g.out;
   const int n = g.n, k = g.k, m = g.m, m_r = g.m_r;
   a.ntn = (n + 15) / 16;
-  const bool need_M = o.dG || o.dJ || o.dlambda;
-  a.m_tiles = need_M ? a.ntn * a.ntn : 0;
-  a.a_tiles = (o.dA_eq && k > 0) ? ((k + 15) / 16) * a.ntn : 0;
-  a.has_r = o.dJ && g.r_stride != 0;   // a shared r: Q = r s_u^T, formed by the finish kernel
+  a.m_tiles = nd.M ? a.ntn * a.ntn : 0;
+  a.a_tiles = nd.A ? ((k + 15) / 16) * a.ntn : 0;
+  a.has_r = nd.Q;
   a.q_tiles = a.has_r ? ((m_r + 15) / 16) * a.ntn : 0;
   a.tiles = a.m_tiles + 2 * a.a_tiles + a.q_tiles;
   a.vec = n + k + 2 * m;
@@ -329,8 +341,8 @@ MomentArgs plan_of(const SharedGradArgs& g, int elem, int num_cus) {
   a.chunk_len = shared_grad_chunk_len(g.batch, num_cus);
   a.chunks = shared_grad_chunks(g.batch, num_cus);
   a.chunk_elems = (long long)a.tiles * 256 + a.vec_pad;
-  a.has_y = k > 0 && (o.dA_eq || o.db_eq);
-  a.has_z = m > 0 && (o.dcons_a || o.dcons_b);
+  a.has_y = nd.y;
+  a.has_z = nd.z;
   int w = 0;
   auto seg = [&w](int len, bool present) { const int at = w; if (present) w += (len + 15) & ~15; return at; };
   a.off_x = seg(n, true); a.off_ux = seg(n, true);
@@ -350,6 +362,8 @@ MomentArgs plan_of(const SharedGradArgs& g, int elem, int num_cus) {
   return a;
 }
 
+MomentArgs plan_of(const SharedGradArgs& g, int elem, int num_cus) { return plan_of(g, needs_of(g), elem, num_cus); }
+
 size_t lds_of(const MomentArgs& a, int elem) { return ((size_t)a.stage * a.S + a.vec_pad) * elem; }
 
 }  // namespace
@@ -361,18 +375,42 @@ size_t shared_grad_workspace_bytes(const SharedGradArgs& g, int elem_size, int n
 
 size_t shared_grad_lds_bytes(const SharedGradArgs& g, int elem_size) { return lds_of(plan_of(g, elem_size, 1), elem_size); }
 
+// stage 1: a workgroup per (chunk, group of tiles); none for an empty batch
+static hipError_t launch_moments(const MomentArgs& a, int dtype, size_t lds, hipStream_t stream) {
+  if (a.chunks <= 0) return hipSuccess;
+  const int groups = (a.tiles + kTilesPerGroup - 1) / kTilesPerGroup;   // (none: group 0 still owns the column sums)
+  const dim3 grid((unsigned)a.chunks, (unsigned)(groups > 0 ? groups : 1));
+  if (dtype == MO_F64) hipLaunchKernelGGL(qp_moment_kernel<double>, grid, dim3(kThreads), lds, stream, a);
+  else hipLaunchKernelGGL(qp_moment_kernel<float>, grid, dim3(kThreads), lds, stream, a);
+  return hipGetLastError();
+}
+
+MomentLayout shared_moment_layout(const SharedGradArgs& g, const MomentNeeds& needs, int elem_size, int num_cus) {
+  const MomentArgs a = plan_of(g, needs, elem_size, num_cus);
+  MomentLayout l;
+  l.ntn = a.ntn; l.m_tiles = a.m_tiles; l.a_tiles = a.a_tiles; l.tiles = a.tiles; l.vec_pad = a.vec_pad;
+  l.chunks = a.chunks; l.chunk_elems = a.chunk_elems;
+  return l;
+}
+
+size_t shared_moment_lds_bytes(const SharedGradArgs& g, const MomentNeeds& needs, int elem_size) {
+  return lds_of(plan_of(g, needs, elem_size, 1), elem_size);
+}
+
+hipError_t launch_qp_moments(const SharedGradArgs& g, const MomentNeeds& needs, int dtype, int num_cus, hipStream_t stream) {
+  const int elem = dtype == MO_F64 ? 8 : 4;
+  const MomentArgs a = plan_of(g, needs, elem, num_cus);
+  const size_t lds = lds_of(a, elem);
+  if (lds > 64 * 1024) return hipErrorInvalidValue;   // (mo_qp_gradients_blocks_shared refuses such shapes with its own message)
+  return launch_moments(a, dtype, lds, stream);
+}
+
 hipError_t launch_qp_gradients_shared(const SharedGradArgs& g, int dtype, int num_cus, hipStream_t stream) {
   const int elem = dtype == MO_F64 ? 8 : 4;
   const MomentArgs a = plan_of(g, elem, num_cus);
   const size_t lds = lds_of(a, elem);
   if (lds > 64 * 1024) return hipErrorInvalidValue;   // (mo_qp_gradients_shared refuses such shapes with its own message)
-  if (a.chunks > 0) {
-    const int groups = (a.tiles + kTilesPerGroup - 1) / kTilesPerGroup;   // (none: group 0 still owns the column sums)
-    const dim3 grid((unsigned)a.chunks, (unsigned)(groups > 0 ? groups : 1));
-    if (dtype == MO_F64) hipLaunchKernelGGL(qp_moment_kernel<double>, grid, dim3(kThreads), lds, stream, a);
-    else hipLaunchKernelGGL(qp_moment_kernel<float>, grid, dim3(kThreads), lds, stream, a);
-    if (hipError_t e = hipGetLastError()) return e;
-  }
+  if (hipError_t e = launch_moments(a, dtype, lds, stream)) return e;
   // pass 0: one thread per workspace element of a chunk; pass 1: one thread per 16-byte piece (or element) of the largest output
   long long work0 = (a.chunk_elems + kThreads - 1) / kThreads;
   long long largest = (long long)g.n * g.n;

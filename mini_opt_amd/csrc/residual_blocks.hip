@@ -56,8 +56,8 @@ __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const Blocks
     }
     const T lam = a.lambda_vec ? ((const T*)a.lambda_vec)[p * a.lambda_vec_stride] : (T)a.lambda;
     T* G = (T*)a.G_out + p * a.G_out_stride;
-    // consecutive lanes own consecutive cells of G's column-major order: whole-line stores when G_ld == n
-    for (int cell = tid; cell < nn; cell += kThreads) {
+    // consecutive lanes own consecutive cells of G's column-major order: whole-line stores when G_ld == n.  (G_out NULL: c and half_sq only)
+    for (int cell = tid; a.G_out && cell < nn; cell += kThreads) {
       const int col = cell / n, row = cell - col * n;
       const int e1 = a.g_ptr[cell + 1];
       T s = 0;

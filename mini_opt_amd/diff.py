@@ -4,6 +4,7 @@
     qp_gradients    mo_qp_gradients  gradients of a loss with respect to the QP's data from the state v and the adjoint u = K^-T g
     qp_gradients_shared    mo_qp_gradients_shared  the same gradients SUMMED over the batch, for data the whole batch shares
     qp_gradients_blocks, qp_gradients_eq_blocks    the same for residual-block input: gradients of the PACKED local Jacobians
+    qp_gradients_blocks_shared    mo_qp_gradients_blocks_shared  those gradients SUMMED over the batch, for blocks the whole batch shares
     qp_tangent_rhs  mo_qp_tangent_rhs  forward mode: rho = F_theta thetadot from the state v and a direction in the QP's data
     qp_jvp          qp_tangent_rhs + kkt_solve: the directional derivative vdot of the whole solution [x | s | y | z]
     qp_tangent_rhs_blocks, qp_jvp_blocks    the same for residual-block input: rho from the PACKED tangents of the blocks
@@ -182,9 +183,8 @@ def qp_gradients_shared(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor,
     want = tuple(want)
     _check_dense_names(problem, want, "gradient")
     dt, dev = problem.dtype, problem.device
-    for name, st in (("status_fwd", status_fwd), ("status_adj", status_adj)):
-        if st is not None and (st.dtype != torch.int32 or tuple(st.shape) != (B,) or not st.is_contiguous() or st.device != dev):
-            raise ValueError(f"{name}: expected a contiguous [{B}] int32 tensor on {dev}")
+    _check_status(status_fwd, "status_fwd", B, dev)
+    _check_status(status_adj, "status_adj", B, dev)
     new = lambda *shape: torch.empty(1, *shape, dtype=dt, device=dev)
     out: Dict[str, torch.Tensor] = {}
     g = L.QPGrads()
@@ -444,6 +444,72 @@ def qp_gradients_eq_blocks(eq_layout: ResidualLayout, vars: torch.Tensor, u: tor
     return out
 
 
+def _check_status(st: Optional[torch.Tensor], name: str, B: int, dev) -> None:
+    if st is not None and (st.dtype != torch.int32 or tuple(st.shape) != (B,) or not st.is_contiguous() or st.device != dev):
+        raise ValueError(f"{name}: expected a contiguous [{B}] int32 tensor on {dev}")
+
+
+BLOCK_GRADIENTS = ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq")
+
+
+def qp_gradients_blocks_shared(layout: ResidualLayout, J_blocks: Optional[torch.Tensor], r: Optional[torch.Tensor], vars: torch.Tensor,
+                               u: torch.Tensor, k: int = 0, m: int = 0, want: Iterable[str] = ("J_blocks", "lam"),
+                               eq_layout: Optional[ResidualLayout] = None, status_fwd: Optional[torch.Tensor] = None,
+                               status_adj: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """mo_qp_gradients_blocks_shared: the gradients of qp_gradients_blocks / qp_gradients_eq_blocks named in `want`, SUMMED over the batch,
+    for packed blocks the whole batch shares: "J_blocks" [1, values], "r" [1, rows], "lam" [1], "J_eq_blocks" [1, eq_layout.values],
+    "r_eq" [1, k].  J_blocks [1, values] and r [B or 1, rows] are needed (and read) only with "J_blocks" / "r"; "r" needs r [1, rows].
+    k, m: the (G, c) problem's equality and inequality rows (k = eq_layout.rows when an eq_layout is given).  status_fwd / status_adj: [B]
+    int32 status words; a problem counts iff every given word is MO_STATUS_OK (its rows of `vars` / `u` / `r` may then hold anything).
+    No [B, values] gradient is formed: the workspace (chunk partials, from torch's allocator) is a few tiles and packed values per CU."""
+    want = tuple(want)
+    if eq_layout is not None:
+        if eq_layout.n != layout.n or eq_layout.dtype != layout.dtype or eq_layout.device != layout.device:
+            raise ValueError("eq_layout must share n, dtype and device with layout")
+        k = eq_layout.rows
+    k, m = int(k), int(m)
+    _check_names(want, "gradient", BLOCK_GRADIENTS, ("J_eq_blocks", "r_eq") if eq_layout is None or k == 0 else ())
+    V = layout.n + 2 * m + k
+    B = _check_state_pair(vars, u, "u", V, layout)
+    dt, dev = layout.dtype, layout.device
+    _check_status(status_fwd, "status_fwd", B, dev)
+    _check_status(status_adj, "status_adj", B, dev)
+    keep = []
+    J_ptr = r_ptr = None
+    r_stride = 0
+    if "J_blocks" in want or "r" in want:
+        J_ptr, _ = _take(J_blocks, "J_blocks", (layout.values,), 1, dt, dev, keep)          # ONE instance
+        r_ptr, r_stride = _take(r, "r", (layout.rows,), B, dt, dev, keep)
+        if "r" in want and int(r.shape[0]) != 1:
+            raise ValueError("gradient 'r' summed over the batch needs r [1, rows]")
+    new = lambda *shape: torch.empty(1, *shape, dtype=dt, device=dev)
+    out: Dict[str, torch.Tensor] = {}
+    g = L.BlockSharedGrads()
+    if "J_blocks" in want:
+        out["J_blocks"] = new(layout.values)
+        g.dJ_blocks = _ptr(out["J_blocks"])
+    if "r" in want:
+        out["r"] = new(layout.rows)
+        g.dr = _ptr(out["r"])
+    if "lam" in want:
+        out["lam"] = new()
+        g.dlambda = _ptr(out["lam"])
+    if "J_eq_blocks" in want:
+        out["J_eq_blocks"] = new(eq_layout.values)
+        g.dJ_eq_blocks = _ptr(out["J_eq_blocks"])
+    if "r_eq" in want:
+        out["r_eq"] = new(k)
+        g.dr_eq = _ptr(out["r_eq"])
+    plan = _plan_of(layout.n, k, m, 0, dt, dev, B)
+    eq_h = None if eq_layout is None else eq_layout.h
+    nbytes = C.c_int64()
+    L.check(L.lib().mo_qp_gradients_blocks_shared_workspace(plan, layout.h, eq_h, r_stride, B, C.byref(g), C.byref(nbytes)))
+    work = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
+    L.check(L.lib().mo_qp_gradients_blocks_shared(plan, layout.h, J_ptr, r_ptr, r_stride, eq_h, B, _ptr(vars), V, _ptr(u), V, _ptr(status_fwd),
+                                                  _ptr(status_adj), C.byref(g), _ptr(work), int(work.numel()), _stream()))
+    return out
+
+
 BLOCK_TANGENTS = ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq", "cons_a", "cons_b")
 
 
@@ -517,22 +583,36 @@ def qp_jvp_blocks(problem: BatchedQP, layout: ResidualLayout, J_blocks: torch.Te
 class QPSolveBlocksFunction(torch.autograd.Function):
     """QPSolveFunction for residual-block input.  forward(J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, cons_var, layout, eq_layout,
     params) -> (v, status): linearize_blocks gives (G, c), jacobian_blocks gives A_eq (b_eq = r_eq), mo_qp_solve runs on the (G, c) problem --
-    the sequence of mo_nls_solve_blocks.  The backward solves K(v)^T u = g once on that problem (the fused right-hand-side twin where
-    kkt_solve_kernel says so), launches mo_qp_gradients_blocks once, mo_qp_gradients_eq_blocks if an equality input requires a gradient and
-    mo_qp_gradients for cons_a / cons_b if asked.  No n x n or m_r x n gradient is formed.  lam's gradient counts only where lam was added
-    (lam > 0).  Zero gradients for problems whose forward or adjoint status is not OK, as QPSolveFunction."""
+    the sequence of mo_nls_solve_blocks.  Every tensor has a leading dimension of B or of 1 (given once for the batch: read with stride 0,
+    never expanded; the constraint triple all three or none).  With J_blocks AND lam given once, G is formed ONCE, [1, n, n], and c by the
+    c-only linearize; a J_eq_blocks given once gives A_eq [1, n, k].  The backward solves K(v)^T u = g once on that problem (the fused
+    right-hand-side twin where kkt_solve_kernel says so); inputs per problem go to mo_qp_gradients_blocks, mo_qp_gradients_eq_blocks and
+    mo_qp_gradients (cons_a / cons_b), inputs given once to ONE mo_qp_gradients_blocks_shared launch (and mo_qp_gradients_shared for
+    cons_a / cons_b): their gradients are summed over the batch by the kernels and arrive as [1, ...].  No n x n or m_r x n gradient is
+    formed.  lam's gradient counts only where lam was added (lam > 0).  Zero gradients for problems whose forward or adjoint status is not
+    OK, as QPSolveFunction."""
+
+    NAMES = ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq", "cons_a", "cons_b")
 
     @staticmethod
     def forward(ctx, J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, cons_var, layout, eq_layout, params):
         det = lambda t: None if t is None else t.detach()
         J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b = (det(t) for t in (J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b))
-        G, c, _ = linearize_blocks(layout, J_blocks, r, lam_vec=lam)
-        B, n = int(G.shape[0]), layout.n
+        inputs = (J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b)
+        B = max(int(t.shape[0]) for t in inputs if t is not None)
+        once = lambda t: int(t.shape[0]) == 1 and B > 1
+        ctx.shared = frozenset(nm for nm, t in zip(QPSolveBlocksFunction.NAMES, inputs) if t is not None and once(t))
+        if once(J_blocks) and once(lam):   # one G for the batch: a batch-1 linearize; c from the call that forms no G
+            G, _, _ = linearize_blocks(layout, J_blocks, r[:1], lam_vec=lam)
+            _, c, _ = linearize_blocks(layout, J_blocks, r, lam_vec=lam, want_G=False)
+        else:
+            G, c, _ = linearize_blocks(layout, J_blocks, r, lam_vec=lam, batch=B)
+        n = layout.n
         k = 0 if eq_layout is None else eq_layout.rows
         m = 0 if cons_a is None else int(cons_a.shape[1])
         A_eq = None
-        if eq_layout is not None:
-            A_eq, _ = jacobian_blocks(eq_layout, J_eq_blocks, r_eq)       # [B, n, k]: memory = k x n column-major, BatchedQP's layout
+        if eq_layout is not None:   # [B or 1, n, k]: memory = k x n column-major, BatchedQP's layout (r_eq is not read: no |r|_1 is kept)
+            A_eq, _ = jacobian_blocks(eq_layout, J_eq_blocks, r_eq[:1] if once(J_eq_blocks) else r_eq)
         problem = BatchedQP(n=n, k=k, m=m, G=G, c=c, A_eq=A_eq, b_eq=r_eq if k else None, cons_var=cons_var, cons_a=cons_a, cons_b=cons_b)
         ctx.layout, ctx.eq_layout, ctx.J_blocks, ctx.r, ctx.lam = layout, eq_layout, J_blocks, r, lam
         return _solve_forward(ctx, problem, B, params)
@@ -540,17 +620,37 @@ class QPSolveBlocksFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_status):
         problem, v, u, ok = _adjoint(ctx, g)
-        need = ctx.needs_input_grad
-        want = [nm for nm, nd in zip(("J_blocks", "r", "lam"), need[:3]) if nd]
-        cost = qp_gradients_blocks(ctx.layout, ctx.J_blocks, ctx.r, v, u, k=problem.k, m=problem.m, want=want) if want else {}
-        if "lam" in cost:
-            cost["lam"] = torch.where(ctx.lam > 0, cost["lam"], torch.zeros((), dtype=v.dtype, device=v.device))
-        want = [nm for nm, nd in zip(("J_eq_blocks", "r_eq"), need[3:5]) if nd]
-        eq = qp_gradients_eq_blocks(ctx.eq_layout, v, u, m=problem.m, want=want) if want else {}
-        want = [nm for nm, nd in zip(("cons_a", "cons_b"), need[5:7]) if nd]
-        cons = qp_gradients(problem, v, u, want) if want else {}
-        out = [cost.get("J_blocks"), cost.get("r"), cost.get("lam"), eq.get("J_eq_blocks"), eq.get("r_eq"), cons.get("cons_a"), cons.get("cons_b")]
-        return (*[_masked(t, ok) for t in out], None, None, None, None)
+        names = QPSolveBlocksFunction.NAMES
+        want = [nm for nm, nd in zip(names, ctx.needs_input_grad[:7]) if nd]
+        # summed by the kernels: what the batch shares -- but "r" given once against J_blocks per problem, which the reduced launch refuses
+        # (dr = -sum s_u J_b needs one J_blocks): that one is formed per problem and summed here
+        summed = [nm for nm in want if nm in ctx.shared and not (nm == "r" and "J_blocks" not in ctx.shared)]
+        each = [nm for nm in want if nm not in summed]
+        grads: Dict[str, torch.Tensor] = {}
+        sel = lambda group, among: [nm for nm in group if nm in among]
+        cost, eq, cons = sel(each, ("J_blocks", "r", "lam")), sel(each, ("J_eq_blocks", "r_eq")), sel(each, ("cons_a", "cons_b"))
+        if cost:
+            grads.update(qp_gradients_blocks(ctx.layout, ctx.J_blocks, ctx.r, v, u, k=problem.k, m=problem.m, want=cost))
+        if eq:
+            grads.update(qp_gradients_eq_blocks(ctx.eq_layout, v, u, m=problem.m, want=eq))
+        if cons:
+            grads.update(qp_gradients(problem, v, u, cons))
+        if "lam" in grads:
+            grads["lam"] = torch.where(ctx.lam > 0, grads["lam"], torch.zeros((), dtype=v.dtype, device=v.device))
+        grads = {nm: _masked(t, ok) for nm, t in grads.items()}
+        for nm in each:
+            if nm in ctx.shared:
+                grads[nm] = grads[nm].sum(0, keepdim=True)
+        blocks, cons = sel(summed, BLOCK_GRADIENTS), sel(summed, ("cons_a", "cons_b"))
+        if blocks:
+            red = qp_gradients_blocks_shared(ctx.layout, ctx.J_blocks, ctx.r, v, u, k=problem.k, m=problem.m, want=blocks, eq_layout=ctx.eq_layout,
+                                             status_fwd=ctx.status, status_adj=ctx.adjoint_status)
+            if "lam" in red:
+                red["lam"] = torch.where(ctx.lam > 0, red["lam"], torch.zeros((), dtype=v.dtype, device=v.device))
+            grads.update(red)
+        if cons:
+            grads.update(qp_gradients_shared(problem, v, u, cons, status_fwd=ctx.status, status_adj=ctx.adjoint_status))
+        return (*[grads.get(nm) for nm in names], None, None, None, None)
 
     @staticmethod
     def jvp(ctx, dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b, _dcons_var, _dlayout, _deq_layout, _dparams):
@@ -613,7 +713,9 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     cons_var int32 [B, m] (never differentiable), cons_a, cons_b [B, m]; a leading dimension of 1 is ONE instance for the whole batch (a
     learned layer's parameters): it is read with stride 0, never copied B times, and its gradient arrives summed over the batch, [1, ...],
     from one batch-reduced launch (mo_qp_gradients_shared).  The constraint triple is shared only if all three have a leading dimension
-    of 1; the residual-block form below still broadcasts by copying.
+    of 1.  The residual-block form below follows the same rule: J_blocks, r, lam, J_eq_blocks, r_eq and the constraint triple given once are
+    read with stride 0 (J_blocks and lam given once: ONE G for the batch), and their gradients arrive summed, [1, ...], from one
+    batch-reduced launch (mo_qp_gradients_blocks_shared).
     OR the residual-block form (the reference's own cost model): layout = a qp.ResidualLayout, J_blocks [B, layout.values] the packed local
     Jacobians, r [B, layout.rows], lam as above; equalities, if any, as eq_layout, J_eq_blocks [B, eq_layout.values], r_eq [B, k] (A_eq = the
     stacked UpdateJacobian, b_eq = r_eq) instead of A_eq / b_eq.  Its gradients arrive in the packed layouts and are computed from the
@@ -673,9 +775,11 @@ def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, con
         tensors.append(lam)
     B = max(int(t.shape[0]) for t in tensors)
     full = lambda t: _full(t, B)
-    lam_t = full(lam) if isinstance(lam, torch.Tensor) else torch.full((B,), float(lam), dtype=layout.dtype, device=layout.device)
-    v, status = QPSolveBlocksFunction.apply(full(J_blocks), full(r), lam_t, full(J_eq_blocks), full(r_eq), full(cons_a), full(cons_b),
-                                            full(cons_var), layout, eq_layout, params)
+    one = lambda t: None if t is None else (t.contiguous() if int(t.shape[0]) == 1 else _full(t, B))   # given once: passed through
+    lam_t = one(lam) if isinstance(lam, torch.Tensor) else torch.full((1,), float(lam), dtype=layout.dtype, device=layout.device)
+    cons = one if cons_var is not None and all(int(t.shape[0]) == 1 for t in (cons_var, cons_a, cons_b)) else full
+    v, status = QPSolveBlocksFunction.apply(one(J_blocks), one(r), lam_t, one(J_eq_blocks), one(r_eq), cons(cons_a), cons(cons_b),
+                                            cons(cons_var), layout, eq_layout, params)
     k = 0 if eq_layout is None else eq_layout.rows
     m = 0 if cons_a is None else int(cons_a.shape[1])
     return _result(v, status, layout.n, m, k, return_all, return_status)

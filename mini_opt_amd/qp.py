@@ -456,19 +456,28 @@ def _check_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tenso
     return B, (0 if J_blocks.shape[0] == 1 else layout.values), (0 if r.shape[0] == 1 else layout.rows)
 
 
-def linearize_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, lam: float = 0.0, lam_vec: Optional[torch.Tensor] = None):
+def linearize_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, lam: float = 0.0, lam_vec: Optional[torch.Tensor] = None,
+                     want_G: bool = True, batch: Optional[int] = None):
     """Cost part of LinearizeAndFillQP (nonlinear.cc:182-189) from packed residual blocks: sum_b UpdateHessian (residual.hpp:186-226) +
-    lambda I.  Returns (G [B,n,n] col-major lower, strict upper 0; c [B,n]; sum_b 0.5 |r_b|^2 [B])."""
+    lambda I.  Returns (G [B,n,n] col-major lower, strict upper 0; c [B,n]; sum_b 0.5 |r_b|^2 [B]).  J_blocks / r / lam_vec with a leading
+    dimension of 1 are read with stride 0; B is the largest leading dimension (or `batch`, if that is larger).  want_G=False: G is not
+    formed (returned as None); c has the bits of the full call."""
     B, js, rs = _check_blocks(layout, J_blocks, r)
     n = layout.n
-    G = torch.empty(B, n, n, dtype=layout.dtype, device=layout.device)
-    c = torch.empty(B, n, dtype=layout.dtype, device=layout.device)
-    f = torch.empty(B, dtype=layout.dtype, device=layout.device)
     ls = 0
     if lam_vec is not None:
         if lam_vec.dtype != layout.dtype or not lam_vec.is_contiguous() or lam_vec.dim() != 1:
             raise ValueError("lam_vec must be a contiguous [B] tensor of the layout's dtype")
         ls = 0 if lam_vec.shape[0] == 1 else 1
+        B = max(B, int(lam_vec.shape[0]))
+    if batch is not None:
+        B = max(B, int(batch))
+    for t in (J_blocks, r, lam_vec):
+        if t is not None and int(t.shape[0]) not in (1, B):
+            raise ValueError(f"leading dimension {int(t.shape[0])}: expected {B} or 1")
+    G = torch.empty(B, n, n, dtype=layout.dtype, device=layout.device) if want_G else None
+    c = torch.empty(B, n, dtype=layout.dtype, device=layout.device)
+    f = torch.empty(B, dtype=layout.dtype, device=layout.device)
     L.check(L.lib().mo_linearize_blocks(layout._plan, layout.h, _ptr(J_blocks), js, _ptr(r), rs, float(lam), _ptr(lam_vec), ls, B,
                                         _ptr(G), n * n, n, _ptr(c), n, _ptr(f), _stream()))
     return G, c, f

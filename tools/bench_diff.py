@@ -311,6 +311,78 @@ def run_shared(shape, dtype, batch, reps, warmup, rounds):
     return res
 
 
+BLOCK_SHARED_SHAPES = {"blocks_shared_n64": (64, 96, 2, 4, 32), "blocks_shared_n128": (128, 200, 3, 6, 64)}   # n, blocks, R, P, m box rows
+
+
+def run_blocks_shared(shape, dtype, batch, reps, warmup, rounds):
+    """J_blocks given once, r per problem: the reduced launch against mo_qp_gradients_blocks + sum(0), and solve_qp(layout=...) forward and
+    backward against the call with J_blocks expanded by the caller.  Both routes in one process, alternating, best of `rounds`."""
+    import numpy as np
+    n, count, R, Pn, m = BLOCK_SHARED_SHAPES[shape]
+    dev = torch.device("cuda:0")
+    elem = 8 if dtype == torch.float64 else 4
+    rng = np.random.default_rng(50)
+    blocks = [(tuple(int(i) for i in rng.permutation(n)[:Pn]), R) for _ in range(count)]
+    lay = Q.ResidualLayout(n, blocks, dtype=dtype)
+    values, rows = lay.values, lay.rows
+    gen = torch.Generator(device=dev).manual_seed(50)
+    rnd = lambda *shape_: torch.rand(*shape_, dtype=dtype, device=dev, generator=gen) * 2 - 1   # noqa: E731
+    J1, r = rnd(1, values), rnd(batch, rows)
+    half = m // 2
+    var = torch.arange(half, dtype=torch.int32, device=dev).repeat(2)[None].contiguous()
+    a = torch.cat([torch.ones(half, dtype=dtype, device=dev), -torch.ones(half, dtype=dtype, device=dev)])[None].contiguous()
+    b = torch.full((1, m), 0.5, dtype=dtype, device=dev)
+    cons = dict(cons_var=var, cons_a=a, cons_b=b)
+    prm = Q.Params(max_iterations=10)
+    V = n + 2 * m
+    v = torch.randn(batch, V, dtype=dtype, device=dev, generator=gen)
+    u = torch.randn(batch, V, dtype=dtype, device=dev, generator=gen)
+    members = ("J_blocks", "lam")
+    graphs = {}
+
+    def forward(key, expanded):
+        leaf = (J1.expand(batch, values).contiguous() if expanded else J1.clone()).requires_grad_(True)
+
+        def fn():
+            graphs[key] = (leaf, D.solve_qp(layout=lay, J_blocks=leaf, r=r, lam=0.1, params=prm, **cons))
+        return fn
+
+    def backward(key):
+        def fn():
+            leaf, x = graphs[key]
+            leaf.grad = None
+            x.backward(torch.ones_like(x), retain_graph=True)
+        return fn
+
+    calls = {
+        "gradients_blocks_shared": lambda: D.qp_gradients_blocks_shared(lay, J1, r, v, u, m=m, want=members),
+        "gradients_blocks_then_sum": lambda: {key: t.sum(0, keepdim=True) for key, t in D.qp_gradients_blocks(lay, J1, r, v, u, m=m, want=members).items()},
+        "solve_qp_forward_shared": forward("shared", False),
+        "solve_qp_forward_expanded": forward("expanded", True),
+        "solve_qp_backward_shared": backward("shared"),
+        "solve_qp_backward_expanded": backward("expanded"),
+    }
+    for fn in calls.values():
+        for _ in range(warmup):
+            fn()
+    best = {key: float("inf") for key in calls}
+    for _ in range(rounds):  # alternating rounds, best of
+        for key, fn in calls.items():
+            best[key] = min(best[key], wall(fn, reps if key.startswith("gradients") else 1))
+    res = {"shape": shape, "n": n, "blocks": count, "R": R, "P": Pn, "values": values, "rows": rows, "m": m, "dtype": str(dtype).split(".")[-1],
+           "batch": batch, "chunks": S_chunks(batch, torch.cuda.get_device_properties(dev).multi_processor_count),
+           "forward_bit_equal": bool(torch.equal(graphs["shared"][1], graphs["expanded"][1]))}
+    res.update({key + "_s": t for key, t in best.items()})
+    res["shared_speedup_gradients"] = best["gradients_blocks_then_sum"] / best["gradients_blocks_shared"]
+    res["shared_speedup_forward"] = best["solve_qp_forward_expanded"] / best["solve_qp_forward_shared"]
+    res["shared_speedup_backward"] = best["solve_qp_backward_expanded"] / best["solve_qp_backward_shared"]
+    res["gradients_blocks_shared_bytes"] = elem * (batch * (2 * n + rows) + 2 * values)           # x, u_x and r of every problem in, one packed gradient out
+    res["gradients_blocks_then_sum_bytes"] = elem * (batch * (2 * n + rows + 2 * values) + 2 * values)   # ... + the packed gradient per problem out and in again
+    for key in ("gradients_blocks_shared", "gradients_blocks_then_sum"):
+        res[key + "_TBps"] = res[key + "_bytes"] / best[key] / 1e12
+    return res
+
+
 def S_chunks(batch, cus):
     c = max(1, min(cus, (batch + 31) // 32))
     length = max(1, -(-batch // c))
@@ -330,7 +402,7 @@ def main():
     L.build()
     lines = []
     for sh in a.shapes.split(","):
-        res = (run_blocks if sh in BLOCK_SHAPES else run_shared if sh in SHARED_SHAPES else run)(sh, torch.float64 if a.dtype == "f64" else torch.float32, a.batch, a.reps, a.warmup, a.rounds)
+        res = (run_blocks if sh in BLOCK_SHAPES else run_shared if sh in SHARED_SHAPES else run_blocks_shared if sh in BLOCK_SHARED_SHAPES else run)(sh, torch.float64 if a.dtype == "f64" else torch.float32, a.batch, a.reps, a.warmup, a.rounds)
         print(json.dumps(res), flush=True)
         lines.append(res)
         torch.cuda.empty_cache()

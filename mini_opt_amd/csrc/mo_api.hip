@@ -215,6 +215,52 @@ template <typename Members> int check_dG_dA_ld(const mo_plan_desc& d, const Memb
   return MO_OK;
 }
 
+// The one judge of the dense gradient members (mo_qp_gradients, mo_qp_gradients_shared and its workspace query): what the arguments alone
+// tell, then the plan (sens_args) and the members against it.  summed: ONE instance per member, summed over the batch -- J and the constraint
+// set must then have stride 0.  `a` (a GradArgs or the SharedGradArgs derived from it) arrives zeroed; the LDS rules stay with the callers.
+int grad_args(const mo_plan* plan, const mo_problem* prob, int64_t batch, const void* vars, int64_t vars_stride, const mo_qp_grads* out,
+              bool summed, mo::GradArgs* a) {
+  if (!prob) return fail(MO_ERR_INVALID_ARGUMENT, "Must pass a non-null problem");
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  const bool j_level = prob->J != nullptr;
+  if (j_level && out->dG) return fail(MO_ERR_INVALID_ARGUMENT, "dG asked for with J-level input: ask for dJ / dr / dlambda");
+  if (!j_level && (out->dJ || out->dr || out->dlambda))
+    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr / dlambda asked for with (G, c) input: ask for dG / dc");
+  if (summed && (out->dJ || out->dr) && prob->J_stride != 0)
+    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr summed over the batch need one J for the batch: J_stride is %lld, not 0", (long long)prob->J_stride);
+  a->out = *out;
+  if (int rc = sens_args(plan, prob, batch, vars, vars_stride, &a->out, a)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  if (summed && (a->out.dcons_a || a->out.dcons_b) && prob->cons_stride != 0)
+    return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a / dcons_b summed over the batch need one constraint set for the batch: cons_stride is %lld, not 0",
+                (long long)prob->cons_stride);
+  if (a->J && !prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "J given without r");   // (t, w = J x + r: both outputs that read J read r)
+  if (a->out.dJ) {
+    if (a->out.dJ_layout != MO_ROW_MAJOR && a->out.dJ_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad dJ_layout");
+    const int min_dld = a->out.dJ_layout == MO_ROW_MAJOR ? d.n : d.m_r;
+    if (a->out.dJ_ld < min_dld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a->out.dJ_ld, min_dld);
+  }
+  if (int rc = check_dG_dA_ld(d, a->out)) return rc;
+  if (a->out.dcons_a) {
+    if (!prob->cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a asked for but cons_var is NULL");
+    a->cons_var = prob->cons_var; a->cons_stride = summed ? 0 : prob->cons_stride;
+  }
+  return MO_OK;
+}
+
+// The tail of the two batch-reduced launches, once their members are judged: vars, u and the workspace (`query` names its `need` bytes)
+int reduced_call_tail(const mo_plan* plan, int64_t batch, const void* vars, int64_t vars_stride, const void* u, int64_t u_stride,
+                      const void* workspace, int64_t workspace_bytes, size_t need, const char* query) {
+  if (batch > 0 && (!vars || !u)) return fail(MO_ERR_INVALID_ARGUMENT, "vars / u is NULL");
+  const int V = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
+  if (batch > 1 && (vars_stride < V || u_stride < V)) return fail(MO_ERR_DIMENSION, "vars_stride %lld / u_stride %lld < V = %d", (long long)vars_stride, (long long)u_stride, V);
+  if (!workspace || workspace_bytes < (int64_t)need)
+    return fail(MO_ERR_INVALID_ARGUMENT, "workspace too small: %lld bytes given, %lld needed (%s)", (long long)(workspace ? workspace_bytes : 0), (long long)need, query);
+  if ((uintptr_t)workspace & 15) return fail(MO_ERR_INVALID_ARGUMENT, "workspace is not 16-byte aligned");
+  return MO_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -561,31 +607,12 @@ int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const 
                     int64_t u_stride, const mo_qp_grads* out, void* stream) {
   g_err[0] = 0;
   // (what can be judged from the arguments alone comes first)
-  if (!prob) return fail(MO_ERR_INVALID_ARGUMENT, "Must pass a non-null problem");
-  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
-  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
-  const bool j_level = prob->J != nullptr;
-  if (j_level && out->dG) return fail(MO_ERR_INVALID_ARGUMENT, "dG asked for with J-level input: ask for dJ / dr / dlambda");
-  if (!j_level && (out->dJ || out->dr || out->dlambda))
-    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr / dlambda asked for with (G, c) input: ask for dG / dc");
   if (!vars || !u) return fail(MO_ERR_INVALID_ARGUMENT, "vars / u is NULL");
   mo::GradArgs a;
   memset(&a, 0, sizeof(a));
   a.u = u; a.u_stride = u_stride;
-  a.out = *out;
-  if (int rc = sens_args(plan, prob, batch, vars, vars_stride, &a.out, &a)) return rc;
+  if (int rc = grad_args(plan, prob, batch, vars, vars_stride, out, false, &a)) return rc;
   const mo_plan_desc& d = plan->desc;
-  if (a.J && !prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "J given without r");   // (t, w = J x + r: both outputs that read J read r)
-  if (a.out.dJ) {
-    if (a.out.dJ_layout != MO_ROW_MAJOR && a.out.dJ_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad dJ_layout");
-    const int min_dld = a.out.dJ_layout == MO_ROW_MAJOR ? d.n : d.m_r;
-    if (a.out.dJ_ld < min_dld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a.out.dJ_ld, min_dld);
-  }
-  if (int rc = check_dG_dA_ld(d, a.out)) return rc;
-  if (a.out.dcons_a) {
-    if (!prob->cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a asked for but cons_var is NULL");
-    a.cons_var = prob->cons_var; a.cons_stride = prob->cons_stride;
-  }
   if (mo::qp_grad_lds_bytes(a, plan->elem) > 64 * 1024)
     return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, m_r = %d: the vectors of one problem exceed the 64 KiB of LDS the gradient kernel uses", d.n, d.k, d.m, a.m_r);
   if (batch == 0) return MO_OK;
@@ -597,36 +624,12 @@ int mo_qp_gradients(mo_plan* plan, const mo_problem* prob, int64_t batch, const 
 }  // extern "C"
 
 namespace {
-// What mo_qp_gradients_shared and its workspace query judge alike: the members against the input level and against what the batch shares,
-// then the plan and the leading dimensions (sens_args, check_dG_dA_ld: those of mo_qp_gradients).  vars / u are not looked at here.
+// What mo_qp_gradients_shared and its workspace query judge alike: grad_args with the rules of a sum over the batch, then the LDS rule of
+// the moment kernel.  vars / u are not looked at here.
 int shared_grad_args(const mo_plan* plan, const mo_problem* prob, int64_t batch, const mo_qp_grads* out, mo::SharedGradArgs* a) {
-  if (!prob) return fail(MO_ERR_INVALID_ARGUMENT, "Must pass a non-null problem");
-  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
-  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
-  const bool j_level = prob->J != nullptr;
-  if (j_level && out->dG) return fail(MO_ERR_INVALID_ARGUMENT, "dG asked for with J-level input: ask for dJ / dr / dlambda");
-  if (!j_level && (out->dJ || out->dr || out->dlambda))
-    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr / dlambda asked for with (G, c) input: ask for dG / dc");
-  if ((out->dJ || out->dr) && prob->J_stride != 0)
-    return fail(MO_ERR_INVALID_ARGUMENT, "dJ / dr summed over the batch need one J for the batch: J_stride is %lld, not 0", (long long)prob->J_stride);
   memset(a, 0, sizeof(*a));
-  a->out = *out;
-  if (int rc = sens_args(plan, prob, batch, nullptr, 0, &a->out, a)) return rc;
+  if (int rc = grad_args(plan, prob, batch, nullptr, 0, out, true, a)) return rc;
   const mo_plan_desc& d = plan->desc;
-  if ((a->out.dcons_a || a->out.dcons_b) && prob->cons_stride != 0)
-    return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a / dcons_b summed over the batch need one constraint set for the batch: cons_stride is %lld, not 0",
-                (long long)prob->cons_stride);
-  if (a->J && !prob->r) return fail(MO_ERR_INVALID_ARGUMENT, "J given without r");
-  if (a->out.dJ) {
-    if (a->out.dJ_layout != MO_ROW_MAJOR && a->out.dJ_layout != MO_COL_MAJOR) return fail(MO_ERR_INVALID_ARGUMENT, "bad dJ_layout");
-    const int min_dld = a->out.dJ_layout == MO_ROW_MAJOR ? d.n : d.m_r;
-    if (a->out.dJ_ld < min_dld) return fail(MO_ERR_DIMENSION, "dJ_ld %d < %d", a->out.dJ_ld, min_dld);
-  }
-  if (int rc = check_dG_dA_ld(d, a->out)) return rc;
-  if (a->out.dcons_a) {
-    if (!prob->cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a asked for but cons_var is NULL");
-    a->cons_var = prob->cons_var; a->cons_stride = 0;
-  }
   if (mo::shared_grad_lds_bytes(*a, plan->elem) > 64 * 1024)
     return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, m_r = %d: four problems' vectors exceed the 64 KiB of LDS the moment kernel uses", d.n, d.k, d.m, a->m_r);
   return MO_OK;
@@ -650,13 +653,8 @@ int mo_qp_gradients_shared(mo_plan* plan, const mo_problem* prob, int64_t batch,
   g_err[0] = 0;
   mo::SharedGradArgs a;
   if (int rc = shared_grad_args(plan, prob, batch, out, &a)) return rc;
-  if (batch > 0 && (!vars || !u)) return fail(MO_ERR_INVALID_ARGUMENT, "vars / u is NULL");
-  const int V = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
-  if (batch > 1 && (vars_stride < V || u_stride < V)) return fail(MO_ERR_DIMENSION, "vars_stride %lld / u_stride %lld < V = %d", (long long)vars_stride, (long long)u_stride, V);
-  const int64_t need = (int64_t)mo::shared_grad_workspace_bytes(a, plan->elem, plan->num_cus);
-  if (!workspace || workspace_bytes < need)
-    return fail(MO_ERR_INVALID_ARGUMENT, "workspace too small: %lld bytes given, %lld needed (mo_qp_gradients_shared_workspace)", (long long)(workspace ? workspace_bytes : 0), (long long)need);
-  if ((uintptr_t)workspace & 15) return fail(MO_ERR_INVALID_ARGUMENT, "workspace is not 16-byte aligned");
+  if (int rc = reduced_call_tail(plan, batch, vars, vars_stride, u, u_stride, workspace, workspace_bytes,
+                                 mo::shared_grad_workspace_bytes(a, plan->elem, plan->num_cus), "mo_qp_gradients_shared_workspace")) return rc;
   a.vars = vars; a.vars_stride = vars_stride;
   a.u = u; a.u_stride = u_stride;
   a.status_fwd = status_fwd; a.status_adj = status_adj;
@@ -839,6 +837,23 @@ int check_layout(const mo_plan* plan, const mo_residual_layout* layout) {
   if (!layout) return fail(MO_ERR_INVALID_ARGUMENT, "layout is NULL");
   if (layout->n != plan->desc.n) return fail(MO_ERR_DIMENSION, "layout built for n = %d, plan n = %d", layout->n, plan->desc.n);
   if (layout->device != plan->desc.device) return fail(MO_ERR_INVALID_ARGUMENT, "layout lives on device %d, plan on %d", layout->device, plan->desc.device);
+  return MO_OK;
+}
+
+// The admission of a cost layout and an optional equality layout: what the arguments alone tell (eq_members: the call has equality members,
+// `verb` "asked for" / "given"), then the plan and both layouts against it.  *eq: the equality layout the call works with -- NULL without one
+// and with k = 0, where the equality members and the layout are ignored.
+int check_layout_pair(const mo_plan* plan, const mo_residual_layout* cost_layout, const mo_residual_layout* eq_layout, bool eq_members,
+                      const char* verb, const mo_residual_layout** eq) {
+  if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
+  if (eq_members && !eq_layout) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_eq_blocks / dr_eq %s but eq_layout is NULL", verb);
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, cost_layout)) return rc;
+  *eq = eq_layout && plan->desc.k > 0 ? eq_layout : nullptr;
+  if (*eq) {
+    if (int rc = check_layout(plan, *eq)) return rc;
+    if ((*eq)->rows != plan->desc.k) return fail(MO_ERR_DIMENSION, "eq_layout has %d rows, plan k = %d", (*eq)->rows, plan->desc.k);
+  }
   return MO_OK;
 }
 
@@ -1368,23 +1383,17 @@ namespace {
 // and the LDS rule.  J_blocks / r / vars / u / the workspace are not looked at here.
 int block_shared_args(const mo_plan* plan, const mo_residual_layout* cost_layout, const mo_residual_layout* eq_layout, int64_t r_stride,
                       int64_t batch, const mo_block_shared_grads* out, mo::BlockSharedArgs* a) {
-  if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
   if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
   if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
   if (out->dr && r_stride != 0)
     return fail(MO_ERR_INVALID_ARGUMENT, "dr summed over the batch needs one r for the batch: r_stride is %lld, not 0", (long long)r_stride);
-  if ((out->dJ_eq_blocks || out->dr_eq) && !eq_layout) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_eq_blocks / dr_eq asked for but eq_layout is NULL");
-  if (int rc = check_plan(plan)) return rc;
-  if (int rc = check_layout(plan, cost_layout)) return rc;
+  const mo_residual_layout* eq;
+  if (int rc = check_layout_pair(plan, cost_layout, eq_layout, out->dJ_eq_blocks || out->dr_eq, "asked for", &eq)) return rc;
   const mo_plan_desc& d = plan->desc;
   memset(a, 0, sizeof(*a));
   a->out = *out;
-  if (d.k == 0) { a->out.dJ_eq_blocks = nullptr; a->out.dr_eq = nullptr; }   // (with k = 0 the equality members and the layout are ignored)
-  if (eq_layout && d.k > 0) {
-    if (int rc = check_layout(plan, eq_layout)) return rc;
-    if (eq_layout->rows != d.k) return fail(MO_ERR_DIMENSION, "eq_layout has %d rows, plan k = %d", eq_layout->rows, d.k);
-    a->e_val = eq_layout->e_val; a->eq_values = eq_layout->values;
-  }
+  if (eq) { a->e_val = eq->e_val; a->eq_values = eq->values; }
+  if (d.k == 0) { a->out.dJ_eq_blocks = nullptr; a->out.dr_eq = nullptr; }
   a->n = d.n; a->k = d.k; a->m = d.m; a->rows = cost_layout->rows; a->values = cost_layout->values; a->batch = batch;
   a->d_row = cost_layout->d_row; a->d_idx = cost_layout->d_idx; a->d_val = cost_layout->d_val; a->d_dup = cost_layout->d_dup;
   a->r_stride = r_stride;
@@ -1414,15 +1423,10 @@ int mo_qp_gradients_blocks_shared(mo_plan* plan, const mo_residual_layout* cost_
   g_err[0] = 0;
   // (what can be judged from the arguments alone comes first)
   if (out && (out->dJ_blocks || out->dr) && (!J_blocks || !r)) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_blocks / dr asked for but J_blocks / r is NULL");
-  if (batch > 0 && (!vars || !u)) return fail(MO_ERR_INVALID_ARGUMENT, "vars / u is NULL");
   mo::BlockSharedArgs a;
   if (int rc = block_shared_args(plan, cost_layout, eq_layout, r_stride, batch, out, &a)) return rc;
-  const int V = plan->desc.n + 2 * plan->desc.m + plan->desc.k;
-  if (batch > 1 && (vars_stride < V || u_stride < V)) return fail(MO_ERR_DIMENSION, "vars_stride %lld / u_stride %lld < V = %d", (long long)vars_stride, (long long)u_stride, V);
-  const int64_t need = (int64_t)mo::blocks_shared_workspace_bytes(a, plan->elem, plan->num_cus);
-  if (!workspace || workspace_bytes < need)
-    return fail(MO_ERR_INVALID_ARGUMENT, "workspace too small: %lld bytes given, %lld needed (mo_qp_gradients_blocks_shared_workspace)", (long long)(workspace ? workspace_bytes : 0), (long long)need);
-  if ((uintptr_t)workspace & 15) return fail(MO_ERR_INVALID_ARGUMENT, "workspace is not 16-byte aligned");
+  if (int rc = reduced_call_tail(plan, batch, vars, vars_stride, u, u_stride, workspace, workspace_bytes,
+                                 mo::blocks_shared_workspace_bytes(a, plan->elem, plan->num_cus), "mo_qp_gradients_blocks_shared_workspace")) return rc;
   const mo_block_shared_grads& o = a.out;
   if (!o.dJ_blocks && !o.dr && !o.dlambda && !o.dJ_eq_blocks && !o.dr_eq) return MO_OK;
   a.J = J_blocks; a.r = r;
@@ -1440,20 +1444,14 @@ int mo_qp_tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layou
                              int64_t rho_stride, void* stream) {
   g_err[0] = 0;
   // (what can be judged from the arguments alone comes first)
-  if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
   if (!t) return fail(MO_ERR_INVALID_ARGUMENT, "t is NULL");
   if (!vars || !rho) return fail(MO_ERR_INVALID_ARGUMENT, "vars / rho is NULL");
   if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
   if ((t->dJ_blocks || t->dr) && (!J_blocks || !r)) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_blocks / dr given but J_blocks / r is NULL");
-  if ((t->dJ_eq_blocks || t->dr_eq) && !eq_layout) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_eq_blocks / dr_eq given but eq_layout is NULL");
   if (t->dcons_a && !cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a given but cons_var is NULL");
-  if (int rc = check_plan(plan)) return rc;
-  if (int rc = check_layout(plan, cost_layout)) return rc;
+  const mo_residual_layout* eq;
+  if (int rc = check_layout_pair(plan, cost_layout, eq_layout, t->dJ_eq_blocks || t->dr_eq, "given", &eq)) return rc;
   const mo_plan_desc& d = plan->desc;
-  if (eq_layout && d.k > 0) {  // (with k = 0 the equality members and the layout are ignored)
-    if (int rc = check_layout(plan, eq_layout)) return rc;
-    if (eq_layout->rows != d.k) return fail(MO_ERR_DIMENSION, "eq_layout has %d rows, plan k = %d", eq_layout->rows, d.k);
-  }
   if (!mo::blocks_tangent_fits(d.n, d.k, d.m, cost_layout->rows, plan->elem))
     return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, %d residual rows: the vectors of one problem (%zu B) exceed the 64 KiB of LDS the block tangent kernel uses",
                 d.n, d.k, d.m, cost_layout->rows, mo::blocks_tangent_lds_bytes(d.n, d.k, d.m, cost_layout->rows, plan->elem));
@@ -1465,8 +1463,8 @@ int mo_qp_tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layou
   a.c_ptr = cost_layout->c_ptr; a.c_ent = cost_layout->c_ent;
   a.vars = vars; a.vars_stride = vars_stride; a.rho = rho; a.rho_stride = rho_stride;
   a.t = *t;
-  if (d.k == 0 || !eq_layout) { a.t.dJ_eq_blocks = nullptr; a.t.dr_eq = nullptr; }
-  else { a.e_row = eq_layout->d_row; a.e_val = eq_layout->e_val; a.w_ptr = eq_layout->w_ptr; a.w_ent = eq_layout->w_ent; }
+  if (!eq) { a.t.dJ_eq_blocks = nullptr; a.t.dr_eq = nullptr; }
+  else { a.e_row = eq->d_row; a.e_val = eq->e_val; a.w_ptr = eq->w_ptr; a.w_ent = eq->w_ent; }
   if (d.m == 0) { a.t.dcons_a = nullptr; a.t.dcons_b = nullptr; }
   else if (cons_var) { a.cons_var = cons_var; a.cons_stride = cons_stride; }
   if (a.t.dJ_blocks || a.t.dr) {  // the only tangents that read the blocks; r only against dJ_blocks

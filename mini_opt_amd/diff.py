@@ -19,7 +19,8 @@ torch owns memory, streams and the autograd graph.  Plans are created once per (
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Iterable, Optional
+import math
+from typing import Dict, Iterable, NamedTuple, Optional
 
 import torch
 
@@ -27,7 +28,52 @@ from . import _lib as L
 from .qp import _DT, BatchedQP, Params, ResidualLayout, _ptr, _stream, jacobian_blocks, linearize_blocks
 
 _PLANS: Dict[tuple, C.c_void_p] = {}
-GRADIENTS = ("G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b")
+
+# The members of mo_qp_grads / mo_qp_tangents (dense) and of mo_block_grads / mo_block_shared_grads / mo_block_tangents (blocks):
+# name -> (pointer field, stride field, leading-dimension field or None, tail shape as a function of the problem).  The stride of a member is
+# the product of its tail, its leading dimension the last entry; cons_a and cons_b share one stride field.  A struct without a member's
+# stride field (mo_block_shared_grads: one instance per member) is filled with strided=False.  The order is that of the Functions' inputs.
+_DENSE = {
+    "G": ("dG", "dG_stride", "dG_ld", lambda p: (p.n, p.n)),
+    "c": ("dc", "dc_stride", None, lambda p: (p.n,)),
+    "J": ("dJ", "dJ_stride", "dJ_ld", lambda p: (int(p.J.shape[1]), int(p.J.shape[2]))),   # problem.J's rows and leading dimension
+    "r": ("dr", "dr_stride", None, lambda p: (p.m_r,)),
+    "lam": ("dlambda", "dlambda_stride", None, lambda p: ()),
+    "A_eq": ("dA_eq", "dA_stride", "dA_ld", lambda p: (p.n, p.k)),
+    "b_eq": ("db_eq", "db_stride", None, lambda p: (p.k,)),
+    "cons_a": ("dcons_a", "dcons_stride", None, lambda p: (p.m,)),
+    "cons_b": ("dcons_b", "dcons_stride", None, lambda p: (p.m,)),
+}
+_BLOCK = {   # the problem: a _Blocks
+    "J_blocks": ("dJ_blocks", "dJ_stride", None, lambda s: (s.layout.values,)),
+    "r": ("dr", "dr_stride", None, lambda s: (s.layout.rows,)),
+    "lam": ("dlambda", "dlambda_stride", None, lambda s: ()),
+    "J_eq_blocks": ("dJ_eq_blocks", "dJ_eq_stride", None, lambda s: (s.eq_layout.values,)),
+    "r_eq": ("dr_eq", "dr_eq_stride", None, lambda s: (s.k,)),
+    "cons_a": ("dcons_a", "dcons_stride", None, lambda s: (s.m,)),
+    "cons_b": ("dcons_b", "dcons_stride", None, lambda s: (s.m,)),
+}
+GRADIENTS = tuple(_DENSE)
+BLOCK_TANGENTS = tuple(_BLOCK)
+BLOCK_GRADIENTS = BLOCK_TANGENTS[:5]    # (the constraint members of a block problem go through the dense entry points)
+_DENSE_J, _DENSE_EQ = GRADIENTS[2:5], GRADIENTS[5:7]    # the J-level cost members (G alone belongs to the other level); the equality members
+_BLOCK_COST, _BLOCK_EQ, _CONS = BLOCK_TANGENTS[:3], BLOCK_TANGENTS[3:5], BLOCK_TANGENTS[5:]
+
+
+class _Blocks(NamedTuple):
+    """What the tails of _BLOCK are functions of; dtype and device are the cost layout's (the equality layout's without one)."""
+    layout: Optional[ResidualLayout]
+    eq_layout: Optional[ResidualLayout]
+    k: int
+    m: int
+
+    @property
+    def dtype(self):
+        return (self.eq_layout if self.layout is None else self.layout).dtype
+
+    @property
+    def device(self):
+        return (self.eq_layout if self.layout is None else self.layout).device
 
 
 def plan_for(problem: BatchedQP, batch: int) -> C.c_void_p:
@@ -92,8 +138,76 @@ def _check_names(names, kind: str, allowed, no_rows=(), other_level=()) -> None:
 
 
 def _check_dense_names(problem: BatchedQP, names, kind: str) -> None:
-    no_rows = (("A_eq", "b_eq") if problem.k == 0 else ()) + (("cons_a", "cons_b") if problem.m == 0 else ())
-    _check_names(names, kind, GRADIENTS, no_rows, ("G",) if problem.J is not None else ("J", "r", "lam"))
+    no_rows = (_DENSE_EQ if problem.k == 0 else ()) + (_CONS if problem.m == 0 else ())
+    _check_names(names, kind, GRADIENTS, no_rows, GRADIENTS[:1] if problem.J is not None else _DENSE_J)
+
+
+def _check_status(st: Optional[torch.Tensor], name: str, B: int, dev) -> None:
+    if st is not None and (st.dtype != torch.int32 or tuple(st.shape) != (B,) or not st.is_contiguous() or st.device != dev):
+        raise ValueError(f"{name}: expected a contiguous [{B}] int32 tensor on {dev}")
+
+
+def _outputs(struct, table, problem, want, lead: int, strided: bool = True, zeroed=()):
+    """The outputs named in `want` as new [lead, *tail] tensors (lead: B, or 1 for a gradient summed over the batch) and `struct` with their
+    pointers, leading dimensions and -- strided -- problem strides.  Names in `zeroed` are zero-filled.  Returns (tensors, struct)."""
+    out: Dict[str, torch.Tensor] = {}
+    for nm in want:
+        ptr, stride, ld, tail = table[nm]
+        tail = tail(problem)
+        out[nm] = (torch.zeros if nm in zeroed else torch.empty)(lead, *tail, dtype=problem.dtype, device=problem.device)
+        if struct is None:
+            continue
+        setattr(struct, ptr, _ptr(out[nm]))
+        if strided:
+            setattr(struct, stride, math.prod(tail))
+        if ld:
+            setattr(struct, ld, tail[-1])
+    return out, struct
+
+
+def _dense_outputs(problem: BatchedQP, want, lead: int, strided: bool):
+    """_outputs for mo_qp_grads.  dJ is in problem.J's layout with its leading dimension; the padding beyond the matrix is not written by
+    the kernels, so a padded dJ is defined here: zero."""
+    g = L.QPGrads()
+    col = problem.J_layout == "col"
+    if "J" in want:
+        g.dJ_layout = L.MO_COL_MAJOR if col else L.MO_ROW_MAJOR
+    padded = "J" in want and int(problem.J.shape[2]) > (problem.m_r if col else problem.n)
+    return _outputs(g, _DENSE, problem, want, lead, strided, zeroed=("J",) if padded else ())
+
+
+def _inputs(struct, table, problem, tangents: Dict[str, torch.Tensor], B: int, keep: list, tails=None) -> None:
+    """The tangents of a dict into `struct` through _take: pointers, leading dimensions, strides (0: one direction for the batch).  Two members
+    behind one stride field (cons_a, cons_b) must agree on it.  `tails`: the tails that are not the table's."""
+    strides: Dict[str, int] = {}
+    for nm, x in tangents.items():
+        ptr, stride, ld, tail = table[nm]
+        tail = (tails or {}).get(nm) or tail(problem)
+        p, s = _take(x, f"tangent {nm!r}", tail, B, problem.dtype, problem.device, keep)
+        if strides.setdefault(stride, s) != s:
+            raise ValueError("tangents 'cons_a' and 'cons_b' share one stride: give both per problem or both shared")
+        setattr(struct, ptr, p)
+        setattr(struct, stride, s)
+        if ld:
+            setattr(struct, ld, tail[-1])
+
+
+def _eq_rows(layout: ResidualLayout, eq_layout: Optional[ResidualLayout], k: int) -> int:
+    """The equality rows of a block problem: eq_layout's, which must fit `layout`; the caller's k without one."""
+    if eq_layout is None:
+        return int(k)
+    if eq_layout.n != layout.n or eq_layout.dtype != layout.dtype or eq_layout.device != layout.device:
+        raise ValueError("eq_layout must share n, dtype and device with layout")
+    return eq_layout.rows
+
+
+def _reduced_launch(dev, query, launch) -> None:
+    """A batch-reduced launch: query(bytes*) names its workspace (chunk partials), torch's allocator gives it, launch(workspace, bytes,
+    stream) runs on it."""
+    nbytes = C.c_int64()
+    L.check(query(C.byref(nbytes)))
+    work = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
+    L.check(launch(_ptr(work), int(work.numel()), _stream()))
 
 
 def kkt_solve(problem: BatchedQP, vars: torch.Tensor, rhs: torch.Tensor, transpose: bool = False, include_inequalities: bool = True):
@@ -124,48 +238,11 @@ def qp_gradients(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor, want: 
       "J" (the shape and layout of problem.J)    "r" [B, m_r]    "lam" [B]
     "G" is the gradient with respect to a symmetric G; "G" with J-level input and "J" / "r" / "lam" with (G, c) input raise."""
     B = _check_state_pair(vars, u, "u", problem.V, problem)
-    n, k, m = problem.n, problem.k, problem.m
-    j_level = problem.J is not None
     if want is None:
-        want = (("J", "r", "lam") if j_level else ("G", "c")) + (("A_eq", "b_eq") if k else ()) + (("cons_a", "cons_b") if m else ())
+        want = ((_DENSE_J if problem.J is not None else GRADIENTS[:2]) + (_DENSE_EQ if problem.k else ()) + (_CONS if problem.m else ()))
     want = tuple(want)
     _check_dense_names(problem, want, "gradient")
-    dt, dev = problem.dtype, problem.device
-    new = lambda *shape: torch.empty(*shape, dtype=dt, device=dev)
-    out: Dict[str, torch.Tensor] = {}
-    g = L.QPGrads()
-    if "G" in want:
-        out["G"] = new(B, n, n)
-        g.dG, g.dG_stride, g.dG_ld = _ptr(out["G"]), n * n, n
-    if "c" in want:
-        out["c"] = new(B, n)
-        g.dc, g.dc_stride = _ptr(out["c"]), n
-    if "A_eq" in want:
-        out["A_eq"] = new(B, n, k)
-        g.dA_eq, g.dA_stride, g.dA_ld = _ptr(out["A_eq"]), n * k, k
-    if "b_eq" in want:
-        out["b_eq"] = new(B, k)
-        g.db_eq, g.db_stride = _ptr(out["b_eq"]), k
-    if "cons_a" in want or "cons_b" in want:
-        g.dcons_stride = m
-        if "cons_a" in want:
-            out["cons_a"] = new(B, m)
-            g.dcons_a = _ptr(out["cons_a"])
-        if "cons_b" in want:
-            out["cons_b"] = new(B, m)
-            g.dcons_b = _ptr(out["cons_b"])
-    if "J" in want:
-        rows, ld = int(problem.J.shape[1]), int(problem.J.shape[2])
-        padded = ld > (problem.m_r if problem.J_layout == "col" else n)   # (the padding beyond the matrix is not written: define it)
-        out["J"] = torch.zeros(B, rows, ld, dtype=dt, device=dev) if padded else new(B, rows, ld)
-        g.dJ, g.dJ_stride, g.dJ_ld = _ptr(out["J"]), rows * ld, ld
-        g.dJ_layout = L.MO_COL_MAJOR if problem.J_layout == "col" else L.MO_ROW_MAJOR
-    if "r" in want:
-        out["r"] = new(B, problem.m_r)
-        g.dr, g.dr_stride = _ptr(out["r"]), problem.m_r
-    if "lam" in want:
-        out["lam"] = new(B)
-        g.dlambda, g.dlambda_stride = _ptr(out["lam"]), 1
+    out, g = _dense_outputs(problem, want, B, strided=True)
     prob = problem.as_struct()
     L.check(L.lib().mo_qp_gradients(plan_for(problem, B), C.byref(prob), B, _ptr(vars), problem.V, _ptr(u), problem.V, C.byref(g), _stream()))
     return out
@@ -179,52 +256,15 @@ def qp_gradients_shared(problem: BatchedQP, vars: torch.Tensor, u: torch.Tensor,
     then hold anything, NaN included).  "J" and "r" need problem.J with a leading dimension of 1, "cons_a" / "cons_b" a constraint set with
     one.  No [B, ...] matrix is formed: the workspace (chunk partials, from torch's allocator) is a few tiles per CU."""
     B = _check_state_pair(vars, u, "u", problem.V, problem)
-    n, k, m = problem.n, problem.k, problem.m
     want = tuple(want)
     _check_dense_names(problem, want, "gradient")
-    dt, dev = problem.dtype, problem.device
-    _check_status(status_fwd, "status_fwd", B, dev)
-    _check_status(status_adj, "status_adj", B, dev)
-    new = lambda *shape: torch.empty(1, *shape, dtype=dt, device=dev)
-    out: Dict[str, torch.Tensor] = {}
-    g = L.QPGrads()
-    if "G" in want:
-        out["G"] = new(n, n)
-        g.dG, g.dG_ld = _ptr(out["G"]), n
-    if "c" in want:
-        out["c"] = new(n)
-        g.dc = _ptr(out["c"])
-    if "A_eq" in want:
-        out["A_eq"] = new(n, k)
-        g.dA_eq, g.dA_ld = _ptr(out["A_eq"]), k
-    if "b_eq" in want:
-        out["b_eq"] = new(k)
-        g.db_eq = _ptr(out["b_eq"])
-    if "cons_a" in want:
-        out["cons_a"] = new(m)
-        g.dcons_a = _ptr(out["cons_a"])
-    if "cons_b" in want:
-        out["cons_b"] = new(m)
-        g.dcons_b = _ptr(out["cons_b"])
-    if "J" in want:
-        rows, ld = int(problem.J.shape[1]), int(problem.J.shape[2])
-        padded = ld > (problem.m_r if problem.J_layout == "col" else n)   # (the padding beyond the matrix is not written: define it)
-        out["J"] = torch.zeros(1, rows, ld, dtype=dt, device=dev) if padded else new(rows, ld)
-        g.dJ, g.dJ_ld = _ptr(out["J"]), ld
-        g.dJ_layout = L.MO_COL_MAJOR if problem.J_layout == "col" else L.MO_ROW_MAJOR
-    if "r" in want:
-        out["r"] = new(problem.m_r)
-        g.dr = _ptr(out["r"])
-    if "lam" in want:
-        out["lam"] = new()
-        g.dlambda = _ptr(out["lam"])
-    prob = problem.as_struct()
-    plan = plan_for(problem, B)
-    nbytes = C.c_int64()
-    L.check(L.lib().mo_qp_gradients_shared_workspace(plan, C.byref(prob), B, C.byref(g), C.byref(nbytes)))
-    work = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
-    L.check(L.lib().mo_qp_gradients_shared(plan, C.byref(prob), B, _ptr(vars), problem.V, _ptr(u), problem.V, _ptr(status_fwd), _ptr(status_adj),
-                                           C.byref(g), _ptr(work), int(work.numel()), _stream()))
+    _check_status(status_fwd, "status_fwd", B, problem.device)
+    _check_status(status_adj, "status_adj", B, problem.device)
+    out, g = _dense_outputs(problem, want, 1, strided=False)
+    prob, plan, lib = problem.as_struct(), plan_for(problem, B), L.lib()
+    _reduced_launch(problem.device, lambda nbytes: lib.mo_qp_gradients_shared_workspace(plan, C.byref(prob), B, C.byref(g), nbytes),
+                    lambda work, nbytes, stream: lib.mo_qp_gradients_shared(plan, C.byref(prob), B, _ptr(vars), problem.V, _ptr(u), problem.V,
+                                                                            _ptr(status_fwd), _ptr(status_adj), C.byref(g), work, nbytes, stream))
     return out
 
 
@@ -235,39 +275,16 @@ def qp_tangent_rhs(problem: BatchedQP, vars: torch.Tensor, tangents: Dict[str, t
     "b_eq" [B, k], "cons_a", "cons_b" [B, m], "J" in the layout of problem.J (its own leading dimension allowed), "r" [B, m_r], "lam" [B].
     A missing key is a zero tangent; a leading dimension of 1 is one direction shared by the batch."""
     B = _check_state(vars, "vars", problem.V, problem)
-    n, k, m = problem.n, problem.k, problem.m
+    _check_dense_names(problem, tangents, "tangent")
+    tails = {}
+    if "J" in tangents:   # (its own leading dimension allowed)
+        ld = int(tangents["J"].shape[-1]) if tangents["J"].dim() == 3 else 0
+        if ld < (problem.m_r if problem.J_layout == "col" else problem.n):
+            raise ValueError(f"tangent 'J': leading dimension {ld} below the layout's minimum")
+        tails["J"] = (int(problem.J.shape[1]), ld)
     t = L.QPTangents()
     keep = []
-    take = lambda name, tail: _take(tangents[name], f"tangent {name!r}", tail, B, problem.dtype, problem.device, keep)
-    _check_dense_names(problem, tangents, "tangent")
-    if "G" in tangents:
-        t.dG, t.dG_stride = take("G", (n, n))
-        t.dG_ld = n
-    if "c" in tangents:
-        t.dc, t.dc_stride = take("c", (n,))
-    if "A_eq" in tangents:
-        t.dA_eq, t.dA_stride = take("A_eq", (n, k))
-        t.dA_ld = k
-    if "b_eq" in tangents:
-        t.db_eq, t.db_stride = take("b_eq", (k,))
-    if "cons_a" in tangents:
-        t.dcons_a, t.dcons_stride = take("cons_a", (m,))
-    if "cons_b" in tangents:
-        t.dcons_b, stride_b = take("cons_b", (m,))
-        if "cons_a" in tangents and stride_b != t.dcons_stride:
-            raise ValueError("tangents 'cons_a' and 'cons_b' share one stride: give both per problem or both shared")
-        t.dcons_stride = stride_b
-    if "J" in tangents:
-        rows = int(problem.J.shape[1])
-        ld = int(tangents["J"].shape[-1]) if tangents["J"].dim() == 3 else 0
-        if ld < (problem.m_r if problem.J_layout == "col" else n):
-            raise ValueError(f"tangent 'J': leading dimension {ld} below the layout's minimum")
-        t.dJ, t.dJ_stride = take("J", (rows, ld))
-        t.dJ_ld = ld
-    if "r" in tangents:
-        t.dr, t.dr_stride = take("r", (problem.m_r,))
-    if "lam" in tangents:
-        t.dlambda, t.dlambda_stride = take("lam", ())
+    _inputs(t, _DENSE, problem, tangents, B, keep, tails)
     rho = torch.empty_like(vars)
     prob = problem.as_struct()
     L.check(L.lib().mo_qp_tangent_rhs(plan_for(problem, B), C.byref(prob), B, _ptr(vars), problem.V, C.byref(t), _ptr(rho), problem.V, _stream()))
@@ -289,6 +306,28 @@ def _masked(t: Optional[torch.Tensor], ok: torch.Tensor) -> Optional[torch.Tenso
     if t is None:
         return None
     return torch.where(ok.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros((), dtype=t.dtype, device=t.device))
+
+
+def _partition(want, shared, r_key: str, J_key: str):
+    """(each, summed): the names of `want` computed per problem and the ones a batch-reduced launch sums.  Summed by the kernels: what the
+    batch shares (`shared`) -- but r given once against a J / J_blocks per problem, which the reduced launches refuse (dr = -J s_u needs one
+    J): that one is formed per problem and summed by _per_problem."""
+    summed = [nm for nm in want if nm in shared and not (nm == r_key and J_key not in shared)]
+    return [nm for nm in want if nm not in summed], summed
+
+
+def _per_problem(grads: Dict[str, torch.Tensor], ok: torch.Tensor, shared) -> Dict[str, torch.Tensor]:
+    """What follows the per-problem launches of a backward: the zero-masking rule, then the sum over the batch for the names in `shared`."""
+    grads = {nm: _masked(t, ok) for nm, t in grads.items()}
+    for nm in grads:
+        if nm in shared:
+            grads[nm] = grads[nm].sum(0, keepdim=True)
+    return grads
+
+
+def _where_lam_added(lam: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """lam's gradient or tangent counts only where lam was added (lam > 0)."""
+    return torch.where(lam > 0, t, torch.zeros((), dtype=t.dtype, device=t.device))
 
 
 def _solve_forward(ctx, problem: BatchedQP, B: int, params: Params):
@@ -360,14 +399,8 @@ class QPSolveFunction(torch.autograd.Function):
     def backward(ctx, g, _g_status):
         problem, v, u, ok = _adjoint(ctx, g)
         want = [nm for nm, need in zip(GRADIENTS, ctx.needs_input_grad[:9]) if need]
-        # summed by the kernel: what the batch shares -- but "r" given once against a J per problem, which mo_qp_gradients_shared refuses
-        # (dr = -J s_u needs one J): that one is formed per problem and summed here
-        summed = [nm for nm in want if nm in ctx.shared and not (nm == "r" and "J" not in ctx.shared)]
-        each = [nm for nm in want if nm not in summed]
-        grads = {nm: _masked(t, ok) for nm, t in qp_gradients(problem, v, u, each).items()} if each else {}
-        for nm in each:
-            if nm in ctx.shared:
-                grads[nm] = grads[nm].sum(0, keepdim=True)
+        each, summed = _partition(want, ctx.shared, "r", "J")
+        grads = _per_problem(qp_gradients(problem, v, u, each), ok, ctx.shared) if each else {}
         if summed:
             grads.update(qp_gradients_shared(problem, v, u, summed, status_fwd=ctx.status, status_adj=ctx.adjoint_status))
         return (*[grads.get(nm) for nm in GRADIENTS], None, None)
@@ -395,6 +428,19 @@ def tangent_status(t: torch.Tensor) -> Optional[torch.Tensor]:
     return None
 
 
+def _reads_blocks(names) -> bool:
+    """Whether a launch reads the cost blocks: only the J_blocks and r members do."""
+    return any(nm in names for nm in _BLOCK_COST[:2])
+
+
+def _take_cost_blocks(s: _Blocks, J_blocks, r, B: int, keep: list, J_lead: Optional[int] = None):
+    """(J pointer, J stride, r pointer, r stride) of the packed cost blocks a launch reads, J_blocks [J_lead or B or 1, values] and
+    r [B or 1, rows], through _take."""
+    J_name, r_name = _BLOCK_COST[:2]
+    return (*_take(J_blocks, J_name, _BLOCK[J_name][3](s), J_lead or B, s.dtype, s.device, keep),
+            *_take(r, r_name, _BLOCK[r_name][3](s), B, s.dtype, s.device, keep))
+
+
 def qp_gradients_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, vars: torch.Tensor, u: torch.Tensor, k: int = 0,
                         m: int = 0, want: Iterable[str] = ("J_blocks", "r", "lam")) -> Dict[str, torch.Tensor]:
     """mo_qp_gradients_blocks: gradients of a loss with respect to the packed cost blocks of `layout` (the inputs of linearize_blocks) from the
@@ -402,24 +448,14 @@ def qp_gradients_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch
     inequality rows (V = n + 2 m + k).  J_blocks [B or 1, values], r [B or 1, rows] (1: shared by the batch; the outputs are per problem).
     Returns the ones named in `want`: "J_blocks" [B, values] (the packing of J_blocks), "r" [B, rows], "lam" [B]."""
     want = tuple(want)
-    _check_names(want, "gradient", ("J_blocks", "r", "lam"))
-    B = _check_state_pair(vars, u, "u", layout.n + 2 * int(m) + int(k), layout)
+    _check_names(want, "gradient", _BLOCK_COST)
+    k, m = int(k), int(m)
+    B = _check_state_pair(vars, u, "u", layout.n + 2 * m + k, layout)
+    blocks = _Blocks(layout, None, k, m)
     keep = []
-    J_ptr, J_stride = _take(J_blocks, "J_blocks", (layout.values,), B, layout.dtype, layout.device, keep)
-    r_ptr, r_stride = _take(r, "r", (layout.rows,), B, layout.dtype, layout.device, keep)
-    new = lambda *shape: torch.empty(*shape, dtype=layout.dtype, device=layout.device)
-    out: Dict[str, torch.Tensor] = {}
-    g = L.BlockGrads()
-    if "J_blocks" in want:
-        out["J_blocks"] = new(B, layout.values)
-        g.dJ_blocks, g.dJ_stride = _ptr(out["J_blocks"]), layout.values
-    if "r" in want:
-        out["r"] = new(B, layout.rows)
-        g.dr, g.dr_stride = _ptr(out["r"]), layout.rows
-    if "lam" in want:
-        out["lam"] = new(B)
-        g.dlambda, g.dlambda_stride = _ptr(out["lam"]), 1
-    plan = _plan_of(layout.n, int(k), int(m), 0, layout.dtype, layout.device, B)
+    J_ptr, J_stride, r_ptr, r_stride = _take_cost_blocks(blocks, J_blocks, r, B, keep)
+    out, g = _outputs(L.BlockGrads(), _BLOCK, blocks, want, B)
+    plan = _plan_of(layout.n, k, m, 0, layout.dtype, layout.device, B)
     L.check(L.lib().mo_qp_gradients_blocks(plan, layout.h, J_ptr, J_stride, r_ptr, r_stride, B, _ptr(vars), int(vars.shape[1]), _ptr(u),
                                            int(u.shape[1]), C.byref(g), _stream()))
     return out
@@ -430,26 +466,15 @@ def qp_gradients_eq_blocks(eq_layout: ResidualLayout, vars: torch.Tensor, u: tor
     """mo_qp_gradients_eq_blocks: gradients with respect to the packed equality blocks of `eq_layout` (the inputs of jacobian_blocks; k = its
     rows) from `vars`, `u` [B, n + 2 m + k]: "J_eq_blocks" [B, values] (exactly 0 for a column that loses its global column), "r_eq" [B, k]."""
     want = tuple(want)
-    _check_names(want, "gradient", ("J_eq_blocks", "r_eq"))
+    _check_names(want, "gradient", _BLOCK_EQ)
     k = eq_layout.rows
     B = _check_state_pair(vars, u, "u", eq_layout.n + 2 * int(m) + k, eq_layout)
-    out: Dict[str, torch.Tensor] = {}
-    if "J_eq_blocks" in want:
-        out["J_eq_blocks"] = torch.empty(B, eq_layout.values, dtype=eq_layout.dtype, device=eq_layout.device)
-    if "r_eq" in want:
-        out["r_eq"] = torch.empty(B, k, dtype=eq_layout.dtype, device=eq_layout.device)
+    out, _ = _outputs(None, _BLOCK, _Blocks(None, eq_layout, k, int(m)), want, B)   # (no struct: the entry point takes the two pointers)
+    dJ_eq, dr_eq = (_ptr(out.get(nm)) for nm in _BLOCK_EQ)
     plan = _plan_of(eq_layout.n, k, int(m), 0, eq_layout.dtype, eq_layout.device, B)
     L.check(L.lib().mo_qp_gradients_eq_blocks(plan, eq_layout.h, B, _ptr(vars), int(vars.shape[1]), _ptr(u), int(u.shape[1]),
-                                              _ptr(out.get("J_eq_blocks")), eq_layout.values, _ptr(out.get("r_eq")), k, _stream()))
+                                              dJ_eq, eq_layout.values, dr_eq, k, _stream()))
     return out
-
-
-def _check_status(st: Optional[torch.Tensor], name: str, B: int, dev) -> None:
-    if st is not None and (st.dtype != torch.int32 or tuple(st.shape) != (B,) or not st.is_contiguous() or st.device != dev):
-        raise ValueError(f"{name}: expected a contiguous [{B}] int32 tensor on {dev}")
-
-
-BLOCK_GRADIENTS = ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq")
 
 
 def qp_gradients_blocks_shared(layout: ResidualLayout, J_blocks: Optional[torch.Tensor], r: Optional[torch.Tensor], vars: torch.Tensor,
@@ -463,54 +488,28 @@ def qp_gradients_blocks_shared(layout: ResidualLayout, J_blocks: Optional[torch.
     int32 status words; a problem counts iff every given word is MO_STATUS_OK (its rows of `vars` / `u` / `r` may then hold anything).
     No [B, values] gradient is formed: the workspace (chunk partials, from torch's allocator) is a few tiles and packed values per CU."""
     want = tuple(want)
-    if eq_layout is not None:
-        if eq_layout.n != layout.n or eq_layout.dtype != layout.dtype or eq_layout.device != layout.device:
-            raise ValueError("eq_layout must share n, dtype and device with layout")
-        k = eq_layout.rows
-    k, m = int(k), int(m)
-    _check_names(want, "gradient", BLOCK_GRADIENTS, ("J_eq_blocks", "r_eq") if eq_layout is None or k == 0 else ())
+    k, m = _eq_rows(layout, eq_layout, k), int(m)
+    _check_names(want, "gradient", BLOCK_GRADIENTS, _BLOCK_EQ if eq_layout is None or k == 0 else ())
     V = layout.n + 2 * m + k
     B = _check_state_pair(vars, u, "u", V, layout)
-    dt, dev = layout.dtype, layout.device
-    _check_status(status_fwd, "status_fwd", B, dev)
-    _check_status(status_adj, "status_adj", B, dev)
+    _check_status(status_fwd, "status_fwd", B, layout.device)
+    _check_status(status_adj, "status_adj", B, layout.device)
+    blocks = _Blocks(layout, eq_layout, k, m)
     keep = []
     J_ptr = r_ptr = None
     r_stride = 0
-    if "J_blocks" in want or "r" in want:
-        J_ptr, _ = _take(J_blocks, "J_blocks", (layout.values,), 1, dt, dev, keep)          # ONE instance
-        r_ptr, r_stride = _take(r, "r", (layout.rows,), B, dt, dev, keep)
+    if _reads_blocks(want):
+        J_ptr, _, r_ptr, r_stride = _take_cost_blocks(blocks, J_blocks, r, B, keep, J_lead=1)          # ONE instance of J_blocks
         if "r" in want and int(r.shape[0]) != 1:
             raise ValueError("gradient 'r' summed over the batch needs r [1, rows]")
-    new = lambda *shape: torch.empty(1, *shape, dtype=dt, device=dev)
-    out: Dict[str, torch.Tensor] = {}
-    g = L.BlockSharedGrads()
-    if "J_blocks" in want:
-        out["J_blocks"] = new(layout.values)
-        g.dJ_blocks = _ptr(out["J_blocks"])
-    if "r" in want:
-        out["r"] = new(layout.rows)
-        g.dr = _ptr(out["r"])
-    if "lam" in want:
-        out["lam"] = new()
-        g.dlambda = _ptr(out["lam"])
-    if "J_eq_blocks" in want:
-        out["J_eq_blocks"] = new(eq_layout.values)
-        g.dJ_eq_blocks = _ptr(out["J_eq_blocks"])
-    if "r_eq" in want:
-        out["r_eq"] = new(k)
-        g.dr_eq = _ptr(out["r_eq"])
-    plan = _plan_of(layout.n, k, m, 0, dt, dev, B)
+    out, g = _outputs(L.BlockSharedGrads(), _BLOCK, blocks, want, 1, strided=False)
+    plan, lib = _plan_of(layout.n, k, m, 0, layout.dtype, layout.device, B), L.lib()
     eq_h = None if eq_layout is None else eq_layout.h
-    nbytes = C.c_int64()
-    L.check(L.lib().mo_qp_gradients_blocks_shared_workspace(plan, layout.h, eq_h, r_stride, B, C.byref(g), C.byref(nbytes)))
-    work = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=dev)
-    L.check(L.lib().mo_qp_gradients_blocks_shared(plan, layout.h, J_ptr, r_ptr, r_stride, eq_h, B, _ptr(vars), V, _ptr(u), V, _ptr(status_fwd),
-                                                  _ptr(status_adj), C.byref(g), _ptr(work), int(work.numel()), _stream()))
+    _reduced_launch(layout.device, lambda nbytes: lib.mo_qp_gradients_blocks_shared_workspace(plan, layout.h, eq_h, r_stride, B, C.byref(g), nbytes),
+                    lambda work, nbytes, stream: lib.mo_qp_gradients_blocks_shared(plan, layout.h, J_ptr, r_ptr, r_stride, eq_h, B, _ptr(vars), V,
+                                                                                   _ptr(u), V, _ptr(status_fwd), _ptr(status_adj), C.byref(g),
+                                                                                   work, nbytes, stream))
     return out
-
-
-BLOCK_TANGENTS = ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq", "cons_a", "cons_b")
 
 
 def qp_tangent_rhs_blocks(layout: ResidualLayout, J_blocks: Optional[torch.Tensor], r: Optional[torch.Tensor], vars: torch.Tensor,
@@ -522,48 +521,26 @@ def qp_tangent_rhs_blocks(layout: ResidualLayout, J_blocks: Optional[torch.Tenso
     is a zero tangent, a leading dimension of 1 is one direction shared by the batch.  J_blocks [B or 1, values] and r [B or 1, rows] are
     needed (and read) only with the "J_blocks" / "r" tangents.  k, m: the problem's equality and inequality rows (k = eq_layout.rows when an
     eq_layout is given); cons_var int32 [B or 1, m] with "cons_a"."""
-    if eq_layout is not None:
-        if eq_layout.n != layout.n or eq_layout.dtype != layout.dtype or eq_layout.device != layout.device:
-            raise ValueError("eq_layout must share n, dtype and device with layout")
-        k = eq_layout.rows
-    n, k, m = layout.n, int(k), int(m)
+    n, k, m = layout.n, _eq_rows(layout, eq_layout, k), int(m)
     V = n + 2 * m + k
-    dt, dev = layout.dtype, layout.device
     B = _check_state(vars, "vars", V, layout)
-    no_rows = (("J_eq_blocks", "r_eq") if k == 0 or eq_layout is None else ()) + (("cons_a", "cons_b") if m == 0 else ())
+    no_rows = (_BLOCK_EQ if k == 0 or eq_layout is None else ()) + (_CONS if m == 0 else ())
     _check_names(tangents, "tangent", BLOCK_TANGENTS, no_rows)
+    blocks = _Blocks(layout, eq_layout, k, m)
     keep = []
-    take = lambda x, name, tail, dtype=dt: _take(x, name, tail, B, dtype, dev, keep)
-    t = L.BlockTangents()
     J_ptr = r_ptr = None
     J_stride = r_stride = 0
-    if "J_blocks" in tangents or "r" in tangents:
-        J_ptr, J_stride = take(J_blocks, "J_blocks", (layout.values,))
-        r_ptr, r_stride = take(r, "r", (layout.rows,))
-    if "J_blocks" in tangents:
-        t.dJ_blocks, t.dJ_stride = take(tangents["J_blocks"], "tangent 'J_blocks'", (layout.values,))
-    if "r" in tangents:
-        t.dr, t.dr_stride = take(tangents["r"], "tangent 'r'", (layout.rows,))
-    if "lam" in tangents:
-        t.dlambda, t.dlambda_stride = take(tangents["lam"], "tangent 'lam'", ())
-    if "J_eq_blocks" in tangents:
-        t.dJ_eq_blocks, t.dJ_eq_stride = take(tangents["J_eq_blocks"], "tangent 'J_eq_blocks'", (eq_layout.values,))
-    if "r_eq" in tangents:
-        t.dr_eq, t.dr_eq_stride = take(tangents["r_eq"], "tangent 'r_eq'", (k,))
-    if "cons_a" in tangents:
-        t.dcons_a, t.dcons_stride = take(tangents["cons_a"], "tangent 'cons_a'", (m,))
-    if "cons_b" in tangents:
-        t.dcons_b, stride_b = take(tangents["cons_b"], "tangent 'cons_b'", (m,))
-        if "cons_a" in tangents and stride_b != t.dcons_stride:
-            raise ValueError("tangents 'cons_a' and 'cons_b' share one stride: give both per problem or both shared")
-        t.dcons_stride = stride_b
+    if _reads_blocks(tangents):
+        J_ptr, J_stride, r_ptr, r_stride = _take_cost_blocks(blocks, J_blocks, r, B, keep)
+    t = L.BlockTangents()
+    _inputs(t, _BLOCK, blocks, tangents, B, keep)
     cv_ptr, cv_stride = None, 0
     if m and cons_var is not None:
-        cv_ptr, cv_stride = take(cons_var, "cons_var", (m,), torch.int32)
+        cv_ptr, cv_stride = _take(cons_var, "cons_var", (m,), B, torch.int32, layout.device, keep)
     elif "cons_a" in tangents:
         raise ValueError("tangent 'cons_a' needs cons_var")
     rho = torch.empty_like(vars)
-    plan = _plan_of(n, k, m, 0, dt, dev, B)
+    plan = _plan_of(n, k, m, 0, layout.dtype, layout.device, B)
     L.check(L.lib().mo_qp_tangent_rhs_blocks(plan, layout.h, J_ptr, J_stride, r_ptr, r_stride, None if eq_layout is None else eq_layout.h,
                                              cv_ptr, cv_stride, B, _ptr(vars), V, C.byref(t), _ptr(rho), V, _stream()))
     return rho
@@ -592,7 +569,7 @@ class QPSolveBlocksFunction(torch.autograd.Function):
     formed.  lam's gradient counts only where lam was added (lam > 0).  Zero gradients for problems whose forward or adjoint status is not
     OK, as QPSolveFunction."""
 
-    NAMES = ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq", "cons_a", "cons_b")
+    NAMES = BLOCK_TANGENTS
 
     @staticmethod
     def forward(ctx, J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, cons_var, layout, eq_layout, params):
@@ -622,34 +599,25 @@ class QPSolveBlocksFunction(torch.autograd.Function):
         problem, v, u, ok = _adjoint(ctx, g)
         names = QPSolveBlocksFunction.NAMES
         want = [nm for nm, nd in zip(names, ctx.needs_input_grad[:7]) if nd]
-        # summed by the kernels: what the batch shares -- but "r" given once against J_blocks per problem, which the reduced launch refuses
-        # (dr = -sum s_u J_b needs one J_blocks): that one is formed per problem and summed here
-        summed = [nm for nm in want if nm in ctx.shared and not (nm == "r" and "J_blocks" not in ctx.shared)]
-        each = [nm for nm in want if nm not in summed]
+        each, summed = _partition(want, ctx.shared, "r", "J_blocks")
         grads: Dict[str, torch.Tensor] = {}
         sel = lambda group, among: [nm for nm in group if nm in among]
-        cost, eq, cons = sel(each, ("J_blocks", "r", "lam")), sel(each, ("J_eq_blocks", "r_eq")), sel(each, ("cons_a", "cons_b"))
+        cost, eq, cons = sel(each, _BLOCK_COST), sel(each, _BLOCK_EQ), sel(each, _CONS)
         if cost:
             grads.update(qp_gradients_blocks(ctx.layout, ctx.J_blocks, ctx.r, v, u, k=problem.k, m=problem.m, want=cost))
         if eq:
             grads.update(qp_gradients_eq_blocks(ctx.eq_layout, v, u, m=problem.m, want=eq))
         if cons:
             grads.update(qp_gradients(problem, v, u, cons))
-        if "lam" in grads:
-            grads["lam"] = torch.where(ctx.lam > 0, grads["lam"], torch.zeros((), dtype=v.dtype, device=v.device))
-        grads = {nm: _masked(t, ok) for nm, t in grads.items()}
-        for nm in each:
-            if nm in ctx.shared:
-                grads[nm] = grads[nm].sum(0, keepdim=True)
-        blocks, cons = sel(summed, BLOCK_GRADIENTS), sel(summed, ("cons_a", "cons_b"))
+        grads = _per_problem(grads, ok, ctx.shared)
+        blocks, cons = sel(summed, BLOCK_GRADIENTS), sel(summed, _CONS)
         if blocks:
-            red = qp_gradients_blocks_shared(ctx.layout, ctx.J_blocks, ctx.r, v, u, k=problem.k, m=problem.m, want=blocks, eq_layout=ctx.eq_layout,
-                                             status_fwd=ctx.status, status_adj=ctx.adjoint_status)
-            if "lam" in red:
-                red["lam"] = torch.where(ctx.lam > 0, red["lam"], torch.zeros((), dtype=v.dtype, device=v.device))
-            grads.update(red)
+            grads.update(qp_gradients_blocks_shared(ctx.layout, ctx.J_blocks, ctx.r, v, u, k=problem.k, m=problem.m, want=blocks,
+                                                    eq_layout=ctx.eq_layout, status_fwd=ctx.status, status_adj=ctx.adjoint_status))
         if cons:
             grads.update(qp_gradients_shared(problem, v, u, cons, status_fwd=ctx.status, status_adj=ctx.adjoint_status))
+        if "lam" in grads:   # (per problem or summed; zeroing commutes with the mask: lam per problem is never summed here)
+            grads["lam"] = _where_lam_added(ctx.lam, grads["lam"])
         return (*[grads.get(nm) for nm in names], None, None, None, None)
 
     @staticmethod
@@ -659,7 +627,7 @@ class QPSolveBlocksFunction(torch.autograd.Function):
         forward status or tangent-solve status is not MO_STATUS_OK gets a ZERO tangent (the backward's rule); the solve's status words are
         kept (`tangent_status`)."""
         if dlam is not None:
-            dlam = torch.where(ctx.lam > 0, dlam, torch.zeros((), dtype=ctx.v.dtype, device=ctx.v.device))
+            dlam = _where_lam_added(ctx.lam, dlam)
         tangents = _given(BLOCK_TANGENTS, (dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b))
         return _jvp_result(ctx, *qp_jvp_blocks(ctx.problem, ctx.layout, ctx.J_blocks, ctx.r, ctx.v, tangents, eq_layout=ctx.eq_layout))
 
@@ -688,6 +656,21 @@ def _check_cons(cons_var, cons_a, cons_b) -> None:
 def _full(t: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
     """An input of solve_qp with its leading dimension of 1 broadcast over the batch, contiguous."""
     return None if t is None else (t.expand(B, *t.shape[1:]) if t.shape[0] != B else t).contiguous()
+
+
+def _pass_through(data, lam, cons_var, cons_a, cons_b):
+    """solve_qp's rule for its inputs.  B is the largest leading dimension among `data`, cons_a, cons_b and a tensor `lam` (flattened).  An
+    input with a leading dimension of 1 -- given once for the batch -- stays [1, ...], contiguous; any other is expanded to B, contiguous.
+    The constraint triple is shared only if all three are given once, else all three are expanded.  Returns (B, data, lam, (cons_a, cons_b,
+    cons_var)); None stays None and a `lam` that is no tensor is returned as it came."""
+    _check_cons(cons_var, cons_a, cons_b)
+    if isinstance(lam, torch.Tensor):
+        lam = lam.reshape(-1)
+    B = max(int(t.shape[0]) for t in (*data, cons_a, cons_b, lam) if isinstance(t, torch.Tensor))
+    one = lambda t: t.contiguous() if int(t.shape[0]) == 1 else _full(t, B)
+    cons = one if cons_var is not None and all(int(t.shape[0]) == 1 for t in (cons_var, cons_a, cons_b)) else (lambda t: _full(t, B))
+    opt = lambda f, t: f(t) if isinstance(t, torch.Tensor) else t
+    return B, [opt(one, t) for t in data], opt(one, lam), [opt(cons, t) for t in (cons_a, cons_b, cons_var)]
 
 
 def _result(v: torch.Tensor, status: torch.Tensor, n: int, m: int, k: int, return_all: bool, return_status: bool):
@@ -737,25 +720,14 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     ref = J if J is not None else G
     if ref.dim() != 3:
         raise ValueError("G / J must be [B, rows, n]")
-    B = max(int(t.shape[0]) for t in (G, c, J, r, A_eq, b_eq, cons_a, cons_b) if t is not None)
-    if isinstance(lam, torch.Tensor):
-        B = max(B, int(lam.numel()))
-    full = lambda t: _full(t, B)
-    one = lambda t: None if t is None else (t.contiguous() if int(t.shape[0]) == 1 else _full(t, B))   # given once: passed through
-    lam_t = None
-    if isinstance(lam, torch.Tensor):
-        if J is None:
-            raise ValueError("lam belongs to the (J, r) form")
-        lam_t = one(lam.reshape(-1))
-    elif float(lam) != 0.0:
-        if J is None:
-            raise ValueError("lam belongs to the (J, r) form")
-        lam_t = torch.full((B,), float(lam), dtype=ref.dtype, device=ref.device)
-    _check_cons(cons_var, cons_a, cons_b)
-    A_t = None if A_eq is None else one(A_eq).transpose(1, 2).contiguous()   # BatchedQP's layout: memory = k x n column-major
-    cons = one if cons_var is not None and all(int(t.shape[0]) == 1 for t in (cons_var, cons_a, cons_b)) else full
-    v, status = QPSolveFunction.apply(one(G), one(c), one(J), one(r), lam_t, A_t, one(b_eq), cons(cons_a), cons(cons_b),
-                                      cons(cons_var), params)
+    if J is None and (isinstance(lam, torch.Tensor) or float(lam) != 0.0):
+        raise ValueError("lam belongs to the (J, r) form")
+    B, (G_t, c_t, J_t, r_t, A_t, b_t), lam_t, cons = _pass_through((G, c, J, r, A_eq, b_eq), lam, cons_var, cons_a, cons_b)
+    if not isinstance(lam_t, torch.Tensor):
+        lam_t = None if float(lam) == 0.0 else torch.full((B,), float(lam), dtype=ref.dtype, device=ref.device)
+    if A_t is not None:
+        A_t = A_t.transpose(1, 2).contiguous()   # BatchedQP's layout: memory = k x n column-major
+    v, status = QPSolveFunction.apply(G_t, c_t, J_t, r_t, lam_t, A_t, b_t, *cons, params)
     k = 0 if A_eq is None else int(A_eq.shape[1])
     m = 0 if cons_a is None else int(cons_a.shape[1])
     return _result(v, status, int(ref.shape[2]), m, k, return_all, return_status)
@@ -766,20 +738,10 @@ def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, con
         raise ValueError("the residual-block form needs layout, J_blocks and r")
     if (eq_layout is None) != (J_eq_blocks is None) or (eq_layout is None) != (r_eq is None):
         raise ValueError("eq_layout, J_eq_blocks and r_eq come together")
-    if eq_layout is not None and (eq_layout.n != layout.n or eq_layout.dtype != layout.dtype or eq_layout.device != layout.device):
-        raise ValueError("eq_layout must share n, dtype and device with layout")
-    _check_cons(cons_var, cons_a, cons_b)
-    tensors = [t for t in (J_blocks, r, J_eq_blocks, r_eq, cons_a, cons_b) if t is not None]
-    if isinstance(lam, torch.Tensor):
-        lam = lam.reshape(-1)
-        tensors.append(lam)
-    B = max(int(t.shape[0]) for t in tensors)
-    full = lambda t: _full(t, B)
-    one = lambda t: None if t is None else (t.contiguous() if int(t.shape[0]) == 1 else _full(t, B))   # given once: passed through
-    lam_t = one(lam) if isinstance(lam, torch.Tensor) else torch.full((1,), float(lam), dtype=layout.dtype, device=layout.device)
-    cons = one if cons_var is not None and all(int(t.shape[0]) == 1 for t in (cons_var, cons_a, cons_b)) else full
-    v, status = QPSolveBlocksFunction.apply(one(J_blocks), one(r), lam_t, one(J_eq_blocks), one(r_eq), cons(cons_a), cons(cons_b),
-                                            cons(cons_var), layout, eq_layout, params)
-    k = 0 if eq_layout is None else eq_layout.rows
+    k = _eq_rows(layout, eq_layout, 0)
+    _, (J_t, r_t, J_eq_t, r_eq_t), lam_t, cons = _pass_through((J_blocks, r, J_eq_blocks, r_eq), lam, cons_var, cons_a, cons_b)
+    if not isinstance(lam_t, torch.Tensor):
+        lam_t = torch.full((1,), float(lam), dtype=layout.dtype, device=layout.device)
+    v, status = QPSolveBlocksFunction.apply(J_t, r_t, lam_t, J_eq_t, r_eq_t, *cons, layout, eq_layout, params)
     m = 0 if cons_a is None else int(cons_a.shape[1])
     return _result(v, status, layout.n, m, k, return_all, return_status)

@@ -1,9 +1,12 @@
 """What the tests of the sensitivity layer share (test_gpu_diff, test_gpu_tangent, test_gpu_blocks_diff, test_gpu_blocks_tangent,
-test_gpu_second_problem): problems, layouts, solve parameters and the oracle's KKT solves.  Not a test
-module: nothing here asserts."""
+test_gpu_shared_grad, test_gpu_blocks_shared_grad, test_gpu_fused_rhs, test_gpu_layouts, test_gpu_second_problem): problems, layouts, solve
+parameters, the oracle's KKT solves, plans and guarded buffers.  Not a test module: nothing here asserts."""
+import ctypes as C
+
 import numpy as np
 import torch
 
+from mini_opt_amd import _lib as L
 from mini_opt_amd import qp as Q
 from mini_opt_amd import synth
 from oracle import oracle as orc
@@ -23,6 +26,51 @@ def T(a, dt=torch.float64):
 
 def rel_inf_rows(got, ref):
     return np.max(np.abs(got - ref), axis=1) / np.max(np.abs(ref), axis=1)
+
+
+def cus():
+    return torch.cuda.get_device_properties(dev()).multi_processor_count
+
+
+def expand(t, B):
+    return t.detach().expand(B, *t.shape[1:]).contiguous()
+
+
+def ragged_batch(chunks):
+    """4 chunks(4096) + 1: more than one chunk, a chunk length that is no multiple of four, a shorter last chunk.  `chunks`: the chunk count
+    of (batch, CUs) of the launch under test (shared_grad_reference.chunks, blocks_shared_grad_reference.chunks)."""
+    return 4 * chunks(4096, cus()) + 1
+
+
+class Plan:
+    """A plan of a test's own (mo_plan_create / mo_plan_destroy): plan flags the cached plans of mini_opt_amd.diff do not have, calls whose
+    Python mirror makes a plan per call.  dtype: a torch dtype or MO_F64 / MO_F32; the handle is `.h`."""
+
+    def __init__(self, n, k, m, m_r, dtype, batch, flags=0):
+        desc = L.PlanDesc(n, k, m, m_r, Q._DT.get(dtype, dtype), 0, flags | L.EXTRA_PLAN_FLAGS, 0, int(batch))
+        self.h = C.c_void_p()
+        L.check(L.lib().mo_plan_create(C.byref(desc), C.byref(self.h)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        L.lib().mo_plan_destroy(self.h)
+
+
+CANARY = 777.0
+
+
+class Guarded:
+    """`count` elements starting `off` elements into a buffer filled with the canary: a base off 16 bytes when off is odd."""
+
+    def __init__(self, count, dt, off=1):
+        self.buf = torch.full((off + count + 64,), CANARY, dtype=dt, device=dev())
+        self.view = self.buf[off:off + count]
+        self.off, self.count = off, count
+
+    def intact(self):
+        return bool(torch.all(self.buf[:self.off] == CANARY)) and bool(torch.all(self.buf[self.off + self.count:] == CANARY))
 
 
 # ---- dense problems ----------------------------------------------------------------------------------------------------------------------------

@@ -91,6 +91,64 @@ def test_argument_errors_without_gpu(lib):
     assert b"bytes" in lib.mo_last_error()
 
 
+# ---- the front end (mini_opt_amd.diff): the partition of the block backward, the member table, the filled structs ---------------------------
+def test_partition_of_the_block_backward():
+    """(each, summed): what the batch shares goes to the reduced launches -- but r given once against J_blocks per problem is computed per
+    problem."""
+    from mini_opt_amd import diff as D
+    names = ["J_blocks", "r", "lam", "J_eq_blocks", "r_eq", "cons_a", "cons_b"]
+    assert list(D.QPSolveBlocksFunction.NAMES) == names
+    part = lambda want, shared: D._partition(want, frozenset(shared), "r", "J_blocks")
+    assert part(names, names) == ([], names)                                             # everything shared
+    assert part(names, ()) == (names, [])                                                # nothing shared
+    assert part(["J_blocks", "r", "lam"], ["r"]) == (["J_blocks", "r", "lam"], [])       # r shared, J_blocks per problem: each
+    assert part(["r", "r_eq"], ["r", "r_eq"]) == (["r"], ["r_eq"])                       # ... also when dJ_blocks is not asked for
+    assert part(["J_blocks", "r", "lam"], ["J_blocks", "r"]) == (["lam"], ["J_blocks", "r"])   # r and J_blocks both shared: summed
+    assert part(["r_eq", "cons_a", "cons_b"], ["cons_a", "cons_b"]) == (["r_eq"], ["cons_a", "cons_b"])
+    assert part(["r_eq", "cons_a", "cons_b"], ["r_eq", "J_eq_blocks"]) == (["cons_a", "cons_b"], ["r_eq"])
+
+
+def test_block_member_table_against_the_structs():
+    from mini_opt_amd import _lib as L
+    from mini_opt_amd import diff as D
+    assert tuple(D._BLOCK) == D.BLOCK_TANGENTS == ("J_blocks", "r", "lam", "J_eq_blocks", "r_eq", "cons_a", "cons_b")
+    assert D.BLOCK_GRADIENTS == D.BLOCK_TANGENTS[:5]
+    for struct, names, strided in ((L.BlockGrads, D.BLOCK_TANGENTS[:3], True), (L.BlockSharedGrads, D.BLOCK_GRADIENTS, False),
+                                   (L.BlockTangents, D.BLOCK_TANGENTS, True)):
+        fields = dict(struct._fields_)
+        for name in names:
+            ptr, stride, ld, _tail = D._BLOCK[name]
+            assert fields[ptr] is C.c_void_p and ld is None and (not strided or fields[stride] is C.c_int64), (struct, name)
+        assert {D._BLOCK[name][0] for name in names} == {f for f, t in struct._fields_ if t is C.c_void_p}   # every pointer has its name
+    assert D._BLOCK["cons_a"][1] == D._BLOCK["cons_b"][1] == "dcons_stride"
+
+
+def test_block_gradient_structs_are_filled_as_before():
+    """_outputs on CPU tensors (no launch) for a cost layout of 23 values in 11 rows and an equality layout of 7 values in k = 3 rows, against
+    the values qp_gradients_blocks (per problem, B = 5: strides values, rows, 1) and qp_gradients_blocks_shared (one instance per member,
+    pointers alone) set member by member before the table."""
+    import types
+    from mini_opt_amd import _lib as L
+    from mini_opt_amd import diff as D
+    lay = lambda values, rows: types.SimpleNamespace(n=7, values=values, rows=rows, dtype=torch.float64, device=torch.device("cpu"))
+    blocks = D._Blocks(lay(23, 11), lay(7, 3), 3, 4)
+    fields = lambda g: {f: getattr(g, f) for f, _ in g._fields_}
+    out, g = D._outputs(L.BlockGrads(), D._BLOCK, blocks, ("J_blocks", "r", "lam"), 5)
+    assert [tuple(t.shape) for t in out.values()] == [(5, 23), (5, 11), (5,)]
+    assert fields(g) == dict(dJ_blocks=out["J_blocks"].data_ptr(), dJ_stride=23, dr=out["r"].data_ptr(), dr_stride=11,
+                             dlambda=out["lam"].data_ptr(), dlambda_stride=1)
+    out, g = D._outputs(L.BlockGrads(), D._BLOCK, blocks, ("lam",), 5)
+    assert fields(g) == dict(dJ_blocks=None, dJ_stride=0, dr=None, dr_stride=0, dlambda=out["lam"].data_ptr(), dlambda_stride=1)
+    out, g = D._outputs(L.BlockSharedGrads(), D._BLOCK, blocks, D.BLOCK_GRADIENTS, 1, strided=False)
+    assert [tuple(t.shape) for t in out.values()] == [(1, 23), (1, 11), (1,), (1, 7), (1, 3)]
+    assert fields(g) == dict(dJ_blocks=out["J_blocks"].data_ptr(), dr=out["r"].data_ptr(), dlambda=out["lam"].data_ptr(),
+                             dJ_eq_blocks=out["J_eq_blocks"].data_ptr(), dr_eq=out["r_eq"].data_ptr())
+    out, g = D._outputs(L.BlockSharedGrads(), D._BLOCK, blocks, ("r_eq",), 1, strided=False)
+    assert fields(g) == dict(dJ_blocks=None, dr=None, dlambda=None, dJ_eq_blocks=None, dr_eq=out["r_eq"].data_ptr())
+    out, g = D._outputs(None, D._BLOCK, D._Blocks(None, lay(7, 3), 3, 4), ("J_eq_blocks", "r_eq"), 5)   # qp_gradients_eq_blocks: tensors alone
+    assert g is None and [tuple(t.shape) for t in out.values()] == [(5, 7), (5, 3)] and all(t.dtype == torch.float64 for t in out.values())
+
+
 # ---- the formulas ------------------------------------------------------------------------------------------------------------------------
 def _case(name, integers=False):
     rng = np.random.default_rng({"n7": 7007, "n33": 3303}[name])

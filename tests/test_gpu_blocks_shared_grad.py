@@ -17,7 +17,8 @@ from mini_opt_amd import diff as D
 from mini_opt_amd import qp as Q
 from tests import blocks_shared_grad_reference as BS
 from tests import shared_grad_reference as S
-from tests.sens_fixtures import LAM, N7_COST, PARAMS, T, UNIT, autograd_layout, dev, random_layout
+from tests.sens_fixtures import (CANARY, LAM, N7_COST, PARAMS, UNIT, Guarded, T, autograd_layout, cus, dev, expand, ragged_batch,
+                                 random_layout)
 
 pytestmark = pytest.mark.gpu
 F64, F32 = torch.float64, torch.float32
@@ -25,10 +26,6 @@ NPDT = {F64: np.float64, F32: np.float32}
 DTYPES = pytest.mark.parametrize("dt", [F64, F32], ids=["f64", "f32"])
 N7_EQ = [((0, 4, 0), 1), ((2, 6), 2)]     # the eq layout repeats an index inside a block: local column 0 LOSES variable 0
 COST_KEYS, EQ_KEYS = ("J_blocks", "lam"), ("J_eq_blocks", "r_eq")
-
-
-def cus():
-    return torch.cuda.get_device_properties(dev()).multi_processor_count
 
 
 class Case:
@@ -118,11 +115,6 @@ def test_integer_data_gives_the_integer_result(name, dt):
 
 
 # ---- 2. random data within the derived bound -----------------------------------------------------------------------------------------------
-def ragged_batch():
-    """4 chunks(4096) + 1: more than one chunk, a chunk length that is no multiple of four, a shorter last chunk."""
-    return 4 * BS.chunks(4096, cus()) + 1
-
-
 def per_problem_sum(c, d, dt, keys):
     """The float64 host sum of mo_qp_gradients_blocks' and mo_qp_gradients_eq_blocks' per-problem outputs."""
     v, u = T(d["V"], dt), T(d["U"], dt)
@@ -139,7 +131,7 @@ def test_random_data_against_the_float64_sum(name, which, dt):
     """B = 1 and 3 (less than one MFMA step), 5 (a ragged second step), 4 chunks + 1 and 4096 (many chunks), r per problem and shared: within
     the bound of the float64 direct sum, and within the same bound of the float64 host sum of the per-problem kernels' outputs."""
     c = Case.get(name, dt)
-    B = ragged_batch() if which == "ragged" else int(which)
+    B = ragged_batch(BS.chunks) if which == "ragged" else int(which)
     if which == "ragged":
         assert BS.chunks(B, cus()) > 1 and BS.chunk_len(B, cus()) % 4 != 0
     for r_shared in (False, True):
@@ -240,21 +232,6 @@ def test_empty_batch_with_an_r_per_problem_writes_zeros():
 
 
 # ---- 4. layout: strides, misaligned bases, canaries -------------------------------------------------------------------------------------------
-CANARY = 777.0
-
-
-class Guarded:
-    """`count` elements starting `off` elements into a buffer filled with the canary: a base off 16 bytes when off is odd."""
-
-    def __init__(self, count, dt, off=1):
-        self.buf = torch.full((off + count + 64,), CANARY, dtype=dt, device=dev())
-        self.view = self.buf[off:off + count]
-        self.off, self.count = off, count
-
-    def intact(self):
-        return bool(torch.all(self.buf[:self.off] == CANARY)) and bool(torch.all(self.buf[self.off + self.count:] == CANARY))
-
-
 def raw_call(c, plan, B, v, u, stride, J, r, r_stride, g, work, nbytes, base=0):
     rc = L.lib().mo_qp_gradients_blocks_shared(plan, c.lay.h, Q._ptr(J), Q._ptr(r), r_stride, c.eq_lay.h, B, Q._ptr(v), stride, Q._ptr(u), stride,
                                                None, None, C.byref(g), C.c_void_p(work.data_ptr() + base), nbytes, Q._stream())
@@ -465,10 +442,6 @@ def test_linearize_blocks_without_G_gives_the_bits_of_the_full_call(name, dt):
 
 
 # ---- 7. solve_qp end to end ----------------------------------------------------------------------------------------------------------------------
-def expand(t, B):
-    return t.detach().expand(B, *t.shape[1:]).contiguous()
-
-
 def bits_equal(a, b):
     """torch.equal on the bit patterns: a failed problem's row may hold NaN, which must be the same NaN."""
     as_int = torch.int64 if a.dtype == F64 else torch.int32

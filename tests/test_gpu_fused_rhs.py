@@ -2,6 +2,7 @@
 (csrc/kkt_fused_rhs.hip) against LU on the oracle's full system, against the generic kernel on a MO_PLAN_FORCE_GENERIC plan and against the
 fused Newton step; status words, layouts, scheduling, the launch path, solve_qp's autograd at n = 64 and one full-size launch.
 Bound everywhere: TOL64 = 1e-10 rel-inf per problem, the project's BASELINE tolerance; every problem of every shape is held to it."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -15,6 +16,8 @@ from mini_opt_amd import synth
 from oracle import oracle as orc
 from tests import diff_reference as R
 from tests import fused_rhs_reference as F
+from tests import sens_fixtures as S
+from tests.sens_fixtures import T, dev, device_problem, host_batch, oracle_kkt_solves, oracle_solver, rel_inf_rows
 
 pytestmark = pytest.mark.gpu
 TOL64 = 1e-10
@@ -23,55 +26,15 @@ IDS = [f"n{s[0]}k{s[1]}m{s[2]}-{lvl}" for s, lvl in CASES]
 MO_STEP_NO_INEQUALITIES = 1
 
 
-def dev():
-    return torch.device("cuda:0")
-
-
-def T(a, dt=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev()).contiguous()
-
-
-def rel_inf_rows(got, ref):
-    return np.max(np.abs(got - ref), axis=1) / np.max(np.abs(ref), axis=1)
-
-
-def host_batch(n, k, m, m_r, B, stream):
-    hb = synth.make_batch(n, k, m, m_r, B, stream=stream)
-    hb.G = np.einsum("bqi,bqj->bij", hb.J, hb.J) + hb.lam * np.eye(n)
-    hb.c = np.einsum("bqi,bq->bi", hb.J, hb.r)
-    return hb
-
-
-def device_problem(hb, level, dt=torch.float64, J_layout="row"):
-    kw = dict(n=hb.n, k=hb.k, m=hb.m)
-    if hb.k:
-        kw.update(A_eq=T(hb.A_eq, dt), b_eq=T(hb.b_eq, dt))
-    if hb.m:
-        kw.update(cons_var=T(hb.cons_var, torch.int32), cons_a=T(hb.cons_a, dt), cons_b=T(hb.cons_b, dt))
-    if level == "G":
-        return Q.BatchedQP(G=T(hb.G, dt), c=T(hb.c, dt), **kw)
-    if J_layout == "col":
-        return Q.BatchedQP(J=T(hb.J.transpose(0, 2, 1), dt), r=T(hb.r, dt), lam=hb.lam, J_layout="col", J_rows=hb.J.shape[1], **kw)
-    return Q.BatchedQP(J=T(hb.J, dt), r=T(hb.r, dt), lam=hb.lam, **kw)
-
-
 def expected_kernel(n, level):
     return "fused_rhs_%s_f64_n%d" % ("mfma" if level == "J" else "qp", 32 if n <= 32 else 64 if n <= 64 else 96 if n <= 96 else 128)
 
 
-class Plan:
-    """A plan of this test's own (plan flags the cached plans of mini_opt_amd.diff do not have)."""
-
-    def __init__(self, prob, batch, flags=0, dtype=L.MO_F64):
-        self.h = C.c_void_p()
-        desc = L.PlanDesc(prob.n, prob.k, prob.m, prob.m_r, dtype, 0, flags | L.EXTRA_PLAN_FLAGS, 0, int(batch))
-        L.check(L.lib().mo_plan_create(C.byref(desc), C.byref(self.h)))
-
-    def __enter__(self):
-        return self.h
-
-    def __exit__(self, *exc):
-        L.lib().mo_plan_destroy(self.h)
+@contextlib.contextmanager
+def Plan(prob, batch, flags=0, dtype=L.MO_F64):
+    """The handle of a plan of this test's own (plan flags the cached plans of mini_opt_amd.diff do not have)."""
+    with S.Plan(prob.n, prob.k, prob.m, prob.m_r, dtype, batch, flags) as plan:
+        yield plan.h
 
 
 def kkt_solve_on(plan, ps, v, rhs, flags=0, vars_stride=None, rhs_stride=None, out=None, out_stride=None):
@@ -88,26 +51,6 @@ def kernel_on(prob, flags=0, dtype=L.MO_F64, batch=8):
     ps = prob.as_struct()
     with Plan(prob, batch, flags, dtype) as plan:
         return L.lib().mo_plan_kkt_solve_kernel(plan, C.byref(ps)).decode()
-
-
-def oracle_solver(hb, p, state):
-    o = orc.Solver(orc.QP(G=np.tril(hb.G[p]), c=hb.c[p], A_eq=hb.A_eq[p].T if hb.k else None, b_eq=hb.b_eq[p] if hb.k else None,
-                          cons_var=hb.cons_var[p], cons_a=hb.cons_a[p], cons_b=hb.cons_b[p]))
-    o.variables[:] = state
-    return o
-
-
-def oracle_kkt_solves(o, n, k, m, rhs, g):
-    """delta with K delta = -rhs and u with K^T u = g by LU on the oracle's full_system() matrix Hf at its current state.  Hf is the
-    reference's BuildFullSystem: the row of r_comp divided by s, and the y and z unknowns negated, i.e. K = D_r Hf D_c with
-    D_r = diag(1, s, 1, 1), D_c = diag(1, 1, -1, -1)."""
-    Hf, _ = o.full_system()
-    s = np.array(o.variables[n:n + m])
-    d_r = np.concatenate([np.ones(n), s, np.ones(k + m)])
-    d_c = np.concatenate([np.ones(n + m), -np.ones(k + m)])
-    delta = d_c * np.linalg.solve(Hf, -rhs / d_r)
-    u = np.linalg.solve(Hf.T, d_c * g) / d_r
-    return delta, u
 
 
 def lu_references(hb, rhs, problems):

@@ -14,6 +14,7 @@ gather, ny2, ny34, mc4 and tiny, the fp32 unit, the generic kernel LDS-resident 
  5. once per kernel family, every output documented "may be NULL" as NULL: the remaining outputs keep their bits.
 The store sites of those outputs were read first: every one is behind a test of its pointer in kkt_fused.hip, kkt_fused_tiny.hip,
 kkt_fused_f32.hip and kkt_generic.hip."""
+import contextlib
 import ctypes as C
 import functools
 
@@ -25,6 +26,7 @@ from mini_opt_amd import _lib as L
 from mini_opt_amd import qp as Q
 from oracle import oracle as orc
 from tests import layout_cases as LC
+from tests import sens_fixtures as SF
 
 pytestmark = pytest.mark.gpu
 B = LC.B
@@ -42,22 +44,13 @@ def is_f32(case):
     return case.dtype == "f32"
 
 
-class Plan:
-    """A plan of this test's own, as Plan of tests/test_gpu_fused_rhs.py."""
-
-    def __init__(self, case, level, k=None, m=None, force_generic=False):
-        n, k0, m0, m_r = case.shape
-        flags = (L.MO_PLAN_FORCE_GENERIC if case.force_generic or force_generic else 0) | (L.MO_PLAN_NO_TINY if case.no_tiny else 0)
-        self.h = C.c_void_p()
-        desc = L.PlanDesc(n, k0 if k is None else k, m0 if m is None else m, m_r if level == "J" else 0, L.MO_F32 if is_f32(case) else L.MO_F64, 0,
-                          flags | L.EXTRA_PLAN_FLAGS, 0, B)
-        L.check(L.lib().mo_plan_create(C.byref(desc), C.byref(self.h)))
-
-    def __enter__(self):
-        return self.h
-
-    def __exit__(self, *exc):
-        L.lib().mo_plan_destroy(self.h)
+@contextlib.contextmanager
+def Plan(case, level, k=None, m=None, force_generic=False):
+    """The handle of a plan of this test's own for a case of tests/layout_cases.py."""
+    n, k0, m0, m_r = case.shape
+    flags = (L.MO_PLAN_FORCE_GENERIC if case.force_generic or force_generic else 0) | (L.MO_PLAN_NO_TINY if case.no_tiny else 0)
+    with SF.Plan(n, k0 if k is None else k, m0 if m is None else m, m_r if level == "J" else 0, L.MO_F32 if is_f32(case) else L.MO_F64, B, flags) as plan:
+        yield plan.h
 
 
 def ptr(buf):

@@ -50,7 +50,7 @@ from oracle import nls_oracle as N
 from oracle import oracle as orc
 from tests import blocks_diff_reference as BR
 from tests import diff_reference as R
-from tests.sens_fixtures import UNIT, device_problem, host_batch, oracle_kkt_solves, oracle_solver, random_layout
+from tests.sens_fixtures import UNIT, Plan, device_problem, host_batch, oracle_kkt_solves, oracle_solver, random_layout
 from tests.test_gpu_parity import TOL32, TOL64, T, rel_inf_rows, solves_agree_or_knife_edge
 from tests.test_gpu_residual_blocks import bound_terms, oracle_hessian, oracle_jacobian, pack_np
 from tests.test_gpu_residual_blocks import draw as draw_blocks
@@ -120,26 +120,6 @@ def pick_sample(B, first, healthy, failing, seed):
 def oracle_sample(healthy, seed, count=512):
     idx = np.flatnonzero(healthy)
     return np.sort(np.random.default_rng(seed).permutation(idx)[:count])
-
-
-class Plan:
-    """A plan of its own (mo_plan_create / mo_plan_destroy) for the calls whose Python mirror makes one per call."""
-
-    def __init__(self, n, k, m, m_r, dt, batch, flags=0):
-        desc = L.PlanDesc(n, k, m, m_r, Q._DT[dt], 0, flags | L.EXTRA_PLAN_FLAGS, 0, batch)
-        self.h = C.c_void_p()
-        L.check(L.lib().mo_plan_create(C.byref(desc), C.byref(self.h)))
-
-    def close(self):
-        if self.h is not None:
-            L.lib().mo_plan_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def full(shape, dt, value=NAN):

@@ -14,17 +14,13 @@ from mini_opt_amd import _lib as L
 from mini_opt_amd import diff as D
 from mini_opt_amd import qp as Q
 from tests import shared_grad_reference as S
-from tests.sens_fixtures import PARAMS, T, UNIT, dev, host_batch
+from tests.sens_fixtures import CANARY, PARAMS, UNIT, Guarded, T, cus, dev, expand, host_batch, ragged_batch
 
 pytestmark = pytest.mark.gpu
 F64, F32 = torch.float64, torch.float32
 NPDT = {F64: np.float64, F32: np.float32}
 SHAPES = [(7, 3, 4, 9), (16, 0, 0, 4), (33, 17, 6, 35), (64, 8, 32, 128), (128, 16, 64, 256)]   # (n, k, m, m_r)
 J_KEYS, G_KEYS = ("J", "r", "lam"), ("G", "c")
-
-
-def cus():
-    return torch.cuda.get_device_properties(dev()).multi_processor_count
 
 
 def row_keys(k, m):
@@ -109,11 +105,6 @@ def test_integer_data_gives_the_integer_result(shape, J_layout, dt):
 
 
 # ---- 2. random data within the derived bound ------------------------------------------------------------------------------------------------
-def ragged_batch():
-    """4 chunks(4096) + 1: more than one chunk, a chunk length that is no multiple of four, a shorter last chunk."""
-    return 4 * S.chunks(4096, cus()) + 1
-
-
 @pytest.mark.parametrize("dt", [F64, F32], ids=["f64", "f32"])
 @pytest.mark.parametrize("which", ["1", "3", "5", "ragged", "4096"])
 @pytest.mark.parametrize("shape", [SHAPES[2], SHAPES[3]], ids=["n33", "n64"])
@@ -121,7 +112,7 @@ def test_random_data_against_the_float64_sum(shape, which, dt):
     """B = 1 and 3 (less than one MFMA step), 5 (a ragged second step), 4 chunks + 1 and 4096 (many chunks): within the bound of the float64
     sum, and within the same bound of the float64 host sum of mo_qp_gradients' per-problem outputs."""
     n, k, m, m_r = shape
-    B = ragged_batch() if which == "ragged" else int(which)
+    B = ragged_batch(S.chunks) if which == "ragged" else int(which)
     if which == "ragged":
         assert S.chunks(B, cus()) > 1 and S.chunk_len(B, cus()) % 4 != 0
     d = data(shape, B, dt, 7 * n + B)
@@ -196,21 +187,6 @@ def test_empty_batch_writes_zeros():
 
 
 # ---- 4. layout: strides, leading dimensions, misaligned bases, canaries ----------------------------------------------------------------------
-CANARY = 777.0
-
-
-class Guarded:
-    """`count` elements starting `off` elements into a buffer filled with the canary: a base off 16 bytes when off is odd."""
-
-    def __init__(self, count, dt, off=1):
-        self.buf = torch.full((off + count + 64,), CANARY, dtype=dt, device=dev())
-        self.view = self.buf[off:off + count]
-        self.off, self.count = off, count
-
-    def intact(self):
-        return bool(torch.all(self.buf[:self.off] == CANARY)) and bool(torch.all(self.buf[self.off + self.count:] == CANARY))
-
-
 @pytest.mark.parametrize("dt", [F64, F32], ids=["f64", "f32"])
 @pytest.mark.parametrize("J_layout", ["row", "col"])
 @pytest.mark.parametrize("off", [1, 0], ids=["misaligned", "aligned"])
@@ -371,10 +347,6 @@ def test_no_allocation_on_the_launch_path():
 
 
 # ---- 6. solve_qp end to end ------------------------------------------------------------------------------------------------------------------
-def expand(t, B):
-    return t.detach().expand(B, *t.shape[1:]).contiguous()
-
-
 def adjoint_of(n, k, m, kw, x, s, y, z, status, J_level):
     """(V, U, ok) on the host for the loss x.sum(): the state solve_qp returned and the adjoint mo_kkt_solve gives for g = [1 | 0 | 0 | 0]."""
     v = torch.cat([x, s, y, z], dim=1).detach().contiguous()

@@ -59,6 +59,83 @@ def test_argument_errors_without_gpu():
     assert b"plan" in lib.mo_last_error()
 
 
+# ---- the front end (mini_opt_amd.diff): the partition of a backward, the member table, the filled struct ------------------------------------
+def test_partition_of_the_backward():
+    """(each, summed): what the batch shares goes to the reduced launch -- but r given once against a J per problem is computed per problem."""
+    from mini_opt_amd import diff as D
+    names = ["G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b"]
+    part = lambda want, shared: D._partition(want, frozenset(shared), "r", "J")
+    assert part(names, names) == ([], names)                                             # everything shared
+    assert part(names, ()) == (names, [])                                                # nothing shared
+    assert part(["J", "r", "lam"], ["r"]) == (["J", "r", "lam"], [])                     # r shared, J per problem: each
+    assert part(["r", "lam"], ["r", "lam"]) == (["r"], ["lam"])                          # ... also when J's gradient is not asked for
+    assert part(["J", "r", "lam"], ["J", "r"]) == (["lam"], ["J", "r"])                  # r and J both shared: summed
+    assert part(["c", "cons_a", "cons_b"], ["cons_a", "cons_b"]) == (["c"], ["cons_a", "cons_b"])
+    assert part(["c", "cons_a", "cons_b"], ["c"]) == (["cons_a", "cons_b"], ["c"])
+    assert part(["c", "b_eq"], ["A_eq", "G"]) == (["c", "b_eq"], [])                     # shared inputs whose gradient is not asked for
+
+
+def test_member_table_against_the_structs():
+    import ctypes as C
+    from mini_opt_amd import _lib as L
+    from mini_opt_amd import diff as D
+    assert tuple(D._DENSE) == D.GRADIENTS == ("G", "c", "J", "r", "lam", "A_eq", "b_eq", "cons_a", "cons_b")
+    for struct in (L.QPGrads, L.QPTangents):
+        fields = dict(struct._fields_)
+        for name, (ptr, stride, ld, _tail) in D._DENSE.items():
+            assert fields[ptr] is C.c_void_p and fields[stride] is C.c_int64 and (ld is None or fields[ld] is C.c_int32), (struct, name)
+    assert len({entry[0] for entry in D._DENSE.values()}) == 9                           # nine pointers ...
+    assert D._DENSE["cons_a"][1] == D._DENSE["cons_b"][1] == "dcons_stride"            # ... cons_a and cons_b behind one stride
+    assert D._DENSE["lam"][3](None) == ()
+
+
+def _filled(struct, out, pointers, **values):
+    """Every field of `struct`: the pointers of `out` under the fields named in `pointers`, `values`, and nothing else set."""
+    import ctypes as C
+    want = {f: (None if t is C.c_void_p else 0) for f, t in struct._fields_}
+    want.update({field: out[name].data_ptr() for name, field in pointers.items()})
+    want.update(values)
+    assert {f: getattr(struct, f) for f, _ in struct._fields_} == want
+
+
+@pytest.mark.parametrize("case", ["row", "row_padded", "col", "col_padded", "G"])
+def test_gradient_struct_is_filled_as_before(case):
+    """_dense_outputs on CPU tensors (no launch) for (n, k, m, m_r) = (7, 3, 4, 9), per problem at B = 5 and summed at 1, against the values
+    qp_gradients / qp_gradients_shared set member by member before the table: strides n n, n, n k, k, m, rows ld, m_r, 1 per problem and
+    none summed; dG_ld = n, dA_ld = k, dJ_ld and dJ_layout those of problem.J; a dJ with a padded leading dimension zero-filled."""
+    from mini_opt_amd import _lib as L
+    from mini_opt_amd import diff as D
+    from mini_opt_amd import qp as Q
+    n, k, m, m_r, B = 7, 3, 4, 9, 5
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
+    common = dict(n=n, k=k, m=m, A_eq=z(B, n, k), b_eq=z(B, k), cons_var=torch.zeros(B, m, dtype=torch.int32), cons_a=z(B, m), cons_b=z(B, m))
+    rows, ld, layout = {"row": (m_r, n, L.MO_ROW_MAJOR), "row_padded": (m_r, n + 3, L.MO_ROW_MAJOR), "col": (n, m_r, L.MO_COL_MAJOR),
+                        "col_padded": (n, m_r + 3, L.MO_COL_MAJOR), "G": (0, 0, 0)}[case]
+    if case == "G":
+        prob = Q.BatchedQP(G=z(B, n, n), c=z(B, n), **common)
+        want, pointers = ("G", "c", "A_eq", "b_eq", "cons_b"), dict(G="dG", c="dc", A_eq="dA_eq", b_eq="db_eq", cons_b="dcons_b")
+        lds = dict(dG_ld=7, dA_ld=3)
+        strides = dict(dG_stride=49, dc_stride=7, dA_stride=21, db_stride=3, dcons_stride=4)
+        shapes = dict(G=(7, 7), c=(7,), A_eq=(7, 3), b_eq=(3,), cons_b=(4,))
+    else:
+        prob = Q.BatchedQP(J=z(B, rows, ld), r=z(B, m_r), J_layout=case[:3], J_rows=m_r, **common)
+        want, pointers = ("J", "r", "lam", "cons_a", "cons_b"), dict(J="dJ", r="dr", lam="dlambda", cons_a="dcons_a", cons_b="dcons_b")
+        lds = dict(dJ_ld=ld, dJ_layout=layout)
+        strides = dict(dJ_stride=rows * ld, dr_stride=9, dlambda_stride=1, dcons_stride=4)
+        shapes = dict(J=(rows, ld), r=(9,), lam=(), cons_a=(4,), cons_b=(4,))
+    assert prob.m_r == (0 if case == "G" else m_r)
+    for lead, strided in ((B, True), (1, False)):
+        out, g = D._dense_outputs(prob, want, lead, strided)
+        assert isinstance(g, L.QPGrads) and tuple(out) == want
+        for name in want:
+            assert tuple(out[name].shape) == (lead, *shapes[name]) and out[name].dtype == torch.float64 and out[name].is_contiguous()
+        _filled(g, out, pointers, **lds, **(strides if strided else {}))
+        if case.endswith("padded"):
+            assert bool(torch.all(out["J"] == 0))
+    out, g = D._dense_outputs(prob, (), B, True)                                         # nothing asked for: nothing set
+    _filled(g, out, {})
+
+
 def test_chunk_count_is_a_function_of_batch_and_cus():
     assert [S.chunks(B, 256) for B in (0, 1, 31, 32, 33, 64, 65, 4096, 65536, 65537)] == [0, 1, 1, 1, 2, 2, 3, 128, 256, 256]
     assert S.chunk_len(65536, 256) == 256 and S.chunk_len(65, 256) == 22 and S.chunk_len(1, 256) == 1

@@ -643,6 +643,69 @@ int mo_qp_tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layou
                              const int32_t* cons_var, int64_t cons_stride, int64_t batch, const void* vars, int64_t vars_stride,
                              const mo_block_tangents* t, void* rho, int64_t rho_stride, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Per-row weights for residual-block costs: the cost  1/2 sum_i w_i (J x + r)_i^2 + 1/2 lambda |x|^2  with one weight per stacked residual
+ * row of the cost layout (block order, the order of r), per problem.  A per-block weight is the caller's repeat of it over the block's
+ * rows.  This is the pair rule of UpdateHessian with one factor per row, W_b the diagonal of block b's weights:
+ *   per block and local pair q <= p:   G_low[max(i, j), min(i, j)] += sum_rho w_rho J_b[rho, p] J_b[rho, q]      (i = idx_b[p], j = idx_b[q])
+ *   c[idx_b[p]] += sum_rho w_rho J_b[rho, p] r_rho       lambda on the diagonal after the sum, where > 0       half_sq = 1/2 sum w_rho r_rho^2
+ * A pair of local columns on one variable still lands once, on the diagonal; the order of every sum is that of the unweighted kernels.
+ * Every term is formed as (w_rho J_b[rho, p]) * (.): with every weight 1 the calls below compute the bits of their unweighted siblings, and
+ * with weights that are powers of four the bits of the siblings on (sqrt(w) J, sqrt(w) r).
+ * ZERO WEIGHTS.  A row whose weight is exactly 0 contributes exactly nothing: the forward never multiplies that row's J values or r (they
+ * may hold NaN or Inf: a measurement that is missing in some problems of the batch, under one layout), and in the backward dJ_blocks and dr
+ * at that row are exactly 0.  dweights at that row is computed like any other row, from whatever the data hold -- a caller that masks does
+ * not ask for it.  No sign or range is asked of w; a negative weight can make G indefinite (the solve then reports it in its status).
+ * weights: [batch][sum R_b] with weights_stride in elements, 0 = one instance for the batch.  weights == NULL: each call IS its sibling,
+ * bit for bit (dweights, as an output or as a tangent, is then MO_ERR_INVALID_ARGUMENT: "... weights is NULL").  J_stride = 0 with per-problem
+ * weights -- one fixed linear model, per-problem confidences -- is the main case: J is read in place, never expanded.
+ * No allocation and no synchronisation on any launch path; argument errors are judged before the plan is looked at, as the siblings do.
+ *
+ * mo_linearize_blocks_weighted: mo_linearize_blocks with the weights (G_out == NULL included).  No LDS rule: J_blocks, r and the weights go
+ * through LDS when (sum R_b P_b + 2 sum R_b) values fit 48 KiB (rows more than the sibling) and are read from global memory otherwise. */
+int mo_linearize_blocks_weighted(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
+                                 int64_t r_stride, const void* weights, int64_t weights_stride, double lambda, const void* lambda_vec,
+                                 int64_t lambda_stride, int64_t batch, void* G_out, int64_t G_stride, int32_t G_ld, void* c_out, int64_t c_stride,
+                                 void* half_sq_out, void* stream);
+/* mo_qp_gradients_blocks_weighted: mo_qp_gradients_blocks for the weighted cost.  With t = J_b x_loc + r_b and s = J_b u_loc (the kernel's t
+ * and w), per stacked row:
+ *   dJ_blocks[e] = w_row x (the unweighted value, repeated-variable term included)        dr[row] = -w_row s[row]        dlambda unchanged
+ *   dweights[row] = -s[row] t[row] + sum over the pairs {p, p'} of local columns of the row's block on ONE variable i of  u_i x_i J[row, p] J[row, p']
+ * The last sum is the derivative of the pair rule: such a pair lands once on the diagonal, so G lacks one w J_p . J_p' against the dense
+ * J^T W J, whose derivative -s t would count it twice; it exists only for blocks that name a variable twice (the pair lists are built by
+ * mo_residual_layout_create and are empty for almost every layout).  J_blocks and r are read for dJ_blocks, dr and dweights.
+ * MO_ERR_UNSUPPORTED if (2 n + 3 sum R_b) values (x, u_x; t, s, the weights) exceed 63 KiB -- sum R_b values more than the sibling. */
+typedef struct {
+  void* dJ_blocks; int64_t dJ_stride;
+  void* dr;        int64_t dr_stride;
+  void* dlambda;   int64_t dlambda_stride;
+  void* dweights;  int64_t dweights_stride;   /* sum R_b per problem */
+} mo_block_weighted_grads;
+int mo_qp_gradients_blocks_weighted(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride, const void* r,
+                                    int64_t r_stride, const void* weights, int64_t weights_stride, int64_t batch, const void* vars,
+                                    int64_t vars_stride, const void* u, int64_t u_stride, const mo_block_weighted_grads* out, void* stream);
+/* mo_qp_tangent_rhs_blocks_weighted: mo_qp_tangent_rhs_blocks for the weighted cost, rho_d += Gdot x + cdot with
+ *   Gdot = sum_b (dJ_b^T W_b J_b + J_b^T W_b dJ_b + J_b^T Wdot_b J_b)  (pair rule)      cdot = sum_b (dJ_b^T W_b r_b + J_b^T Wdot_b r_b + J_b^T W_b dr_b)
+ * i.e. the sibling's walk with  t := w t  and  tdot := w tdot + wdot t  per stacked row, the repeated-variable correction carrying the row's
+ * weight (and wdot, each pair once).  dweights is the tangent of the weights (NULL: zero; stride 0 = one direction for the batch); J_blocks
+ * is read with dJ_blocks, dr or dweights, r with dJ_blocks or dweights.  A row whose weight is 0 and whose wdot is 0 or absent is skipped.
+ * The transpose identity of the sibling holds with dweights among the members.
+ * MO_ERR_UNSUPPORTED if (2 n + 2 k + m + 3 sum R_b) values + 4 m bytes exceed 64 KiB -- sum R_b values more than the sibling. */
+typedef struct {
+  const void* dJ_blocks;    int64_t dJ_stride;
+  const void* dr;           int64_t dr_stride;
+  const void* dlambda;      int64_t dlambda_stride;
+  const void* dJ_eq_blocks; int64_t dJ_eq_stride;
+  const void* dr_eq;        int64_t dr_eq_stride;
+  const void* dcons_a; const void* dcons_b; int64_t dcons_stride;
+  const void* dweights;     int64_t dweights_stride;   /* sum R_b */
+} mo_block_weighted_tangents;
+int mo_qp_tangent_rhs_blocks_weighted(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride,
+                                      const void* r, int64_t r_stride, const void* weights, int64_t weights_stride,
+                                      const mo_residual_layout* eq_layout, const int32_t* cons_var, int64_t cons_stride, int64_t batch,
+                                      const void* vars, int64_t vars_stride, const mo_block_weighted_tangents* t, void* rho, int64_t rho_stride,
+                                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ from ._lib import MiniOptError, build  # noqa: F401
 _DIFF_EXPORTS = ("solve_qp", "kkt_solve", "qp_gradients", "qp_gradients_shared", "qp_gradients_blocks", "qp_gradients_eq_blocks",
                  "qp_gradients_blocks_shared", "QPSolveFunction",
                  "QPSolveBlocksFunction", "adjoint_status", "qp_tangent_rhs", "qp_jvp", "tangent_status",
-                 "qp_tangent_rhs_blocks", "qp_jvp_blocks")
+                 "qp_tangent_rhs_blocks", "qp_jvp_blocks", "qp_gradients_blocks_weighted", "qp_tangent_rhs_blocks_weighted",
+                 "qp_jvp_blocks_weighted", "QPSolveWeightedBlocksFunction")
 
 
 def __getattr__(name):  # the differentiable front end needs torch: imported on first use, like qp

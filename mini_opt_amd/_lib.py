@@ -37,7 +37,8 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_linearize_blocks", "mo_jacobian_blocks", "mo_nls_solve_blocks", "mo_kkt_solve", "mo_qp_gradients",
            "mo_qp_gradients_shared_workspace", "mo_qp_gradients_shared",
            "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_gradients_blocks_shared_workspace", "mo_qp_gradients_blocks_shared",
-           "mo_qp_tangent_rhs", "mo_qp_tangent_rhs_blocks"]
+           "mo_qp_tangent_rhs", "mo_qp_tangent_rhs_blocks",
+           "mo_linearize_blocks_weighted", "mo_qp_gradients_blocks_weighted", "mo_qp_tangent_rhs_blocks_weighted"]
 
 
 class PlanDesc(C.Structure):
@@ -135,6 +136,16 @@ class BlockTangents(C.Structure):
                 ("dcons_a", C.c_void_p), ("dcons_b", C.c_void_p), ("dcons_stride", C.c_int64)]
 
 
+class BlockWeightedGrads(C.Structure):
+    """mo_block_weighted_grads: mo_block_grads and the gradient of the per-row weights (mo_qp_gradients_blocks_weighted)."""
+    _fields_ = BlockGrads._fields_ + [("dweights", C.c_void_p), ("dweights_stride", C.c_int64)]
+
+
+class BlockWeightedTangents(C.Structure):
+    """mo_block_weighted_tangents: mo_block_tangents and the tangent of the per-row weights (mo_qp_tangent_rhs_blocks_weighted)."""
+    _fields_ = BlockTangents._fields_ + [("dweights", C.c_void_p), ("dweights_stride", C.c_int64)]
+
+
 NLS_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
 MO_NLS_EVAL_LINEARIZE, MO_NLS_EVAL_ERRORS, MO_NLS_EVAL_RETRACT, MO_NLS_EVAL_ITERATION_DONE = 0, 1, 2, 3
 MO_RETRACT_EUCLIDEAN, MO_RETRACT_WRAP_PI, MO_RETRACT_CALLBACK = 0, 1, 2
@@ -219,6 +230,10 @@ def lib() -> C.CDLL:
     L.mo_qp_gradients_blocks_shared.argtypes = [vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, C.POINTER(BlockSharedGrads), vp, i64, vp]
     L.mo_qp_tangent_rhs.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, C.POINTER(QPTangents), vp, i64, vp]
     L.mo_qp_tangent_rhs_blocks.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, C.POINTER(BlockTangents), vp, i64, vp]
+    L.mo_linearize_blocks_weighted.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, dbl, vp, i64, i64, vp, i64, i32, vp, i64, vp, vp]
+    L.mo_qp_gradients_blocks_weighted.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.POINTER(BlockWeightedGrads), vp]
+    L.mo_qp_tangent_rhs_blocks_weighted.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64,
+                                                    C.POINTER(BlockWeightedTangents), vp, i64, vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what the header declares
     _lib = L

@@ -59,6 +59,8 @@ struct mo_residual_layout {
   const int* g_ptr; const int4* g_ent; const int* c_ptr; const int4* c_ent; const int2* row_info; const int* win;
   // the backward schedule (mo_qp_gradients_blocks / mo_qp_gradients_eq_blocks, mo::BlockGradArgs)
   const int4* d_row; const int4* d_val; const int2* e_val; const int* d_idx; const int* d_dup;
+  // the pairs of local columns on one variable, per stacked row (mo_qp_gradients_blocks_weighted: dweights)
+  const int* d_pair; const int* d_plist;
   // the forward-mode schedule of an equality layout (mo_qp_tangent_rhs_blocks, mo::BlockTangentArgs): c_ptr / c_ent filtered by winners
   const int* w_ptr; const int4* w_ent;
 };
@@ -1178,7 +1180,7 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
       const int R = rows[b], P = params[b];
       const int32_t* idx = index + ib;
       for (int a = 0; a < P; ++a) {
-        for (int c = 0; c <= a; ++c) g_ent[g_cur[cell_of(idx[a], idx[c])]++] = make_int4((int)(off + (long long)a * R), (int)(off + (long long)c * R), R, 0);
+        for (int c = 0; c <= a; ++c) g_ent[g_cur[cell_of(idx[a], idx[c])]++] = make_int4((int)(off + (long long)a * R), (int)(off + (long long)c * R), R, (int)roff);
         c_ent[c_cur[idx[a]]++] = make_int4((int)(off + (long long)a * R), (int)roff, R, 0);
         win[(size_t)b * n + idx[a]] = (int)(off + (long long)a * R);  // UpdateJacobian assigns: the last local column wins
       }
@@ -1190,7 +1192,7 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
   // that variable (almost always none), and for equality blocks whether the value's column is the one that won its global column
   std::vector<int4> d_row((size_t)total_rows), d_val((size_t)values);
   std::vector<int2> e_val((size_t)values);
-  std::vector<int> d_idx(index, index + total_idx), d_dup;
+  std::vector<int> d_idx(index, index + total_idx), d_dup, d_pair((size_t)total_rows, -1), d_plist;
   {
     long long ib = 0, off = 0, roff = 0;
     for (int b = 0; b < num_blocks; ++b) {
@@ -1213,6 +1215,18 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
           e_val[(size_t)(off + (long long)a * R + q)] = make_int2((int)(roff + q), wins ? idx[a] : -1);
         }
       }
+      // the pairs p' < p of local columns on one variable, as offsets from the row's first value: {count, count x {p R, p' R, variable}}
+      int pairs_b = 0;
+      for (int a = 0; a < P; ++a)
+        for (int c = 0; c < a; ++c) pairs_b += idx[c] == idx[a];
+      if (pairs_b) {
+        const int start = (int)d_plist.size();
+        d_plist.push_back(pairs_b);
+        for (int a = 0; a < P; ++a)
+          for (int c = 0; c < a; ++c)
+            if (idx[c] == idx[a]) { d_plist.push_back(a * R); d_plist.push_back(c * R); d_plist.push_back(idx[a]); }
+        for (int q = 0; q < R; ++q) d_pair[(size_t)(roff + q)] = start;
+      }
       ib += P; off += (long long)R * P; roff += R;
     }
   }
@@ -1228,18 +1242,19 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
       w_ptr[(size_t)i + 1] = (int)w_ent.size();
     }
   }
-  // one device allocation: [g_ent | c_ent | g_ptr | c_ptr | row_info | win | d_row | d_val | e_val | d_idx | d_dup | w_ent | w_ptr], 16-byte aligned pieces
+  // one device allocation: [g_ent | c_ent | g_ptr | c_ptr | row_info | win | d_row | d_val | e_val | d_idx | d_dup | w_ent | w_ptr | d_pair | d_plist], 16-byte aligned pieces
   auto pad = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
   const size_t b_ge = pad(g_ent.size() * sizeof(int4)), b_ce = pad(c_ent.size() * sizeof(int4)), b_gp = pad(g_ptr.size() * sizeof(int)),
                b_cp = pad(c_ptr.size() * sizeof(int)), b_ri = pad(row_info.size() * sizeof(int2)), b_w = pad(win.size() * sizeof(int)),
                b_dr = pad(d_row.size() * sizeof(int4)), b_dv = pad(d_val.size() * sizeof(int4)), b_ev = pad(e_val.size() * sizeof(int2)),
                b_di = pad(d_idx.size() * sizeof(int)), b_dd = pad(d_dup.size() * sizeof(int)),
-               b_we = pad(w_ent.size() * sizeof(int4)), b_wp = pad(w_ptr.size() * sizeof(int));
+               b_we = pad(w_ent.size() * sizeof(int4)), b_wp = pad(w_ptr.size() * sizeof(int)),
+               b_dp = pad(d_pair.size() * sizeof(int)), b_dl = pad(d_plist.size() * sizeof(int));
   mo_residual_layout* L = new (std::nothrow) mo_residual_layout();
   if (!L) return fail(MO_ERR_HIP, "out of host memory");
   L->device = plan->desc.device; L->n = n; L->num_blocks = num_blocks; L->rows = (int)total_rows; L->values = values;
   L->dev = nullptr;
-  const size_t total = b_ge + b_ce + b_gp + b_cp + b_ri + b_w + b_dr + b_dv + b_ev + b_di + b_dd + b_we + b_wp;
+  const size_t total = b_ge + b_ce + b_gp + b_cp + b_ri + b_w + b_dr + b_dv + b_ev + b_di + b_dd + b_we + b_wp + b_dp + b_dl;
   if (hipSetDevice(plan->desc.device) != hipSuccess || hipMalloc(&L->dev, total) != hipSuccess) {
     (void)hipGetLastError();
     delete L;
@@ -1253,10 +1268,11 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
       {d_row.data(), d_row.size() * sizeof(int4), b_dr}, {d_val.data(), d_val.size() * sizeof(int4), b_dv},
       {e_val.data(), e_val.size() * sizeof(int2), b_ev}, {d_idx.data(), d_idx.size() * sizeof(int), b_di},
       {d_dup.data(), d_dup.size() * sizeof(int), b_dd},  {w_ent.data(), w_ent.size() * sizeof(int4), b_we},
-      {w_ptr.data(), w_ptr.size() * sizeof(int), b_wp}};
+      {w_ptr.data(), w_ptr.size() * sizeof(int), b_wp},  {d_pair.data(), d_pair.size() * sizeof(int), b_dp},
+      {d_plist.data(), d_plist.size() * sizeof(int), b_dl}};
   size_t at = 0;
-  const void* dst[13];
-  for (int i = 0; i < 13; ++i) {
+  const void* dst[15];
+  for (int i = 0; i < 15; ++i) {
     dst[i] = base + at;
     if (pieces[i].bytes && hipMemcpy(base + at, pieces[i].src, pieces[i].bytes, hipMemcpyHostToDevice) != hipSuccess) {
       (void)hipGetLastError();
@@ -1271,6 +1287,7 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
   L->d_row = (const int4*)dst[6]; L->d_val = (const int4*)dst[7]; L->e_val = (const int2*)dst[8]; L->d_idx = (const int*)dst[9];
   L->d_dup = (const int*)dst[10];
   L->w_ent = (const int4*)dst[11]; L->w_ptr = (const int*)dst[12];
+  L->d_pair = (const int*)dst[13]; L->d_plist = (const int*)dst[14];
   *out = L;
   return MO_OK;
 }
@@ -1357,6 +1374,68 @@ int mo_qp_gradients_blocks(mo_plan* plan, const mo_residual_layout* cost_layout,
   return MO_OK;
 }
 
+int mo_linearize_blocks_weighted(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
+                                 int64_t r_stride, const void* weights, int64_t weights_stride, double lambda, const void* lambda_vec,
+                                 int64_t lambda_stride, int64_t batch, void* G_out, int64_t G_stride, int32_t G_ld, void* c_out, int64_t c_stride,
+                                 void* half_sq_out, void* stream) {
+  if (!weights)
+    return mo_linearize_blocks(plan, layout, J_blocks, J_stride, r, r_stride, lambda, lambda_vec, lambda_stride, batch, G_out, G_stride, G_ld,
+                               c_out, c_stride, half_sq_out, stream);
+  g_err[0] = 0;
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, layout)) return rc;
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (layout->rows != plan->desc.m_r) return fail(MO_ERR_DIMENSION, "layout has %d rows, plan m_r = %d", layout->rows, plan->desc.m_r);
+  if (!J_blocks || !r) return fail(MO_ERR_INVALID_ARGUMENT, "J_blocks / r is NULL");
+  if (!c_out) return fail(MO_ERR_INVALID_ARGUMENT, "c_out is NULL");
+  if (G_out && G_ld < plan->desc.n) return fail(MO_ERR_DIMENSION, "G_ld %d < n", G_ld);
+  if (batch == 0) return MO_OK;
+  mo::BlocksArgs a = blocks_args(layout, batch);
+  a.J = J_blocks; a.J_stride = J_stride; a.r = r; a.r_stride = r_stride;
+  a.weights = weights; a.weights_stride = weights_stride;
+  a.lambda = lambda; a.lambda_vec = lambda_vec; a.lambda_vec_stride = lambda_stride;
+  a.G_out = G_out; a.G_out_stride = G_stride; a.G_out_ld = G_ld;
+  a.c_out = c_out; a.c_out_stride = c_stride; a.half_sq_out = half_sq_out;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_blocks_linearize(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+int mo_qp_gradients_blocks_weighted(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride, const void* r,
+                                    int64_t r_stride, const void* weights, int64_t weights_stride, int64_t batch, const void* vars,
+                                    int64_t vars_stride, const void* u, int64_t u_stride, const mo_block_weighted_grads* out, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (!weights) {
+    if (out && out->dweights) return fail(MO_ERR_INVALID_ARGUMENT, "dweights asked for but weights is NULL");
+    if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+    const mo_block_grads g = {out->dJ_blocks, out->dJ_stride, out->dr, out->dr_stride, out->dlambda, out->dlambda_stride};
+    return mo_qp_gradients_blocks(plan, cost_layout, J_blocks, J_stride, r, r_stride, batch, vars, vars_stride, u, u_stride, &g, stream);
+  }
+  if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
+  if (!vars) return fail(MO_ERR_INVALID_ARGUMENT, "vars is NULL");
+  if (!u) return fail(MO_ERR_INVALID_ARGUMENT, "u is NULL");
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if ((out->dJ_blocks || out->dr || out->dweights) && (!J_blocks || !r))
+    return fail(MO_ERR_INVALID_ARGUMENT, "dJ_blocks / dr / dweights asked for but J_blocks / r is NULL");
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, cost_layout)) return rc;
+  if (!mo::blocks_grad_fits(plan->desc.n, cost_layout->rows, plan->elem, true))
+    return fail(MO_ERR_UNSUPPORTED, "n = %d, %d residual rows: the vectors of one problem (2 n + 3 rows values) exceed the 63 KiB of LDS the weighted block gradient kernel uses", plan->desc.n, cost_layout->rows);
+  if (batch == 0 || (!out->dJ_blocks && !out->dr && !out->dlambda && !out->dweights)) return MO_OK;
+  mo::BlockGradArgs a = block_grad_args(plan, cost_layout, batch, vars, vars_stride, u, u_stride);
+  a.J = J_blocks; a.J_stride = J_stride; a.r = r; a.r_stride = r_stride;
+  a.weights = weights; a.weights_stride = weights_stride;
+  a.d_pair = cost_layout->d_pair; a.d_plist = cost_layout->d_plist;
+  a.dJ = out->dJ_blocks; a.dJ_stride = out->dJ_stride; a.dr = out->dr; a.dr_stride = out->dr_stride;
+  a.dlambda = out->dlambda; a.dlambda_stride = out->dlambda_stride;
+  a.dw = out->dweights; a.dw_stride = out->dweights_stride;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_blocks_grad(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
 int mo_qp_gradients_eq_blocks(mo_plan* plan, const mo_residual_layout* eq_layout, int64_t batch, const void* vars, int64_t vars_stride,
                               const void* u, int64_t u_stride, void* dJ_eq_blocks, int64_t dJ_eq_stride, void* dr_eq,
                               int64_t dr_eq_stride, void* stream) {
@@ -1438,23 +1517,62 @@ int mo_qp_gradients_blocks_shared(mo_plan* plan, const mo_residual_layout* cost_
   return MO_OK;
 }
 
+}  // extern "C"
+
+namespace {
+int tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride, const void* r,
+                       int64_t r_stride, const void* weights, int64_t weights_stride, const void* dweights, int64_t dweights_stride,
+                       const mo_residual_layout* eq_layout, const int32_t* cons_var, int64_t cons_stride, int64_t batch, const void* vars,
+                       int64_t vars_stride, const mo_block_tangents* t, void* rho, int64_t rho_stride, void* stream);
+}  // namespace
+
+extern "C" {
+
+int mo_qp_tangent_rhs_blocks_weighted(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride,
+                                      const void* r, int64_t r_stride, const void* weights, int64_t weights_stride,
+                                      const mo_residual_layout* eq_layout, const int32_t* cons_var, int64_t cons_stride, int64_t batch,
+                                      const void* vars, int64_t vars_stride, const mo_block_weighted_tangents* wt, void* rho, int64_t rho_stride,
+                                      void* stream) {
+  g_err[0] = 0;
+  if (!wt) return fail(MO_ERR_INVALID_ARGUMENT, "t is NULL");
+  if (wt->dweights && !weights) return fail(MO_ERR_INVALID_ARGUMENT, "dweights given but weights is NULL");
+  const mo_block_tangents t = {wt->dJ_blocks, wt->dJ_stride, wt->dr, wt->dr_stride, wt->dlambda, wt->dlambda_stride, wt->dJ_eq_blocks,
+                               wt->dJ_eq_stride, wt->dr_eq, wt->dr_eq_stride, wt->dcons_a, wt->dcons_b, wt->dcons_stride};
+  return tangent_rhs_blocks(plan, cost_layout, J_blocks, J_stride, r, r_stride, weights, weights_stride, wt->dweights, wt->dweights_stride,
+                            eq_layout, cons_var, cons_stride, batch, vars, vars_stride, &t, rho, rho_stride, stream);
+}
+
 int mo_qp_tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride,
                              const void* r, int64_t r_stride, const mo_residual_layout* eq_layout, const int32_t* cons_var,
                              int64_t cons_stride, int64_t batch, const void* vars, int64_t vars_stride, const mo_block_tangents* t, void* rho,
                              int64_t rho_stride, void* stream) {
   g_err[0] = 0;
+  return tangent_rhs_blocks(plan, cost_layout, J_blocks, J_stride, r, r_stride, nullptr, 0, nullptr, 0, eq_layout, cons_var, cons_stride, batch,
+                            vars, vars_stride, t, rho, rho_stride, stream);
+}
+
+}  // extern "C"
+
+namespace {
+// mo_qp_tangent_rhs_blocks (weights NULL) and mo_qp_tangent_rhs_blocks_weighted: one admission, one launch
+int tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, int64_t J_stride, const void* r,
+                       int64_t r_stride, const void* weights, int64_t weights_stride, const void* dweights, int64_t dweights_stride,
+                       const mo_residual_layout* eq_layout, const int32_t* cons_var, int64_t cons_stride, int64_t batch, const void* vars,
+                       int64_t vars_stride, const mo_block_tangents* t, void* rho, int64_t rho_stride, void* stream) {
   // (what can be judged from the arguments alone comes first)
   if (!t) return fail(MO_ERR_INVALID_ARGUMENT, "t is NULL");
   if (!vars || !rho) return fail(MO_ERR_INVALID_ARGUMENT, "vars / rho is NULL");
   if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
-  if ((t->dJ_blocks || t->dr) && (!J_blocks || !r)) return fail(MO_ERR_INVALID_ARGUMENT, "dJ_blocks / dr given but J_blocks / r is NULL");
+  if ((t->dJ_blocks || t->dr || dweights) && (!J_blocks || !r))
+    return fail(MO_ERR_INVALID_ARGUMENT, weights ? "dJ_blocks / dr / dweights given but J_blocks / r is NULL" : "dJ_blocks / dr given but J_blocks / r is NULL");
   if (t->dcons_a && !cons_var) return fail(MO_ERR_INVALID_ARGUMENT, "dcons_a given but cons_var is NULL");
   const mo_residual_layout* eq;
   if (int rc = check_layout_pair(plan, cost_layout, eq_layout, t->dJ_eq_blocks || t->dr_eq, "given", &eq)) return rc;
   const mo_plan_desc& d = plan->desc;
-  if (!mo::blocks_tangent_fits(d.n, d.k, d.m, cost_layout->rows, plan->elem))
+  const bool weighted = weights != nullptr;
+  if (!mo::blocks_tangent_fits(d.n, d.k, d.m, cost_layout->rows, plan->elem, weighted))
     return fail(MO_ERR_UNSUPPORTED, "n = %d, k = %d, m = %d, %d residual rows: the vectors of one problem (%zu B) exceed the 64 KiB of LDS the block tangent kernel uses",
-                d.n, d.k, d.m, cost_layout->rows, mo::blocks_tangent_lds_bytes(d.n, d.k, d.m, cost_layout->rows, plan->elem));
+                d.n, d.k, d.m, cost_layout->rows, mo::blocks_tangent_lds_bytes(d.n, d.k, d.m, cost_layout->rows, plan->elem, weighted));
   if (batch == 0) return MO_OK;
   mo::BlockTangentArgs a;
   memset(&a, 0, sizeof(a));
@@ -1467,14 +1585,18 @@ int mo_qp_tangent_rhs_blocks(mo_plan* plan, const mo_residual_layout* cost_layou
   else { a.e_row = eq->d_row; a.e_val = eq->e_val; a.w_ptr = eq->w_ptr; a.w_ent = eq->w_ent; }
   if (d.m == 0) { a.t.dcons_a = nullptr; a.t.dcons_b = nullptr; }
   else if (cons_var) { a.cons_var = cons_var; a.cons_stride = cons_stride; }
-  if (a.t.dJ_blocks || a.t.dr) {  // the only tangents that read the blocks; r only against dJ_blocks
+  a.weights = weights; a.weights_stride = weights_stride; a.dw = dweights; a.dw_stride = dweights_stride;
+  if (a.t.dJ_blocks || a.t.dr || a.dw) {  // the only tangents that read the blocks; r only against dJ_blocks and dweights
     a.J = J_blocks; a.J_stride = J_stride;
-    if (a.t.dJ_blocks) { a.r = r; a.r_stride = r_stride; }
+    if (a.t.dJ_blocks || a.dw) { a.r = r; a.r_stride = r_stride; }
   }
   MO_HIP_CHECK(hipSetDevice(d.device));
   MO_HIP_CHECK(mo::launch_blocks_tangent(a, d.dtype, plan->num_cus, (hipStream_t)stream));
   return MO_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int mo_residual_eval(mo_plan* plan, int32_t family, int32_t rows, const void* params, const void* x, int64_t x_stride,
                      int64_t batch, void* r, int64_t r_stride, void* J, int64_t J_stride, int32_t J_ld, int32_t J_layout,

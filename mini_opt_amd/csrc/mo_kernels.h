@@ -174,7 +174,7 @@ struct BlocksArgs {
   long long values;           // sum R_b P_b: packed Jacobian length per problem
   long long batch;
   const int* g_ptr;           // [n * n + 1] CSR over the cells of G in column-major order (strict upper cells: empty lists)
-  const int4* g_ent;          // {offset of J col a, offset of J col b, R_b, 0}: G(i, j) += J_a . J_b, in the reference's order
+  const int4* g_ent;          // {offset of J col a, offset of J col b, R_b, first stacked row of block b}: G(i, j) += J_a . J_b, in the reference's order
   const int* c_ptr;           // [n + 1]
   const int4* c_ent;          // {offset of J col a, offset of block b's rows in r, R_b, a's partner list in d_dup or -1}: c(i) += J_a . r_b
   const int2* row_info;       // [rows] {b * n, row within block b}
@@ -187,6 +187,9 @@ struct BlocksArgs {
   void* half_sq_out;          // [batch] or NULL
   void* J_out; long long J_out_stride; int J_out_ld; int J_out_row_major;
   void* abs_sum_out;          // [batch] or NULL
+  // mo_linearize_blocks_weighted (behind every older field): one weight per stacked row, NULL = unweighted; g_ent's fourth component is the
+  // first stacked row of the entry's block (c_ent.y has it already)
+  const void* weights; long long weights_stride;
 };
 hipError_t launch_blocks_linearize(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
 hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
@@ -209,8 +212,13 @@ struct BlockGradArgs {
   void* dJ; long long dJ_stride;
   void* dr; long long dr_stride;
   void* dlambda; long long dlambda_stride;
+  // mo_qp_gradients_blocks_weighted (behind every older field): NULL weights = unweighted
+  const void* weights; long long weights_stride;
+  void* dw; long long dw_stride;
+  const int* d_pair;          // [rows] start of the row's block's pair list in d_plist, -1: the block repeats no variable
+  const int* d_plist;         // pair lists: {count, count x {p R_b, p' R_b, variable}}: the pairs p' < p of local columns on one variable
 };
-bool blocks_grad_fits(int n, int rows, int elem_size);   // the vectors the kernel keeps in LDS (x, u_x, t, w) within 63 KiB
+bool blocks_grad_fits(int n, int rows, int elem_size, bool weighted = false);   // the vectors the kernel keeps in LDS (x, u_x, t, w; the weights) within 63 KiB
 hipError_t launch_blocks_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream);
 hipError_t launch_blocks_eq_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream);
 
@@ -322,9 +330,12 @@ struct BlockTangentArgs {
   const int* cons_var; long long cons_stride;
   mo_block_tangents t;        // NULL members are zero tangents
   void* rho; long long rho_stride;
+  // mo_qp_tangent_rhs_blocks_weighted (behind every older field): NULL weights = unweighted; dw the tangent of the weights (NULL: zero)
+  const void* weights; long long weights_stride;
+  const void* dw; long long dw_stride;
 };
-size_t blocks_tangent_lds_bytes(int n, int k, int m, int rows, int elem_size);   // the vectors the kernel always keeps in LDS
-bool blocks_tangent_fits(int n, int k, int m, int rows, int elem_size);          // ... within 64 KiB
+size_t blocks_tangent_lds_bytes(int n, int k, int m, int rows, int elem_size, bool weighted = false);   // the vectors the kernel always keeps in LDS
+bool blocks_tangent_fits(int n, int k, int m, int rows, int elem_size, bool weighted = false);          // ... within 64 KiB
 hipError_t launch_blocks_tangent(const BlockTangentArgs& a, int dtype, int num_cus, hipStream_t stream);
 
 }  // namespace mo

@@ -24,7 +24,11 @@ namespace {
 constexpr size_t kStageBudget = 48 * 1024;  // per workgroup: above it the packed values and tangents are read straight from global memory
 constexpr size_t kTangentLds = 64 * 1024;   // the vectors the kernel always keeps in LDS and, staged, the values on top
 
-template <typename T, bool kStaged>
+// kW (mo_qp_tangent_rhs_blocks_weighted): Gdot = sum_b (dJ^T W J + J^T W dJ + J^T Wdot J), cdot = sum_b (dJ^T W r + J^T Wdot r + J^T W dr).
+// Phase 2 keeps the weights in LDS and stores  t := w t  and  tdot := w tdot + wdot t  per stacked row, so that phase 3 is the unweighted walk;
+// a row whose two values are exactly 0 (weight 0, no direction in it) is skipped there, whatever its J and dJ hold.  The repeated-variable
+// correction carries the row's weight, and for the pair's derivative along wdot each pair is taken once (the partner behind the column).
+template <typename T, bool kStaged, bool kW = false>
 __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTangentArgs a, const int width) {
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char smem[];
@@ -36,7 +40,8 @@ __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTan
   T* std_ = st + rows;  // tdot = dJ x_loc + dr
   T* srd = std_ + rows; // rho_d
   T* spe = srd + n;     // rho_pe
-  T* sJ = spe + k;      // staged: J_blocks, dJ_blocks, r, dr
+  T* sg = spe + k;      // kW: the weights
+  T* sJ = sg + (kW ? rows : 0);   // staged: J_blocks, dJ_blocks, r, dr
   T* sdJ = sJ + (kStaged ? a.values : 0);
   T* sR = sdJ + (kStaged ? a.values : 0);
   T* sdR = sR + (kStaged ? rows : 0);
@@ -44,7 +49,9 @@ __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTan
   const int tid = threadIdx.x;
   const mo_block_tangents& t = a.t;
   const bool has_dJ = t.dJ_blocks != nullptr, has_dr = t.dr != nullptr;
-  const bool cost = has_dJ || has_dr;                 // the only tangents that read J_blocks; r is read only against dJ_blocks
+  const bool has_dw = kW && a.dw != nullptr;
+  const bool need_r = has_dJ || has_dw;               // r is read only against dJ_blocks (and the tangent of the weights)
+  const bool cost = has_dJ || has_dr || has_dw;       // the only tangents that read J_blocks
   const bool eq = k > 0 && t.dJ_eq_blocks != nullptr;
   const bool cons = m > 0 && t.dcons_a != nullptr;
   const int sub = tid / width, l = tid - sub * width, per_pass = kThreads / width;
@@ -64,7 +71,9 @@ __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTan
     const T* vp = (const T*)a.vars + p * a.vars_stride;
     T* rho = (T*)a.rho + p * a.rho_stride;
     const T* Jv = cost ? (const T*)a.J + p * a.J_stride : nullptr;
-    const T* rv = has_dJ ? (const T*)a.r + p * a.r_stride : nullptr;
+    const T* rv = need_r ? (const T*)a.r + p * a.r_stride : nullptr;
+    const T* wv = kW ? (const T*)a.weights + p * a.weights_stride : nullptr;
+    const T* dwv = has_dw ? (const T*)a.dw + p * a.dw_stride : nullptr;
     const T* dJv = has_dJ ? (const T*)t.dJ_blocks + p * t.dJ_stride : nullptr;
     const T* drv = has_dr ? (const T*)t.dr + p * t.dr_stride : nullptr;
     const T* dJe = eq ? (const T*)t.dJ_eq_blocks + p * t.dJ_eq_stride : nullptr;
@@ -89,8 +98,10 @@ __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTan
       Jv = sJ;
       if (has_dJ) {
         for (long long i = tid; i < a.values; i += kThreads) sdJ[i] = dJv[i];
-        for (int i = tid; i < rows; i += kThreads) sR[i] = rv[i];
         dJv = sdJ;
+      }
+      if (need_r) {
+        for (int i = tid; i < rows; i += kThreads) sR[i] = rv[i];
         rv = sR;
       }
       if (has_dr) {
@@ -112,8 +123,29 @@ __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTan
             td += p2;
           }
           tt += rv[row];
+        } else if (has_dw) {
+          for (int c = 0; c < ri.z; ++c) {
+            const T p1 = Jv[ri.x + c * ri.y] * sx[a.d_idx[ri.w + c]];
+            tt += p1;
+          }
+          tt += rv[row];
         }
         if (has_dr) td += drv[row];
+        if (kW) {
+          const T g = wv[row];
+          sg[row] = g;
+          const T gt = g * tt, gd = g * td;
+          T tw = g == (T)0 ? (T)0 : gt, tdw = g == (T)0 ? (T)0 : gd;
+          if (has_dw) {
+            const T gdot = dwv[row];
+            if (gdot != (T)0) {
+              const T pw = gdot * tt;
+              tdw += pw;
+            }
+          }
+          tt = tw;
+          td = tdw;
+        }
         st[row] = tt;
         std_[row] = td;
       }
@@ -133,28 +165,49 @@ __global__ __launch_bounds__(kThreads) void blocks_tangent_kernel(const BlockTan
               T d = 0;
               if (has_dJ) {
                 for (int q = 0; q < c.z; ++q) {
+                  if (kW && st[c.y + q] == (T)0 && std_[c.y + q] == (T)0) continue;
                   const T p1 = dJv[c.x + q] * st[c.y + q], p2 = Jv[c.x + q] * std_[c.y + q];
                   d += p1;
                   d += p2;
                 }
-                const int dup = c.w;
-                if (dup >= 0) {  // a repeated variable inside the block: the pair landed once, on the diagonal
-                  const int cnt = a.d_dup[dup];
-                  for (int j = 1; j <= cnt; ++j) {
-                    const int o = a.d_dup[dup + j];
-                    T dd = 0;
+              } else {
+                for (int q = 0; q < c.z; ++q) {
+                  if (kW && std_[c.y + q] == (T)0) continue;
+                  const T p2 = Jv[c.x + q] * std_[c.y + q];
+                  d += p2;
+                }
+              }
+              const int dup = c.w;
+              if (dup >= 0 && (has_dJ || has_dw)) {  // a repeated variable inside the block: the pair landed once, on the diagonal
+                const int cnt = a.d_dup[dup];
+                for (int j = 1; j <= cnt; ++j) {
+                  const int o = a.d_dup[dup + j];
+                  T dd = 0;
+                  if (kW) {
+                    for (int q = 0; q < c.z; ++q) {
+                      const T g = sg[c.y + q];
+                      if (has_dJ && g != (T)0) {
+                        const T gj = g * dJv[c.x + q];
+                        const T pd = gj * Jv[o + q];
+                        dd += pd;
+                      }
+                      if (has_dw && o > c.x) {
+                        const T gdot = dwv[c.y + q];
+                        if (gdot != (T)0) {
+                          const T gj = gdot * Jv[c.x + q];
+                          const T pd = gj * Jv[o + q];
+                          dd += pd;
+                        }
+                      }
+                    }
+                  } else {
                     for (int q = 0; q < c.z; ++q) {
                       const T pd = dJv[c.x + q] * Jv[o + q];
                       dd += pd;
                     }
-                    const T px = xi * dd;
-                    d -= px;
                   }
-                }
-              } else {
-                for (int q = 0; q < c.z; ++q) {
-                  const T p2 = Jv[c.x + q] * std_[c.y + q];
-                  d += p2;
+                  const T px = xi * dd;
+                  d -= px;
                 }
               }
               acc += d;
@@ -220,10 +273,19 @@ int width_for(int n) {
 }
 
 template <typename T> hipError_t launch_t(const BlockTangentArgs& a, int num_cus, hipStream_t stream) {
-  const size_t vectors = blocks_tangent_lds_bytes(a.n, a.k, a.m, a.rows, sizeof(T));
-  const bool cost = a.t.dJ_blocks || a.t.dr;
+  const bool weighted = a.weights != nullptr;
+  const size_t vectors = blocks_tangent_lds_bytes(a.n, a.k, a.m, a.rows, sizeof(T), weighted);
+  const bool cost = a.t.dJ_blocks || a.t.dr || (weighted && a.dw);
   const size_t stage = cost ? (size_t)(2 * (a.values + a.rows)) * sizeof(T) : 0;
   const int width = width_for(a.n);
+  if (weighted) {
+    if (cost && stage <= kStageBudget && vectors + stage <= kTangentLds) {
+      hipLaunchKernelGGL((blocks_tangent_kernel<T, true, true>), dim3(grid_for(a.batch, num_cus, vectors + stage)), dim3(kThreads), vectors + stage, stream, a, width);
+    } else {
+      hipLaunchKernelGGL((blocks_tangent_kernel<T, false, true>), dim3(grid_for(a.batch, num_cus, vectors)), dim3(kThreads), vectors, stream, a, width);
+    }
+    return hipGetLastError();
+  }
   if (cost && stage <= kStageBudget && vectors + stage <= kTangentLds) {
     hipLaunchKernelGGL((blocks_tangent_kernel<T, true>), dim3(grid_for(a.batch, num_cus, vectors + stage)), dim3(kThreads), vectors + stage, stream, a, width);
   } else {
@@ -234,16 +296,18 @@ template <typename T> hipError_t launch_t(const BlockTangentArgs& a, int num_cus
 
 }  // namespace
 
-size_t blocks_tangent_lds_bytes(int n, int k, int m, int rows, int elem_size) {
-  return (size_t)(2 * (long long)n + 2 * (long long)k + (long long)m + 2 * (long long)rows) * elem_size + (size_t)m * sizeof(int);
+size_t blocks_tangent_lds_bytes(int n, int k, int m, int rows, int elem_size, bool weighted) {
+  return (size_t)(2 * (long long)n + 2 * (long long)k + (long long)m + (weighted ? 3 : 2) * (long long)rows) * elem_size + (size_t)m * sizeof(int);
 }
 
-bool blocks_tangent_fits(int n, int k, int m, int rows, int elem_size) { return blocks_tangent_lds_bytes(n, k, m, rows, elem_size) <= kTangentLds; }
+bool blocks_tangent_fits(int n, int k, int m, int rows, int elem_size, bool weighted) {
+  return blocks_tangent_lds_bytes(n, k, m, rows, elem_size, weighted) <= kTangentLds;
+}
 
 hipError_t launch_blocks_tangent(const BlockTangentArgs& a, int dtype, int num_cus, hipStream_t stream) {
   if (a.batch <= 0) return hipSuccess;
   const int elem = dtype == MO_F64 ? 8 : 4;
-  if (!blocks_tangent_fits(a.n, a.k, a.m, a.rows, elem)) return hipErrorInvalidValue;  // (mo_qp_tangent_rhs_blocks refuses with its own message)
+  if (!blocks_tangent_fits(a.n, a.k, a.m, a.rows, elem, a.weights != nullptr)) return hipErrorInvalidValue;  // (mo_qp_tangent_rhs_blocks refuses with its own message)
   return dtype == MO_F64 ? launch_t<double>(a, num_cus, stream) : launch_t<float>(a, num_cus, stream);
 }
 

@@ -34,12 +34,16 @@ template <typename T> __device__ __forceinline__ T block_sum(T v, T* red) {
   return s;
 }
 
-template <typename T, bool kStaged>
+// kW (mo_linearize_blocks_weighted): row rho of a block counts with its weight, G += w J_a J_b, c += w J_a r, half_sq += w r^2, each as
+// (w J_a) * (.) in the order of the unweighted sums -- with w = 1 the same operations, with w a power of four the bits of the call on
+// (sqrt(w) J, sqrt(w) r).  A row whose weight is exactly 0 is skipped: its J values and r are never multiplied (they may be NaN).
+template <typename T, bool kStaged, bool kW = false>
 __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const BlocksArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ T red[kThreads / 64];
   T* sJ = reinterpret_cast<T*>(smem);
   T* sR = sJ + a.values;
+  T* sW = sR + a.rows;   // kW, staged: the weights
   const int tid = threadIdx.x;
   const int n = a.n, nn = n * n;
   for (long long p = blockIdx.x; p < a.batch; p += gridDim.x) {
@@ -47,9 +51,14 @@ __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const Blocks
     const T* gR = (const T*)a.r + p * a.r_stride;
     const T* Jv = gJ;
     const T* rv = gR;
+    const T* wv = kW ? (const T*)a.weights + p * a.weights_stride : nullptr;
     if (kStaged) {
       for (long long i = tid; i < a.values; i += kThreads) sJ[i] = gJ[i];
       for (int i = tid; i < a.rows; i += kThreads) sR[i] = gR[i];
+      if (kW) {
+        for (int i = tid; i < a.rows; i += kThreads) sW[i] = wv[i];
+        wv = sW;
+      }
       __syncthreads();
       Jv = sJ;
       rv = sR;
@@ -64,7 +73,17 @@ __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const Blocks
       for (int e = a.g_ptr[cell]; e < e1; ++e) {
         const int4 c = a.g_ent[e];
         T d = 0;
-        for (int q = 0; q < c.z; ++q) d += Jv[c.x + q] * Jv[c.y + q];
+        if (kW) {
+          for (int q = 0; q < c.z; ++q) {
+            const T w = wv[c.w + q];
+            if (w != (T)0) {
+              const T wa = w * Jv[c.x + q];
+              d += wa * Jv[c.y + q];
+            }
+          }
+        } else {
+          for (int q = 0; q < c.z; ++q) d += Jv[c.x + q] * Jv[c.y + q];
+        }
         s += d;
       }
       if (row == col && lam > (T)0) s += lam;  // nonlinear.cc:187-189, after the sum
@@ -77,14 +96,34 @@ __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const Blocks
       for (int e = a.c_ptr[i]; e < e1; ++e) {
         const int4 c = a.c_ent[e];
         T d = 0;
-        for (int q = 0; q < c.z; ++q) d += Jv[c.x + q] * rv[c.y + q];
+        if (kW) {
+          for (int q = 0; q < c.z; ++q) {
+            const T w = wv[c.y + q];
+            if (w != (T)0) {
+              const T wa = w * Jv[c.x + q];
+              d += wa * rv[c.y + q];
+            }
+          }
+        } else {
+          for (int q = 0; q < c.z; ++q) d += Jv[c.x + q] * rv[c.y + q];
+        }
         s += d;
       }
       cv[i] = s;
     }
     if (a.half_sq_out) {
       T sq = 0;
-      for (int i = tid; i < a.rows; i += kThreads) sq += rv[i] * rv[i];
+      if (kW) {
+        for (int i = tid; i < a.rows; i += kThreads) {
+          const T w = wv[i];
+          if (w != (T)0) {
+            const T wr = w * rv[i];
+            sq += wr * rv[i];
+          }
+        }
+      } else {
+        for (int i = tid; i < a.rows; i += kThreads) sq += rv[i] * rv[i];
+      }
       sq = block_sum(sq, red);
       if (tid == 0) ((T*)a.half_sq_out)[p] = (T)0.5 * sq;
     }
@@ -126,7 +165,10 @@ __global__ __launch_bounds__(kThreads) void blocks_jacobian_kernel(const BlocksA
 // residual row (b, q) and walks the block's P_b columns in order: t = J_b x_loc + r_b, w = J_b u_loc, into LDS; dr = -w.  Phase 2: consecutive
 // lanes own consecutive packed values (column-major inside a block: whole-line stores), dJ = -u_p t[q] - x_p w[q] plus (u_p x_p) J_b[q, q'] for
 // every other local column q' on the same variable.  Every product is rounded before it is added.
-template <typename T, bool kStaged>
+// kW (mo_qp_gradients_blocks_weighted): the weights go to LDS beside t and w; dJ = weight x (the value above), dr = -weight x w, both exactly 0
+// at a row whose weight is exactly 0, whatever its data hold; dweights[row] = -w[row] t[row] + sum over the pairs {p, p'} of local columns of
+// the row's block on one variable i of (u_i x_i) J[row, p] J[row, p'] (d_pair / d_plist of the layout; no list for almost every block).
+template <typename T, bool kStaged, bool kW = false>
 __global__ __launch_bounds__(kThreads) void blocks_grad_kernel(const BlockGradArgs a) {
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char smem[];
@@ -135,11 +177,12 @@ __global__ __launch_bounds__(kThreads) void blocks_grad_kernel(const BlockGradAr
   T* su = sx + a.n;
   T* st = su + a.n;
   T* sw = st + a.rows;
-  T* sJ = sw + a.rows;
+  T* sg = sw + a.rows;   // kW: the weights
+  T* sJ = sg + (kW ? a.rows : 0);
   T* sR = sJ + a.values;
   const int tid = threadIdx.x;
   const int n = a.n, rows = a.rows;
-  const bool need_rows = a.dJ || a.dr;
+  const bool need_rows = a.dJ || a.dr || (kW && a.dw);
   for (long long p = blockIdx.x; p < a.batch; p += gridDim.x) {
     const T* vp = (const T*)a.vars + p * a.vars_stride;
     const T* up = (const T*)a.u + p * a.u_stride;
@@ -155,6 +198,8 @@ __global__ __launch_bounds__(kThreads) void blocks_grad_kernel(const BlockGradAr
     __syncthreads();
     if (need_rows) {
       T* dr = a.dr ? (T*)a.dr + p * a.dr_stride : nullptr;
+      const T* wv = kW ? (const T*)a.weights + p * a.weights_stride : nullptr;
+      T* dw = (kW && a.dw) ? (T*)a.dw + p * a.dw_stride : nullptr;
       for (int row = tid; row < rows; row += kThreads) {
         const int4 ri = a.d_row[row];
         T t = 0, w = 0;
@@ -167,7 +212,30 @@ __global__ __launch_bounds__(kThreads) void blocks_grad_kernel(const BlockGradAr
         }
         st[row] = t + rv[row];
         sw[row] = w;
-        if (dr) dr[row] = -w;
+        if (kW) {
+          const T g = wv[row];
+          sg[row] = g;
+          if (dr) {
+            const T gw = g * w;
+            dr[row] = g == (T)0 ? (T)0 : -gw;
+          }
+          if (dw) {
+            const T wt = w * st[row];
+            T s = -wt;
+            const int pl = a.d_pair[row];
+            if (pl >= 0) {  // a repeated variable inside the block: the derivative of the pair that landed once
+              const int cnt = a.d_plist[pl];
+              for (int d = 0; d < cnt; ++d) {
+                const int ca = a.d_plist[pl + 1 + 3 * d], cb = a.d_plist[pl + 2 + 3 * d], gi = a.d_plist[pl + 3 + 3 * d];
+                const T ux = su[gi] * sx[gi];
+                const T jj = Jv[ri.x + ca] * Jv[ri.x + cb];
+                const T pd = ux * jj;
+                s += pd;
+              }
+            }
+            dw[row] = s;
+          }
+        } else if (dr) dr[row] = -w;
       }
       __syncthreads();
       if (a.dJ) {
@@ -184,6 +252,11 @@ __global__ __launch_bounds__(kThreads) void blocks_grad_kernel(const BlockGradAr
               const T pd = ux * Jv[a.d_dup[vi.w + d] + vi.z];
               s += pd;
             }
+          }
+          if (kW) {
+            const T g = sg[vi.x];
+            const T gs = g * s;
+            s = g == (T)0 ? (T)0 : gs;
           }
           dJ[e] = s;
         }
@@ -231,6 +304,15 @@ __global__ __launch_bounds__(kThreads) void blocks_eq_grad_kernel(const BlockGra
 }
 
 template <typename T> hipError_t launch_linearize_t(const BlocksArgs& a, int num_cus, hipStream_t stream) {
+  if (a.weights) {  // the weights are staged with the values: rows more elements
+    const size_t stage = (size_t)(a.values + 2 * (long long)a.rows) * sizeof(T);
+    if (stage <= kStageBudget) {
+      hipLaunchKernelGGL((blocks_linearize_kernel<T, true, true>), dim3(grid_for(a.batch, num_cus, stage)), dim3(kThreads), stage, stream, a);
+    } else {
+      hipLaunchKernelGGL((blocks_linearize_kernel<T, false, true>), dim3(grid_for(a.batch, num_cus, 0)), dim3(kThreads), 0, stream, a);
+    }
+    return hipGetLastError();
+  }
   const size_t stage = (size_t)(a.values + a.rows) * sizeof(T);
   if (stage <= kStageBudget) {
     hipLaunchKernelGGL((blocks_linearize_kernel<T, true>), dim3(grid_for(a.batch, num_cus, stage)), dim3(kThreads), stage, stream, a);
@@ -241,6 +323,16 @@ template <typename T> hipError_t launch_linearize_t(const BlocksArgs& a, int num
 }
 
 template <typename T> hipError_t launch_grad_t(const BlockGradArgs& a, int num_cus, hipStream_t stream) {
+  if (a.weights) {
+    const size_t vectors = (size_t)(2 * a.n + 3 * a.rows) * sizeof(T);
+    const size_t stage = (size_t)(a.values + a.rows) * sizeof(T);
+    if (stage <= kStageBudget && vectors + stage <= kGradLds) {
+      hipLaunchKernelGGL((blocks_grad_kernel<T, true, true>), dim3(grid_for(a.batch, num_cus, vectors + stage)), dim3(kThreads), vectors + stage, stream, a);
+    } else {
+      hipLaunchKernelGGL((blocks_grad_kernel<T, false, true>), dim3(grid_for(a.batch, num_cus, vectors)), dim3(kThreads), vectors, stream, a);
+    }
+    return hipGetLastError();
+  }
   const size_t vectors = (size_t)(2 * a.n + 2 * a.rows) * sizeof(T);
   const size_t stage = (size_t)(a.values + a.rows) * sizeof(T);
   if (stage <= kStageBudget && vectors + stage <= kGradLds) {
@@ -266,11 +358,13 @@ hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, h
   return hipGetLastError();
 }
 
-bool blocks_grad_fits(int n, int rows, int elem_size) { return (size_t)(2 * (long long)n + 2 * (long long)rows) * elem_size <= kGradLds; }
+bool blocks_grad_fits(int n, int rows, int elem_size, bool weighted) {
+  return (size_t)(2 * (long long)n + (weighted ? 3 : 2) * (long long)rows) * elem_size <= kGradLds;
+}
 
 hipError_t launch_blocks_grad(const BlockGradArgs& a, int dtype, int num_cus, hipStream_t stream) {
   if (a.batch <= 0) return hipSuccess;
-  if (!blocks_grad_fits(a.n, a.rows, dtype == MO_F64 ? 8 : 4)) return hipErrorInvalidValue;  // (mo_qp_gradients_blocks refuses with its own message)
+  if (!blocks_grad_fits(a.n, a.rows, dtype == MO_F64 ? 8 : 4, a.weights != nullptr)) return hipErrorInvalidValue;  // (mo_qp_gradients_blocks refuses with its own message)
   return dtype == MO_F64 ? launch_grad_t<double>(a, num_cus, stream) : launch_grad_t<float>(a, num_cus, stream);
 }
 

@@ -8,6 +8,8 @@
     qp_tangent_rhs  mo_qp_tangent_rhs  forward mode: rho = F_theta thetadot from the state v and a direction in the QP's data
     qp_jvp          qp_tangent_rhs + kkt_solve: the directional derivative vdot of the whole solution [x | s | y | z]
     qp_tangent_rhs_blocks, qp_jvp_blocks    the same for residual-block input: rho from the PACKED tangents of the blocks
+    qp_gradients_blocks_weighted, qp_tangent_rhs_blocks_weighted, qp_jvp_blocks_weighted    the block calls for a cost with one weight per
+                    stacked residual row, 1/2 sum_i w_i (J x + r)_i^2: the weights' own gradient and tangent beside the blocks'
     solve_qp        the user-facing call: forward = Solve (the kernels of qp.QPInteriorPointSolver, fused where the shape allows),
                     backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient
                     (+ ONE batch-reduced launch for the inputs given once for the batch, leading dimension 1),
@@ -58,6 +60,10 @@ BLOCK_TANGENTS = tuple(_BLOCK)
 BLOCK_GRADIENTS = BLOCK_TANGENTS[:5]    # (the constraint members of a block problem go through the dense entry points)
 _DENSE_J, _DENSE_EQ = GRADIENTS[2:5], GRADIENTS[5:7]    # the J-level cost members (G alone belongs to the other level); the equality members
 _BLOCK_COST, _BLOCK_EQ, _CONS = BLOCK_TANGENTS[:3], BLOCK_TANGENTS[3:5], BLOCK_TANGENTS[5:]
+# the weighted block cost (mo_block_weighted_grads / mo_block_weighted_tangents): the members of _BLOCK and, behind them, the per-row weights
+_WEIGHTED = {**_BLOCK, "weights": ("dweights", "dweights_stride", None, lambda s: (s.layout.rows,))}
+WEIGHTED_TANGENTS = tuple(_WEIGHTED)
+_WEIGHTED_COST = _BLOCK_COST + WEIGHTED_TANGENTS[-1:]
 
 
 class _Blocks(NamedTuple):
@@ -557,6 +563,72 @@ def qp_jvp_blocks(problem: BatchedQP, layout: ResidualLayout, J_blocks: torch.Te
     return kkt_solve(problem, vars, rho, transpose=False)
 
 
+def _take_weights(s: _Blocks, weights, B: int, keep: list):
+    return _take(weights, "weights", _WEIGHTED["weights"][3](s), B, s.dtype, s.device, keep)
+
+
+def qp_gradients_blocks_weighted(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, weights: torch.Tensor, vars: torch.Tensor,
+                                 u: torch.Tensor, k: int = 0, m: int = 0,
+                                 want: Iterable[str] = ("J_blocks", "r", "lam", "weights")) -> Dict[str, torch.Tensor]:
+    """mo_qp_gradients_blocks_weighted: qp_gradients_blocks for the cost 1/2 sum_i w_i (J x + r)_i^2, weights [B or 1, rows] (1: one
+    instance, read with stride 0).  Returns the ones named in `want`: "J_blocks" [B, values] and "r" [B, rows] (exactly 0 at a row whose
+    weight is exactly 0, whatever its data hold), "lam" [B], "weights" [B, rows].  J_blocks [1, values] with weights [B, rows] reads the one
+    instance in place; a `want` without "J_blocks" forms no [B, values] tensor."""
+    want = tuple(want)
+    _check_names(want, "gradient", _WEIGHTED_COST)
+    k, m = int(k), int(m)
+    B = _check_state_pair(vars, u, "u", layout.n + 2 * m + k, layout)
+    blocks = _Blocks(layout, None, k, m)
+    keep = []
+    J_ptr, J_stride, r_ptr, r_stride = _take_cost_blocks(blocks, J_blocks, r, B, keep)
+    w_ptr, w_stride = _take_weights(blocks, weights, B, keep)
+    out, g = _outputs(L.BlockWeightedGrads(), _WEIGHTED, blocks, want, B)
+    plan = _plan_of(layout.n, k, m, 0, layout.dtype, layout.device, B)
+    L.check(L.lib().mo_qp_gradients_blocks_weighted(plan, layout.h, J_ptr, J_stride, r_ptr, r_stride, w_ptr, w_stride, B, _ptr(vars),
+                                                    int(vars.shape[1]), _ptr(u), int(u.shape[1]), C.byref(g), _stream()))
+    return out
+
+
+def qp_tangent_rhs_blocks_weighted(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, weights: torch.Tensor, vars: torch.Tensor,
+                                   tangents: Dict[str, torch.Tensor], k: int = 0, m: int = 0, eq_layout: Optional[ResidualLayout] = None,
+                                   cons_var: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mo_qp_tangent_rhs_blocks_weighted: qp_tangent_rhs_blocks for the weighted cost; `tangents` may also hold "weights" [B or 1, rows], the
+    direction in the weights.  J_blocks, r and weights [B or 1, ...] are always given."""
+    n, k, m = layout.n, _eq_rows(layout, eq_layout, k), int(m)
+    V = n + 2 * m + k
+    B = _check_state(vars, "vars", V, layout)
+    no_rows = (_BLOCK_EQ if k == 0 or eq_layout is None else ()) + (_CONS if m == 0 else ())
+    _check_names(tangents, "tangent", WEIGHTED_TANGENTS, no_rows)
+    blocks = _Blocks(layout, eq_layout, k, m)
+    keep = []
+    J_ptr, J_stride, r_ptr, r_stride = _take_cost_blocks(blocks, J_blocks, r, B, keep)
+    w_ptr, w_stride = _take_weights(blocks, weights, B, keep)
+    t = L.BlockWeightedTangents()
+    _inputs(t, _WEIGHTED, blocks, tangents, B, keep)
+    cv_ptr, cv_stride = None, 0
+    if m and cons_var is not None:
+        cv_ptr, cv_stride = _take(cons_var, "cons_var", (m,), B, torch.int32, layout.device, keep)
+    elif "cons_a" in tangents:
+        raise ValueError("tangent 'cons_a' needs cons_var")
+    rho = torch.empty_like(vars)
+    plan = _plan_of(n, k, m, 0, layout.dtype, layout.device, B)
+    L.check(L.lib().mo_qp_tangent_rhs_blocks_weighted(plan, layout.h, J_ptr, J_stride, r_ptr, r_stride, w_ptr, w_stride,
+                                                      None if eq_layout is None else eq_layout.h, cv_ptr, cv_stride, B, _ptr(vars), V,
+                                                      C.byref(t), _ptr(rho), V, _stream()))
+    return rho
+
+
+def qp_jvp_blocks_weighted(problem: BatchedQP, layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, weights: torch.Tensor,
+                           vars: torch.Tensor, tangents: Dict[str, torch.Tensor], eq_layout: Optional[ResidualLayout] = None):
+    """qp_jvp_blocks for the weighted cost: one weighted tangent launch and one KKT solve on `problem`, the (G, c) problem
+    linearize_blocks(..., weights=weights) / jacobian_blocks built.  Returns (vdot, status)."""
+    if problem.n != layout.n or (eq_layout is not None and eq_layout.rows != problem.k):
+        raise ValueError("problem does not belong to these layouts (n / k differ)")
+    rho = qp_tangent_rhs_blocks_weighted(layout, J_blocks, r, weights, vars, tangents, k=problem.k, m=problem.m, eq_layout=eq_layout,
+                                         cons_var=problem.cons_var)
+    return kkt_solve(problem, vars, rho, transpose=False)
+
+
 class QPSolveBlocksFunction(torch.autograd.Function):
     """QPSolveFunction for residual-block input.  forward(J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, cons_var, layout, eq_layout,
     params) -> (v, status): linearize_blocks gives (G, c), jacobian_blocks gives A_eq (b_eq = r_eq), mo_qp_solve runs on the (G, c) problem --
@@ -632,6 +704,78 @@ class QPSolveBlocksFunction(torch.autograd.Function):
         return _jvp_result(ctx, *qp_jvp_blocks(ctx.problem, ctx.layout, ctx.J_blocks, ctx.r, ctx.v, tangents, eq_layout=ctx.eq_layout))
 
 
+class QPSolveWeightedBlocksFunction(torch.autograd.Function):
+    """QPSolveBlocksFunction for the weighted cost 1/2 sum_i w_i (J x + r)_i^2 + 1/2 lam |x|^2.  forward(J_blocks, r, lam, J_eq_blocks, r_eq,
+    cons_a, cons_b, weights, cons_var, layout, eq_layout, params) -> (v, status); weights [B or 1, layout.rows].  Any input given once is read
+    with stride 0 in the forward: J_blocks [1, values] with weights [B, rows] forms G per problem from the ONE instance of J_blocks.  The
+    gradients of the cost members -- J_blocks, r, lam, weights -- come from ONE mo_qp_gradients_blocks_weighted launch per problem; those of
+    inputs given once are summed over the batch afterwards ([1, ...]): the batch-reduced launch (mo_qp_gradients_blocks_shared) knows no
+    weights.  A backward that does not ask for J_blocks' gradient forms no [B, values] tensor.  The equality and constraint members go the
+    ways of QPSolveBlocksFunction; so do lam's rule (its gradient and tangent count only where lam > 0) and the zero gradients and tangents
+    of problems whose forward, adjoint or tangent status is not OK."""
+
+    NAMES = WEIGHTED_TANGENTS
+
+    @staticmethod
+    def forward(ctx, J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, weights, cons_var, layout, eq_layout, params):
+        det = lambda t: None if t is None else t.detach()
+        J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, weights = (det(t) for t in (J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b,
+                                                                                          weights))
+        inputs = (J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, weights)
+        B = max(int(t.shape[0]) for t in inputs if t is not None)
+        once = lambda t: int(t.shape[0]) == 1 and B > 1
+        ctx.shared = frozenset(nm for nm, t in zip(QPSolveWeightedBlocksFunction.NAMES, inputs) if t is not None and once(t))
+        if once(J_blocks) and once(lam) and once(weights):   # one G for the batch, as QPSolveBlocksFunction
+            G, _, _ = linearize_blocks(layout, J_blocks, r[:1], lam_vec=lam, weights=weights)
+            _, c, _ = linearize_blocks(layout, J_blocks, r, lam_vec=lam, want_G=False, weights=weights)
+        else:
+            G, c, _ = linearize_blocks(layout, J_blocks, r, lam_vec=lam, batch=B, weights=weights)
+        k = 0 if eq_layout is None else eq_layout.rows
+        m = 0 if cons_a is None else int(cons_a.shape[1])
+        A_eq = None
+        if eq_layout is not None:
+            A_eq, _ = jacobian_blocks(eq_layout, J_eq_blocks, r_eq[:1] if once(J_eq_blocks) else r_eq)
+        problem = BatchedQP(n=layout.n, k=k, m=m, G=G, c=c, A_eq=A_eq, b_eq=r_eq if k else None, cons_var=cons_var, cons_a=cons_a, cons_b=cons_b)
+        ctx.layout, ctx.eq_layout, ctx.J_blocks, ctx.r, ctx.lam, ctx.weights = layout, eq_layout, J_blocks, r, lam, weights
+        return _solve_forward(ctx, problem, B, params)
+
+    @staticmethod
+    def backward(ctx, g, _g_status):
+        problem, v, u, ok = _adjoint(ctx, g)
+        names = QPSolveWeightedBlocksFunction.NAMES
+        want = [nm for nm, nd in zip(names, ctx.needs_input_grad[:8]) if nd]
+        sel = lambda group, among: [nm for nm in group if nm in among]
+        cost = sel(want, _WEIGHTED_COST)                     # per problem always: shared ones are summed by _per_problem
+        each, summed = _partition(sel(want, _BLOCK_EQ + _CONS), ctx.shared, "r", "J_blocks")
+        grads: Dict[str, torch.Tensor] = {}
+        if cost:
+            grads.update(qp_gradients_blocks_weighted(ctx.layout, ctx.J_blocks, ctx.r, ctx.weights, v, u, k=problem.k, m=problem.m, want=cost))
+        eq, cons = sel(each, _BLOCK_EQ), sel(each, _CONS)
+        if eq:
+            grads.update(qp_gradients_eq_blocks(ctx.eq_layout, v, u, m=problem.m, want=eq))
+        if cons:
+            grads.update(qp_gradients(problem, v, u, cons))
+        grads = _per_problem(grads, ok, ctx.shared)
+        eq, cons = sel(summed, _BLOCK_EQ), sel(summed, _CONS)
+        if eq:
+            grads.update(qp_gradients_blocks_shared(ctx.layout, None, None, v, u, k=problem.k, m=problem.m, want=eq, eq_layout=ctx.eq_layout,
+                                                    status_fwd=ctx.status, status_adj=ctx.adjoint_status))
+        if cons:
+            grads.update(qp_gradients_shared(problem, v, u, cons, status_fwd=ctx.status, status_adj=ctx.adjoint_status))
+        if "lam" in grads:
+            grads["lam"] = _where_lam_added(ctx.lam, grads["lam"])
+        return (*[grads.get(nm) for nm in names], None, None, None, None)
+
+    @staticmethod
+    def jvp(ctx, dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b, dweights, _dcons_var, _dlayout, _deq_layout, _dparams):
+        """torch.autograd.forward_ad: ONE mo_qp_tangent_rhs_blocks_weighted launch + ONE KKT solve; a dual `weights` is the tangent wdot."""
+        if dlam is not None:
+            dlam = _where_lam_added(ctx.lam, dlam)
+        tangents = _given(WEIGHTED_TANGENTS, (dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b, dweights))
+        return _jvp_result(ctx, *qp_jvp_blocks_weighted(ctx.problem, ctx.layout, ctx.J_blocks, ctx.r, ctx.weights, ctx.v, tangents,
+                                                        eq_layout=ctx.eq_layout))
+
+
 def adjoint_status(t: torch.Tensor) -> Optional[torch.Tensor]:
     """The [B] status words of the adjoint solve behind a tensor solve_qp returned (None before the first backward)."""
     seen, todo = set(), [t.grad_fn]
@@ -689,7 +833,7 @@ def _result(v: torch.Tensor, status: torch.Tensor, n: int, m: int, k: int, retur
 
 def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons_var=None, cons_a=None, cons_b=None,
              params: Optional[Params] = None, return_all: bool = False, return_status: bool = False, layout: Optional[ResidualLayout] = None,
-             J_blocks=None, eq_layout: Optional[ResidualLayout] = None, J_eq_blocks=None, r_eq=None):
+             J_blocks=None, eq_layout: Optional[ResidualLayout] = None, J_eq_blocks=None, r_eq=None, weights=None):
     """Solve a batch of QPs   min 1/2 x^T G x + c^T x   s.t.  A_eq x + b_eq = 0,  cons_a[i] x[cons_var[i]] + cons_b[i] >= 0   on the GPU and
     keep the result on the autograd graph.  Give EITHER (G [B, n, n] SYMMETRIC, c [B, n]) OR the least-squares form (J [B, m_r, n], r [B, m_r],
     lam: float or [B] tensor; G = J^T J + lam I, c = J^T r, lam added where > 0).  A_eq [B, k, n] (rows = constraints), b_eq [B, k];
@@ -703,6 +847,13 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     Jacobians, r [B, layout.rows], lam as above; equalities, if any, as eq_layout, J_eq_blocks [B, eq_layout.values], r_eq [B, k] (A_eq = the
     stacked UpdateJacobian, b_eq = r_eq) instead of A_eq / b_eq.  Its gradients arrive in the packed layouts and are computed from the
     blocks alone (QPSolveBlocksFunction).  The three forms are mutually exclusive.
+    weights [B or 1, layout.rows] (residual-block form only): one weight per stacked residual row, the cost 1/2 sum_i w_i (J x + r)_i^2 +
+    1/2 lam |x|^2 -- confidences per measurement, or a 0 / 1 mask: a row whose weight is exactly 0 contributes exactly nothing, its J values
+    and r may be NaN, and its entries of J_blocks.grad and r.grad are exactly 0.  weights.grad arrives as [B, rows] ([1, rows] for a weight
+    given once); forward_ad takes a dual `weights`.  Under weights every input given once is still read with stride 0, but the gradients of
+    J_blocks, r, lam and weights given once are formed per problem and summed afterwards: the batch-reduced launch
+    (mo_qp_gradients_blocks_shared) does not know weights (QPSolveWeightedBlocksFunction).  Without `weights` the call is exactly the
+    unweighted one.
     Returns x [B, n] (return_all: x, s, y, z), and with return_status also the [B] int32 forward status (MO_STATUS_*).
 
     Gradients: every floating-point input that requires_grad receives one, nothing else is computed.  G's gradient is the one with respect
@@ -711,10 +862,11 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     at the returned point: it is as accurate as the solve (termination_kkt_tol), and at an active inequality the slack sits at the
     interior-point floor, so K is ill-conditioned there by construction."""
     params = params if params is not None else Params()
-    if layout is not None or J_blocks is not None or eq_layout is not None or J_eq_blocks is not None or r_eq is not None:
+    if layout is not None or J_blocks is not None or eq_layout is not None or J_eq_blocks is not None or r_eq is not None or weights is not None:
         if G is not None or c is not None or J is not None or A_eq is not None or b_eq is not None:
             raise ValueError("layout= (residual-block input) excludes G, c, J, A_eq and b_eq: the three input forms are mutually exclusive")
-        return _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status)
+        return _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status,
+                                weights)
     if (J is None) == (G is None):
         raise ValueError("give either (G, c) or (J, r)")
     ref = J if J is not None else G
@@ -733,15 +885,21 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     return _result(v, status, int(ref.shape[2]), m, k, return_all, return_status)
 
 
-def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status):
+def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status,
+                     weights=None):
     if layout is None or J_blocks is None or r is None:
         raise ValueError("the residual-block form needs layout, J_blocks and r")
     if (eq_layout is None) != (J_eq_blocks is None) or (eq_layout is None) != (r_eq is None):
         raise ValueError("eq_layout, J_eq_blocks and r_eq come together")
     k = _eq_rows(layout, eq_layout, 0)
-    _, (J_t, r_t, J_eq_t, r_eq_t), lam_t, cons = _pass_through((J_blocks, r, J_eq_blocks, r_eq), lam, cons_var, cons_a, cons_b)
+    _, (J_t, r_t, J_eq_t, r_eq_t, w_t), lam_t, cons = _pass_through((J_blocks, r, J_eq_blocks, r_eq, weights), lam, cons_var, cons_a, cons_b)
     if not isinstance(lam_t, torch.Tensor):
         lam_t = torch.full((1,), float(lam), dtype=layout.dtype, device=layout.device)
-    v, status = QPSolveBlocksFunction.apply(J_t, r_t, lam_t, J_eq_t, r_eq_t, *cons, layout, eq_layout, params)
+    if w_t is not None:
+        cons_a_t, cons_b_t, cons_var_t = cons
+        v, status = QPSolveWeightedBlocksFunction.apply(J_t, r_t, lam_t, J_eq_t, r_eq_t, cons_a_t, cons_b_t, w_t, cons_var_t, layout, eq_layout,
+                                                        params)
+    else:
+        v, status = QPSolveBlocksFunction.apply(J_t, r_t, lam_t, J_eq_t, r_eq_t, *cons, layout, eq_layout, params)
     m = 0 if cons_a is None else int(cons_a.shape[1])
     return _result(v, status, layout.n, m, k, return_all, return_status)

@@ -457,12 +457,21 @@ def _check_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tenso
 
 
 def linearize_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, lam: float = 0.0, lam_vec: Optional[torch.Tensor] = None,
-                     want_G: bool = True, batch: Optional[int] = None):
+                     want_G: bool = True, batch: Optional[int] = None, weights: Optional[torch.Tensor] = None):
     """Cost part of LinearizeAndFillQP (nonlinear.cc:182-189) from packed residual blocks: sum_b UpdateHessian (residual.hpp:186-226) +
     lambda I.  Returns (G [B,n,n] col-major lower, strict upper 0; c [B,n]; sum_b 0.5 |r_b|^2 [B]).  J_blocks / r / lam_vec with a leading
     dimension of 1 are read with stride 0; B is the largest leading dimension (or `batch`, if that is larger).  want_G=False: G is not
-    formed (returned as None); c has the bits of the full call."""
+    formed (returned as None); c has the bits of the full call.  weights [B or 1, rows]: one weight per stacked residual row
+    (mo_linearize_blocks_weighted): G = sum_b J_b^T W_b J_b by the same pair rule, c = sum_b J_b^T W_b r_b, the third result 0.5 sum w r^2; a
+    row whose weight is exactly 0 is never read into the arithmetic (its J values and r may be NaN)."""
     B, js, rs = _check_blocks(layout, J_blocks, r)
+    ws = 0
+    if weights is not None:
+        if (weights.dim() != 2 or int(weights.shape[1]) != layout.rows or not weights.is_contiguous() or weights.dtype != layout.dtype
+                or weights.device != layout.device):
+            raise ValueError(f"weights: expected a contiguous [B or 1, {layout.rows}] {layout.dtype} tensor on {layout.device}")
+        ws = 0 if weights.shape[0] == 1 else layout.rows
+        B = max(B, int(weights.shape[0]))
     n = layout.n
     ls = 0
     if lam_vec is not None:
@@ -472,12 +481,16 @@ def linearize_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Te
         B = max(B, int(lam_vec.shape[0]))
     if batch is not None:
         B = max(B, int(batch))
-    for t in (J_blocks, r, lam_vec):
+    for t in (J_blocks, r, lam_vec, weights):
         if t is not None and int(t.shape[0]) not in (1, B):
             raise ValueError(f"leading dimension {int(t.shape[0])}: expected {B} or 1")
     G = torch.empty(B, n, n, dtype=layout.dtype, device=layout.device) if want_G else None
     c = torch.empty(B, n, dtype=layout.dtype, device=layout.device)
     f = torch.empty(B, dtype=layout.dtype, device=layout.device)
+    if weights is not None:
+        L.check(L.lib().mo_linearize_blocks_weighted(layout._plan, layout.h, _ptr(J_blocks), js, _ptr(r), rs, _ptr(weights), ws, float(lam),
+                                                     _ptr(lam_vec), ls, B, _ptr(G), n * n, n, _ptr(c), n, _ptr(f), _stream()))
+        return G, c, f
     L.check(L.lib().mo_linearize_blocks(layout._plan, layout.h, _ptr(J_blocks), js, _ptr(r), rs, float(lam), _ptr(lam_vec), ls, B,
                                         _ptr(G), n * n, n, _ptr(c), n, _ptr(f), _stream()))
     return G, c, f

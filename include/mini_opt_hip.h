@@ -706,6 +706,54 @@ int mo_qp_tangent_rhs_blocks_weighted(mo_plan* plan, const mo_residual_layout* c
                                       const void* vars, int64_t vars_stride, const mo_block_weighted_tangents* t, void* rho, int64_t rho_stride,
                                       void* stream);
 
+/* mo_qp_gradients_blocks_weighted_shared: the outputs of mo_qp_gradients_blocks_weighted SUMMED over the batch, for ONE instance of J_blocks
+ * under weights and residuals per problem (weights_stride, r_stride != 0) or given once (stride 0).  Stacked row rho lies in block b with
+ * local columns p on the variables i_p = idx_b[p]; the sums run over the problems k that count (every given status word is
+ * MO_STATUS_OK); x, u are the x parts of vars, u.  Per problem
+ *   t_rho = sum_p J[rho, p] x[i_p] + r_rho        s_rho = sum_p J[rho, p] u[i_p]
+ *   a_rho = w_rho t_rho,  c_rho = w_rho s_rho     both exactly 0, formed without a multiplication, where w_rho == 0
+ * and
+ *   dJ_blocks[rho, p] = -sum_k (u[i_p] a_rho + x[i_p] c_rho) + (sum over the OTHER local columns q' on p's variable of J[rho, q']) sum_k w_rho u[i_p] x[i_p]
+ *   dr[rho]           = -sum_k c_rho                                  (only with r_stride == 0)
+ *   dweights[rho]     = -sum_k s_rho t_rho + sum over the pairs {p, p'} of the row's block on ONE variable i of J[rho, p] J[rho, p'] sum_k u_i x_i     (only with weights_stride == 0)
+ *   dlambda           = -sum_k sum_i u_i x_i                          (ONE value: the caller masks it where lambda <= 0)
+ * The second terms of dJ_blocks and dweights exist only for layouts whose partner / pair lists are non-empty; the partner sums and pair
+ * products of J leave the batch sum because J is one instance.  The weights do not: sum_k w_rho u x^T is another matrix for every row, so
+ * nothing factors through the moments of mo_qp_gradients_blocks_shared, and every problem's t and s are formed on chip and consumed at the
+ * packed positions at once (values multiply-adds each; no rows x n product, no [batch][values] gradient).
+ * ZERO WEIGHTS as in the sibling, per problem: a row with w_rho == 0 in problem k may hold NaN in that problem's r and contributes exactly
+ * nothing to dJ_blocks and dr; dweights at a row is computed from whatever the data hold.  A problem that does not count contributes
+ * exactly nothing, whatever its rows of vars / u / r / weights hold.
+ * The plan is that of the (G, c) solve.  The equality and constraint members are not part of this call: they go through
+ * mo_qp_gradients_blocks_shared / mo_qp_gradients_shared, which read no weights.
+ * Arguments are judged before the plan is looked at.  MO_ERR_INVALID_ARGUMENT, with nothing written: NULL cost_layout / out / J_blocks /
+ * r / weights; dr with r_stride != 0; dweights with weights_stride != 0; a workspace smaller than the query reports for the same
+ * arguments, or not 16-byte aligned.  MO_ERR_DIMENSION: the layout's n differs from the plan's; vars_stride / u_stride < V.
+ * MO_ERR_UNSUPPORTED, before any launch: ONE staged problem -- (2 n + 2 sum R_b) values (x, u_x, r, w), and sum R_b values more when
+ * dweights is asked for (s t) -- exceeds 64 KiB less the 64 bytes of the kernel's flags.  The kernel stages the largest of 16, 8, 4, 2
+ * problems whose rows fit 48 KiB, else 1.  J_blocks is not kept in LDS: it is read in place (one instance, the same addresses for every
+ * problem), so `values` has no LDS rule.  batch == 0 writes zeros.
+ * The chunks are those of mo_qp_gradients_shared (a function of batch and CU count alone).  Partial kernel: a workgroup owns a chunk and
+ * 2048 packed values in registers; t, s per (problem, row), then every value's sum in problem order, each product rounded before it is
+ * added; a masked problem is skipped whole.  The finish sums the chunk partials in chunk order in double, forms every output in double
+ * through the layout's schedules and rounds once.  One owner per workspace and output element: no atomics, no memset, the same bits on
+ * every launch of one device, and each member alone gets the bits it gets beside the others.  No allocation and no synchronisation on
+ * the launch path: at most three kernels on `stream`.  The workspace's contents are scratch. */
+typedef struct {            /* ONE instance per member; NULL = neither computed nor written */
+  void* dJ_blocks;          /* cost_layout values, the packing of J_blocks */
+  void* dr;                 /* cost_layout rows; only with r_stride == 0 */
+  void* dlambda;            /* 1 */
+  void* dweights;           /* cost_layout rows; only with weights_stride == 0 */
+} mo_block_weighted_shared_grads;
+int mo_qp_gradients_blocks_weighted_shared_workspace(const mo_plan* plan, const mo_residual_layout* cost_layout, int64_t r_stride,
+                                                     int64_t weights_stride, int64_t batch, const mo_block_weighted_shared_grads* out,
+                                                     int64_t* bytes);
+int mo_qp_gradients_blocks_weighted_shared(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks /* one instance */,
+                                           const void* r, int64_t r_stride, const void* weights, int64_t weights_stride, int64_t batch,
+                                           const void* vars, int64_t vars_stride, const void* u, int64_t u_stride,
+                                           const int32_t* status_fwd, const int32_t* status_adj,
+                                           const mo_block_weighted_shared_grads* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

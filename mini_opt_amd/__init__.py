@@ -12,7 +12,7 @@ _DIFF_EXPORTS = ("solve_qp", "kkt_solve", "qp_gradients", "qp_gradients_shared",
                  "qp_gradients_blocks_shared", "QPSolveFunction",
                  "QPSolveBlocksFunction", "adjoint_status", "qp_tangent_rhs", "qp_jvp", "tangent_status",
                  "qp_tangent_rhs_blocks", "qp_jvp_blocks", "qp_gradients_blocks_weighted", "qp_tangent_rhs_blocks_weighted",
-                 "qp_jvp_blocks_weighted", "QPSolveWeightedBlocksFunction")
+                 "qp_jvp_blocks_weighted", "QPSolveWeightedBlocksFunction", "qp_gradients_blocks_weighted_shared")
 
 
 def __getattr__(name):  # the differentiable front end needs torch: imported on first use, like qp

@@ -38,7 +38,8 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_qp_gradients_shared_workspace", "mo_qp_gradients_shared",
            "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_gradients_blocks_shared_workspace", "mo_qp_gradients_blocks_shared",
            "mo_qp_tangent_rhs", "mo_qp_tangent_rhs_blocks",
-           "mo_linearize_blocks_weighted", "mo_qp_gradients_blocks_weighted", "mo_qp_tangent_rhs_blocks_weighted"]
+           "mo_linearize_blocks_weighted", "mo_qp_gradients_blocks_weighted", "mo_qp_tangent_rhs_blocks_weighted",
+           "mo_qp_gradients_blocks_weighted_shared_workspace", "mo_qp_gradients_blocks_weighted_shared"]
 
 
 class PlanDesc(C.Structure):
@@ -141,6 +142,11 @@ class BlockWeightedGrads(C.Structure):
     _fields_ = BlockGrads._fields_ + [("dweights", C.c_void_p), ("dweights_stride", C.c_int64)]
 
 
+class BlockWeightedSharedGrads(C.Structure):
+    """mo_block_weighted_shared_grads: optional device outputs of mo_qp_gradients_blocks_weighted_shared, ONE instance per member."""
+    _fields_ = [("dJ_blocks", C.c_void_p), ("dr", C.c_void_p), ("dlambda", C.c_void_p), ("dweights", C.c_void_p)]
+
+
 class BlockWeightedTangents(C.Structure):
     """mo_block_weighted_tangents: mo_block_tangents and the tangent of the per-row weights (mo_qp_tangent_rhs_blocks_weighted)."""
     _fields_ = BlockTangents._fields_ + [("dweights", C.c_void_p), ("dweights_stride", C.c_int64)]
@@ -161,7 +167,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "tools", "isa_lint.py"))   # the build lints its own listings: a changed lint re-runs it
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
-        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (eighteen units, the longest 5.7 min)
+        jobs = max(2, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)))   # (nineteen units, the longest 5.7 min)
         subprocess.check_call(["make", "-C", CSRC, f"-j{jobs}"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
@@ -234,6 +240,9 @@ def lib() -> C.CDLL:
     L.mo_qp_gradients_blocks_weighted.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.POINTER(BlockWeightedGrads), vp]
     L.mo_qp_tangent_rhs_blocks_weighted.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64,
                                                     C.POINTER(BlockWeightedTangents), vp, i64, vp]
+    L.mo_qp_gradients_blocks_weighted_shared_workspace.argtypes = [vp, vp, i64, i64, i64, C.POINTER(BlockWeightedSharedGrads), C.POINTER(i64)]
+    L.mo_qp_gradients_blocks_weighted_shared.argtypes = [vp, vp, vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, vp, vp,
+                                                         C.POINTER(BlockWeightedSharedGrads), vp, i64, vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what the header declares
     _lib = L

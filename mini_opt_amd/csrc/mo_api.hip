@@ -63,6 +63,7 @@ struct mo_residual_layout {
   const int* d_pair; const int* d_plist;
   // the forward-mode schedule of an equality layout (mo_qp_tangent_rhs_blocks, mo::BlockTangentArgs): c_ptr / c_ent filtered by winners
   const int* w_ptr; const int4* w_ent;
+  int has_dup;   // some block names a variable twice: d_dup and d_plist are non-empty (mo_qp_gradients_blocks_weighted_shared)
 };
 
 namespace {
@@ -1288,6 +1289,7 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
   L->d_dup = (const int*)dst[10];
   L->w_ent = (const int4*)dst[11]; L->w_ptr = (const int*)dst[12];
   L->d_pair = (const int*)dst[13]; L->d_plist = (const int*)dst[14];
+  L->has_dup = !d_dup.empty();
   *out = L;
   return MO_OK;
 }
@@ -1514,6 +1516,73 @@ int mo_qp_gradients_blocks_shared(mo_plan* plan, const mo_residual_layout* cost_
   a.workspace = workspace;
   MO_HIP_CHECK(hipSetDevice(plan->desc.device));
   MO_HIP_CHECK(mo::launch_blocks_shared_grad(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// What mo_qp_gradients_blocks_weighted_shared and its workspace query judge alike: what the arguments alone tell, then the plan, the layout
+// and the LDS rule.  J_blocks / r / weights / vars / u / the workspace are not looked at here.
+int block_wshared_args(const mo_plan* plan, const mo_residual_layout* cost_layout, int64_t r_stride, int64_t weights_stride, int64_t batch,
+                       const mo_block_weighted_shared_grads* out, mo::BlockWSharedArgs* a) {
+  if (!cost_layout) return fail(MO_ERR_INVALID_ARGUMENT, "cost_layout is NULL");
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (out->dr && r_stride != 0)
+    return fail(MO_ERR_INVALID_ARGUMENT, "dr summed over the batch needs one r for the batch: r_stride is %lld, not 0", (long long)r_stride);
+  if (out->dweights && weights_stride != 0)
+    return fail(MO_ERR_INVALID_ARGUMENT, "dweights summed over the batch needs one instance of the weights: weights_stride is %lld, not 0", (long long)weights_stride);
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, cost_layout)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  memset(a, 0, sizeof(*a));
+  a->out = *out;
+  a->n = d.n; a->k = d.k; a->m = d.m; a->rows = cost_layout->rows; a->values = cost_layout->values; a->batch = batch;
+  a->d_row = cost_layout->d_row; a->d_idx = cost_layout->d_idx; a->d_val = cost_layout->d_val; a->d_dup = cost_layout->d_dup;
+  a->d_pair = cost_layout->d_pair; a->d_plist = cost_layout->d_plist; a->has_dup = cost_layout->has_dup;
+  a->r_stride = r_stride; a->weights_stride = weights_stride;
+  if (!mo::blocks_wshared_fits(*a, plan->elem))
+    return fail(MO_ERR_UNSUPPORTED, "n = %d, %d residual rows: one staged problem (2 n + 2 rows values, rows more with dweights) beside 64 bytes of flags exceeds the 64 KiB of LDS the batch-reduced weighted block gradient uses",
+                d.n, cost_layout->rows);
+  return MO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mo_qp_gradients_blocks_weighted_shared_workspace(const mo_plan* plan, const mo_residual_layout* cost_layout, int64_t r_stride,
+                                                     int64_t weights_stride, int64_t batch, const mo_block_weighted_shared_grads* out,
+                                                     int64_t* bytes) {
+  g_err[0] = 0;
+  if (!bytes) return fail(MO_ERR_INVALID_ARGUMENT, "bytes is NULL");
+  mo::BlockWSharedArgs a;
+  if (int rc = block_wshared_args(plan, cost_layout, r_stride, weights_stride, batch, out, &a)) return rc;
+  *bytes = (int64_t)mo::blocks_wshared_workspace_bytes(a, plan->elem, plan->num_cus);
+  return MO_OK;
+}
+
+int mo_qp_gradients_blocks_weighted_shared(mo_plan* plan, const mo_residual_layout* cost_layout, const void* J_blocks, const void* r,
+                                           int64_t r_stride, const void* weights, int64_t weights_stride, int64_t batch, const void* vars,
+                                           int64_t vars_stride, const void* u, int64_t u_stride, const int32_t* status_fwd,
+                                           const int32_t* status_adj, const mo_block_weighted_shared_grads* out, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (!J_blocks || !r) return fail(MO_ERR_INVALID_ARGUMENT, "J_blocks / r is NULL");
+  if (!weights) return fail(MO_ERR_INVALID_ARGUMENT, "weights is NULL (the unweighted call is mo_qp_gradients_blocks_shared)");
+  mo::BlockWSharedArgs a;
+  if (int rc = block_wshared_args(plan, cost_layout, r_stride, weights_stride, batch, out, &a)) return rc;
+  if (int rc = reduced_call_tail(plan, batch, vars, vars_stride, u, u_stride, workspace, workspace_bytes,
+                                 mo::blocks_wshared_workspace_bytes(a, plan->elem, plan->num_cus), "mo_qp_gradients_blocks_weighted_shared_workspace")) return rc;
+  const mo_block_weighted_shared_grads& o = a.out;
+  if (!o.dJ_blocks && !o.dr && !o.dlambda && !o.dweights) return MO_OK;
+  a.J = J_blocks; a.r = r; a.weights = weights;
+  a.vars = vars; a.vars_stride = vars_stride; a.u = u; a.u_stride = u_stride;
+  a.status_fwd = status_fwd; a.status_adj = status_adj;
+  a.workspace = workspace;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_blocks_wshared_grad(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
   return MO_OK;
 }
 

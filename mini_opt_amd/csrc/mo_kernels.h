@@ -338,4 +338,26 @@ size_t blocks_tangent_lds_bytes(int n, int k, int m, int rows, int elem_size, bo
 bool blocks_tangent_fits(int n, int k, int m, int rows, int elem_size, bool weighted = false);          // ... within 64 KiB
 hipError_t launch_blocks_tangent(const BlockTangentArgs& a, int dtype, int num_cus, hipStream_t stream);
 
+// the gradients of the weighted block cost SUMMED over the batch, for ONE instance of the packed blocks under weights and residuals per
+// problem (mo_qp_gradients_blocks_weighted_shared), qp_grad_blocks_wshared.hip: t = J x_loc + r and s = J u_loc per problem on chip, the
+// packed sums per chunk, and a finish through the layout's backward schedules.  No moments: the weights keep the sums from factoring.
+struct BlockWSharedArgs {
+  int n, k, m, rows;          // plan n, k, m; sum R_b of the cost layout
+  long long values;
+  long long batch;
+  const int4* d_row; const int* d_idx; const int4* d_val; const int* d_dup; const int* d_pair; const int* d_plist;   // cost layout (BlockGradArgs)
+  int has_dup;                // the layout's partner / pair lists are non-empty
+  const void* J;              // ONE instance
+  const void* r; long long r_stride;
+  const void* weights; long long weights_stride;
+  const void* vars; long long vars_stride;
+  const void* u; long long u_stride;
+  const int* status_fwd; const int* status_adj;
+  mo_block_weighted_shared_grads out;   // NULL members are neither computed nor written
+  void* workspace;            // blocks_wshared_workspace_bytes, 16-byte aligned
+};
+size_t blocks_wshared_workspace_bytes(const BlockWSharedArgs& a, int elem_size, int num_cus);
+bool blocks_wshared_fits(const BlockWSharedArgs& a, int elem_size);   // the LDS rule of mo_qp_gradients_blocks_weighted_shared
+hipError_t launch_blocks_wshared_grad(const BlockWSharedArgs& a, int dtype, int num_cus, hipStream_t stream);
+
 }  // namespace mo

@@ -10,6 +10,8 @@
     qp_tangent_rhs_blocks, qp_jvp_blocks    the same for residual-block input: rho from the PACKED tangents of the blocks
     qp_gradients_blocks_weighted, qp_tangent_rhs_blocks_weighted, qp_jvp_blocks_weighted    the block calls for a cost with one weight per
                     stacked residual row, 1/2 sum_i w_i (J x + r)_i^2: the weights' own gradient and tangent beside the blocks'
+    qp_gradients_blocks_weighted_shared    mo_qp_gradients_blocks_weighted_shared  the weighted block gradients SUMMED over the batch, for ONE
+                    instance of the blocks under weights and residuals per problem
     solve_qp        the user-facing call: forward = Solve (the kernels of qp.QPInteriorPointSolver, fused where the shape allows),
                     backward = ONE transposed KKT solve + ONE gradient launch for exactly the inputs that require a gradient
                     (+ ONE batch-reduced launch for the inputs given once for the batch, leading dimension 1),
@@ -589,6 +591,46 @@ def qp_gradients_blocks_weighted(layout: ResidualLayout, J_blocks: torch.Tensor,
     return out
 
 
+def qp_gradients_blocks_weighted_shared(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, weights: torch.Tensor,
+                                        vars: torch.Tensor, u: torch.Tensor, k: int = 0, m: int = 0,
+                                        want: Iterable[str] = ("J_blocks", "lam"), status_fwd: Optional[torch.Tensor] = None,
+                                        status_adj: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """mo_qp_gradients_blocks_weighted_shared: the gradients of qp_gradients_blocks_weighted named in `want`, SUMMED over the batch, for ONE
+    instance of the packed blocks: "J_blocks" [1, values], "r" [1, rows], "lam" [1], "weights" [1, rows].  J_blocks [1, values],
+    r [B or 1, rows], weights [B or 1, rows]; "r" needs r [1, rows], "weights" needs weights [1, rows].  k, m: the (G, c) problem's equality
+    and inequality rows.  status_fwd / status_adj: [B] int32 status words; a problem counts iff every given word is MO_STATUS_OK (its rows
+    of `vars` / `u` / `r` / `weights` may then hold anything).  A row whose weight is exactly 0 in a problem contributes exactly nothing
+    to "J_blocks" and "r" from that problem, whatever its r holds.  No [B, values] gradient is formed: the workspace (chunk partials, from
+    torch's allocator) is a few packed vectors per CU."""
+    want = tuple(want)
+    _check_names(want, "gradient", _WEIGHTED_COST)
+    k, m = int(k), int(m)
+    V = layout.n + 2 * m + k
+    B = _check_state_pair(vars, u, "u", V, layout)
+    _check_status(status_fwd, "status_fwd", B, layout.device)
+    _check_status(status_adj, "status_adj", B, layout.device)
+    blocks = _Blocks(layout, None, k, m)
+    keep = []
+    J_ptr, _, r_ptr, r_stride = _take_cost_blocks(blocks, J_blocks, r, B, keep, J_lead=1)          # ONE instance of J_blocks
+    w_ptr, w_stride = _take_weights(blocks, weights, B, keep)
+    if "r" in want:
+        if int(r.shape[0]) != 1:
+            raise ValueError("gradient 'r' summed over the batch needs r [1, rows]")
+        r_stride = 0      # (also for a batch of one, where _take reports the row's length)
+    if "weights" in want:
+        if int(weights.shape[0]) != 1:
+            raise ValueError("gradient 'weights' summed over the batch needs weights [1, rows]")
+        w_stride = 0
+    out, g = _outputs(L.BlockWeightedSharedGrads(), _WEIGHTED, blocks, want, 1, strided=False)
+    plan, lib = _plan_of(layout.n, k, m, 0, layout.dtype, layout.device, B), L.lib()
+    _reduced_launch(layout.device,
+                    lambda nbytes: lib.mo_qp_gradients_blocks_weighted_shared_workspace(plan, layout.h, r_stride, w_stride, B, C.byref(g), nbytes),
+                    lambda work, nbytes, stream: lib.mo_qp_gradients_blocks_weighted_shared(plan, layout.h, J_ptr, r_ptr, r_stride, w_ptr, w_stride,
+                                                                                            B, _ptr(vars), V, _ptr(u), V, _ptr(status_fwd),
+                                                                                            _ptr(status_adj), C.byref(g), work, nbytes, stream))
+    return out
+
+
 def qp_tangent_rhs_blocks_weighted(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, weights: torch.Tensor, vars: torch.Tensor,
                                    tangents: Dict[str, torch.Tensor], k: int = 0, m: int = 0, eq_layout: Optional[ResidualLayout] = None,
                                    cons_var: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -709,15 +751,18 @@ class QPSolveWeightedBlocksFunction(torch.autograd.Function):
     cons_a, cons_b, weights, cons_var, layout, eq_layout, params) -> (v, status); weights [B or 1, layout.rows].  Any input given once is read
     with stride 0 in the forward: J_blocks [1, values] with weights [B, rows] forms G per problem from the ONE instance of J_blocks.  The
     gradients of the cost members -- J_blocks, r, lam, weights -- come from ONE mo_qp_gradients_blocks_weighted launch per problem; those of
-    inputs given once are summed over the batch afterwards ([1, ...]): the batch-reduced launch (mo_qp_gradients_blocks_shared) knows no
-    weights.  A backward that does not ask for J_blocks' gradient forms no [B, values] tensor.  The equality and constraint members go the
-    ways of QPSolveBlocksFunction; so do lam's rule (its gradient and tangent count only where lam > 0) and the zero gradients and tangents
-    of problems whose forward, adjoint or tangent status is not OK."""
+    inputs given once are summed over the batch afterwards ([1, ...]).  With reduce_in_kernel (the last, optional argument of forward) and
+    J_blocks given once, the cost members given once come from ONE mo_qp_gradients_blocks_weighted_shared launch instead and only the
+    members given per problem go through the per-problem launch, which then forms no [B, values] tensor; the default keeps the bits of
+    the per-problem route's sum.  A backward that does not ask for J_blocks' gradient forms no [B, values] tensor.  The equality and
+    constraint members go the ways of QPSolveBlocksFunction; so do lam's rule (its gradient and tangent count only where lam > 0) and the
+    zero gradients and tangents of problems whose forward, adjoint or tangent status is not OK."""
 
     NAMES = WEIGHTED_TANGENTS
 
     @staticmethod
-    def forward(ctx, J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, weights, cons_var, layout, eq_layout, params):
+    def forward(ctx, J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, weights, cons_var, layout, eq_layout, params, reduce_in_kernel=False):
+        ctx.reduce_in_kernel = bool(reduce_in_kernel)
         det = lambda t: None if t is None else t.detach()
         J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b, weights = (det(t) for t in (J_blocks, r, lam, J_eq_blocks, r_eq, cons_a, cons_b,
                                                                                           weights))
@@ -745,7 +790,9 @@ class QPSolveWeightedBlocksFunction(torch.autograd.Function):
         names = QPSolveWeightedBlocksFunction.NAMES
         want = [nm for nm, nd in zip(names, ctx.needs_input_grad[:8]) if nd]
         sel = lambda group, among: [nm for nm in group if nm in among]
-        cost = sel(want, _WEIGHTED_COST)                     # per problem always: shared ones are summed by _per_problem
+        cost = sel(want, _WEIGHTED_COST)                     # per problem by default: shared ones are summed by _per_problem
+        reduced = [nm for nm in cost if nm in ctx.shared] if ctx.reduce_in_kernel and "J_blocks" in ctx.shared else []
+        cost = [nm for nm in cost if nm not in reduced]      # (reduce_in_kernel: what is left has a leading dimension of B; no dJ_blocks)
         each, summed = _partition(sel(want, _BLOCK_EQ + _CONS), ctx.shared, "r", "J_blocks")
         grads: Dict[str, torch.Tensor] = {}
         if cost:
@@ -756,6 +803,9 @@ class QPSolveWeightedBlocksFunction(torch.autograd.Function):
         if cons:
             grads.update(qp_gradients(problem, v, u, cons))
         grads = _per_problem(grads, ok, ctx.shared)
+        if reduced:
+            grads.update(qp_gradients_blocks_weighted_shared(ctx.layout, ctx.J_blocks, ctx.r, ctx.weights, v, u, k=problem.k, m=problem.m,
+                                                             want=reduced, status_fwd=ctx.status, status_adj=ctx.adjoint_status))
         eq, cons = sel(summed, _BLOCK_EQ), sel(summed, _CONS)
         if eq:
             grads.update(qp_gradients_blocks_shared(ctx.layout, None, None, v, u, k=problem.k, m=problem.m, want=eq, eq_layout=ctx.eq_layout,
@@ -764,10 +814,11 @@ class QPSolveWeightedBlocksFunction(torch.autograd.Function):
             grads.update(qp_gradients_shared(problem, v, u, cons, status_fwd=ctx.status, status_adj=ctx.adjoint_status))
         if "lam" in grads:
             grads["lam"] = _where_lam_added(ctx.lam, grads["lam"])
-        return (*[grads.get(nm) for nm in names], None, None, None, None)
+        return (*[grads.get(nm) for nm in names], None, None, None, None, None)
 
     @staticmethod
-    def jvp(ctx, dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b, dweights, _dcons_var, _dlayout, _deq_layout, _dparams):
+    def jvp(ctx, dJ_blocks, dr, dlam, dJ_eq_blocks, dr_eq, dcons_a, dcons_b, dweights, _dcons_var, _dlayout, _deq_layout, _dparams,
+            _dreduce=None):
         """torch.autograd.forward_ad: ONE mo_qp_tangent_rhs_blocks_weighted launch + ONE KKT solve; a dual `weights` is the tangent wdot."""
         if dlam is not None:
             dlam = _where_lam_added(ctx.lam, dlam)
@@ -833,7 +884,8 @@ def _result(v: torch.Tensor, status: torch.Tensor, n: int, m: int, k: int, retur
 
 def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons_var=None, cons_a=None, cons_b=None,
              params: Optional[Params] = None, return_all: bool = False, return_status: bool = False, layout: Optional[ResidualLayout] = None,
-             J_blocks=None, eq_layout: Optional[ResidualLayout] = None, J_eq_blocks=None, r_eq=None, weights=None):
+             J_blocks=None, eq_layout: Optional[ResidualLayout] = None, J_eq_blocks=None, r_eq=None, weights=None,
+             reduce_in_kernel: bool = False):
     """Solve a batch of QPs   min 1/2 x^T G x + c^T x   s.t.  A_eq x + b_eq = 0,  cons_a[i] x[cons_var[i]] + cons_b[i] >= 0   on the GPU and
     keep the result on the autograd graph.  Give EITHER (G [B, n, n] SYMMETRIC, c [B, n]) OR the least-squares form (J [B, m_r, n], r [B, m_r],
     lam: float or [B] tensor; G = J^T J + lam I, c = J^T r, lam added where > 0).  A_eq [B, k, n] (rows = constraints), b_eq [B, k];
@@ -850,10 +902,14 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
     weights [B or 1, layout.rows] (residual-block form only): one weight per stacked residual row, the cost 1/2 sum_i w_i (J x + r)_i^2 +
     1/2 lam |x|^2 -- confidences per measurement, or a 0 / 1 mask: a row whose weight is exactly 0 contributes exactly nothing, its J values
     and r may be NaN, and its entries of J_blocks.grad and r.grad are exactly 0.  weights.grad arrives as [B, rows] ([1, rows] for a weight
-    given once); forward_ad takes a dual `weights`.  Under weights every input given once is still read with stride 0, but the gradients of
-    J_blocks, r, lam and weights given once are formed per problem and summed afterwards: the batch-reduced launch
-    (mo_qp_gradients_blocks_shared) does not know weights (QPSolveWeightedBlocksFunction).  Without `weights` the call is exactly the
-    unweighted one.
+    given once); forward_ad takes a dual `weights`.  Under weights every input given once is still read with stride 0; by default the
+    gradients of J_blocks, r, lam and weights given once are formed per problem and summed afterwards (QPSolveWeightedBlocksFunction).
+    reduce_in_kernel=True (only with `weights`): with J_blocks given once, the cost members given once -- J_blocks, lam, r, weights -- come
+    from ONE batch-reduced launch (mo_qp_gradients_blocks_weighted_shared) and no [B, values] gradient is formed; r [B, rows] and
+    weights [B, rows] come from one per-problem launch that does not ask for J_blocks' gradient.  The summed gradients then agree with the
+    default route's within rounding, not bit for bit (another order of the sums), which is why the flag is opt-in: the default route
+    keeps the bits it has.  Forward values and jvp are untouched; with J_blocks per problem the flag changes nothing.  Without `weights`
+    the call is exactly the unweighted one, whatever the flag.
     Returns x [B, n] (return_all: x, s, y, z), and with return_status also the [B] int32 forward status (MO_STATUS_*).
 
     Gradients: every floating-point input that requires_grad receives one, nothing else is computed.  G's gradient is the one with respect
@@ -866,7 +922,7 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
         if G is not None or c is not None or J is not None or A_eq is not None or b_eq is not None:
             raise ValueError("layout= (residual-block input) excludes G, c, J, A_eq and b_eq: the three input forms are mutually exclusive")
         return _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status,
-                                weights)
+                                weights, reduce_in_kernel)
     if (J is None) == (G is None):
         raise ValueError("give either (G, c) or (J, r)")
     ref = J if J is not None else G
@@ -886,7 +942,7 @@ def solve_qp(G=None, c=None, J=None, r=None, lam=0.0, A_eq=None, b_eq=None, cons
 
 
 def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, cons_var, cons_a, cons_b, params, return_all, return_status,
-                     weights=None):
+                     weights=None, reduce_in_kernel=False):
     if layout is None or J_blocks is None or r is None:
         raise ValueError("the residual-block form needs layout, J_blocks and r")
     if (eq_layout is None) != (J_eq_blocks is None) or (eq_layout is None) != (r_eq is None):
@@ -898,7 +954,7 @@ def _solve_qp_blocks(layout, J_blocks, r, lam, eq_layout, J_eq_blocks, r_eq, con
     if w_t is not None:
         cons_a_t, cons_b_t, cons_var_t = cons
         v, status = QPSolveWeightedBlocksFunction.apply(J_t, r_t, lam_t, J_eq_t, r_eq_t, cons_a_t, cons_b_t, w_t, cons_var_t, layout, eq_layout,
-                                                        params)
+                                                        params, bool(reduce_in_kernel))
     else:
         v, status = QPSolveBlocksFunction.apply(J_t, r_t, lam_t, J_eq_t, r_eq_t, *cons, layout, eq_layout, params)
     m = 0 if cons_a is None else int(cons_a.shape[1])

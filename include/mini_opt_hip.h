@@ -164,7 +164,12 @@ int mo_linearize(mo_plan* plan, const mo_problem* prob, int64_t batch, void* G_o
 /* QP::ComputeEigenvalueStats (qp.hpp:122-123, qp.cc:12-16): out[p] = {min, max, min |.|} of the eigenvalues of the QP Hessian of problem p
  * (QPEigenvalues, structs.hpp:267-275) -- of sym(G) from the lower triangle of (G, c) input, as Eigen's SelfAdjointEigenSolver reads it, or of
  * G = J^T J + lambda I for (J, r, lambda) input (what LinearizeAndFillQP hands the reference's QP, nonlinear.cc:182-189).  Any n the plan
- * accepts; computed in fp64 (Householder tridiagonalisation + Sturm-count multisection), written in the plan's dtype.  out: [batch][3]. */
+ * accepts; computed in fp64 (Householder tridiagonalisation + Sturm-count multisection), written in the plan's dtype.  out: [batch][3].
+ * Non-finite input: a NaN or +-inf among the entries read -- the lower triangle of G (the strict upper triangle is never read), any entry of
+ * J, or a J^T J that overflows -- makes the three outputs of THAT problem NaN, as SelfAdjointEigenSolver propagates it; the other problems of
+ * the batch are not affected.  A NaN (or negative) lambda acts as 0, like the reference's `if (lambda > 0)`.
+ * Scaling: the matrix is scaled by the exact power of two that brings its largest |entry| into [1, 2) and the results are scaled back, so
+ * 2^s G gives 2^s times the results of G, bit for bit, as long as the results neither overflow nor become subnormal in the plan's dtype. */
 int mo_qp_eigenvalue_stats(mo_plan* plan, const mo_problem* prob, int64_t batch, void* out, void* stream);
 
 /* Replaces the whole of LinearizeAndFillQP (nonlinear.cc:170-214) for dense residual stacks.  The caller hands over the cost

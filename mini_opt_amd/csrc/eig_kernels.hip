@@ -4,12 +4,17 @@
 //
 // One 256-thread workgroup per problem, always in fp64 (an fp32 plan's G is widened on load):
 //   1. A = sym(G) from the lower triangle of the caller's column-major G -- or G = J^T J + lambda I from the stacked Jacobian (any layout of J),
-//      as LinearizeAndFillQP forms it (nonlinear.cc:182-189) -- in LDS (n x (n | 1) doubles); beyond ~139 variables in the plan's global workspace
-//      slot of the workgroup (the H workspace of the generic kernel's LARGE path, allocated by mo_plan_create).
+//      as LinearizeAndFillQP forms it (nonlinear.cc:182-189) -- in LDS (n x (n | 1) doubles) up to n = 140 (163,552 of the 163,840 bytes); from n = 141 on in the
+//      plan's global workspace slot of the workgroup (the H workspace of the generic kernel's LARGE path, allocated by mo_plan_create).
+//      A non-finite entry among those read (NaN, +-inf, or a J^T J that overflows) makes the three outputs of that problem NaN, as Eigen's solver
+//      propagates it; the strict upper triangle of G is never read.  Otherwise A is scaled by the exact power of two that brings max |A_ij| into
+//      [1, 2) -- Eigen divides by the largest |coefficient| -- and the three results are scaled back, so 2^s G gives 2^s times the bits of G
+//      wherever neither is subnormal or overflows: no square underflows to the "already tridiagonal" branch, none overflows.
 //   2. Householder tridiagonalisation T = Q^T A Q (n - 2 reflections; the matrix-vector product and the rank-2 update are spread over the workgroup).
 //   3. Sturm counts on T: the number of eigenvalues below x is the number of negative terms of q_0 = d_0 - x, q_i = d_i - x - e_{i-1}^2 / q_{i-1}.
 //      Four eigenvalues are wanted -- index 0 (min), n - 1 (max) and the two around zero, indices c - 1 and c with c = count(0) -- and each is
-//      located by 64-way multisection: 64 lanes evaluate 64 counts per round, ten rounds shrink the Gershgorin interval by 65^10 > 2^60.
+//      located by 64-way multisection: 64 lanes evaluate 64 counts per round, ten rounds shrink the Gershgorin interval by 65^10 > 2^60
+//      (the loop runs eleven: one to spare).
 //      All 256 threads work: four targets x 64 section points.  Accuracy: a few ulp of |T| absolute, like LAPACK's bisection.
 #include <math.h>
 
@@ -39,6 +44,15 @@ __device__ inline double block_sum(double v, double* red, int tid) {   // sum ov
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
 }
+__device__ inline double block_max(double v, double* red, int tid) {   // max over the workgroup of values that are >= 0 or +inf, never NaN
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+__device__ inline double abs_or_inf(double s) { return fabs(s) <= 1.7976931348623157e308 ? fabs(s) : INFINITY; }   // NaN and +-inf: +inf (fmax would drop a NaN)
 
 template <typename T>
 __global__ __launch_bounds__(kEigThreads) void qp_eig_kernel(const EigArgs a) {
@@ -58,6 +72,7 @@ __global__ __launch_bounds__(kEigThreads) void qp_eig_kernel(const EigArgs a) {
     if (a.skip && a.skip[p * a.skip_stride] >= 0) continue;   // wave-uniform per workgroup: one problem per workgroup
     __syncthreads();
     // ---- 1. A = sym(G)
+    double amax = 0.0;   // max |A_ij| over the entries this thread reads; +inf if one of them is not finite
     if (a.J) {
       const T* Jp = (const T*)a.J + p * a.J_stride;
       const long long rs = a.J_row_major ? a.J_ld : 1, cs = a.J_row_major ? 1 : a.J_ld;
@@ -69,6 +84,7 @@ __global__ __launch_bounds__(kEigThreads) void qp_eig_kernel(const EigArgs a) {
         double s = 0.0;
         for (int r = 0; r < a.m_r; ++r) s = fma((double)Jp[r * rs + i * cs], (double)Jp[r * rs + j * cs], s);
         if (i == j) s += lam;
+        amax = fmax(amax, abs_or_inf(s));
         A[i + (size_t)j * ld] = s;
         A[j + (size_t)i * ld] = s;
       }
@@ -78,6 +94,25 @@ __global__ __launch_bounds__(kEigThreads) void qp_eig_kernel(const EigArgs a) {
         const int i = idx % n, j = idx / n;
         if (i < j) continue;
         const double s = (double)Gp[i + (size_t)j * a.G_ld];   // lower triangle only (SelfAdjointEigenSolver reads Lower)
+        amax = fmax(amax, abs_or_inf(s));
+        A[i + (size_t)j * ld] = s;
+        A[j + (size_t)i * ld] = s;
+      }
+    }
+    amax = block_max(amax, red, tid);
+    if (!(amax < INFINITY)) {   // uniform over the workgroup (amax comes from red[]), like the skip above: every thread reaches the barrier at the top
+      if (tid == 0) {
+        T* o = (T*)a.out + p * a.out_stride;
+        o[0] = o[1] = o[2] = (T)__builtin_nan("");
+      }
+      continue;
+    }
+    const int ex = amax > 0.0 ? ilogb(amax) : 0;   // A <- 2^-ex A: max |A_ij| in [1, 2); exact, so only the pivmin / pad terms see it
+    if (ex != 0) {
+      for (int idx = tid; idx < n * n; idx += kEigThreads) {   // every thread rescales the entries it wrote
+        const int i = idx % n, j = idx / n;
+        if (i < j) continue;
+        const double s = ldexp(A[i + (size_t)j * ld], -ex);
         A[i + (size_t)j * ld] = s;
         A[j + (size_t)i * ld] = s;
       }
@@ -175,7 +210,7 @@ __global__ __launch_bounds__(kEigThreads) void qp_eig_kernel(const EigArgs a) {
       if (below == below) amin = fmin(amin, fabs(below));
       if (above == above) amin = fmin(amin, fabs(above));
       T* o = (T*)a.out + p * a.out_stride;
-      o[0] = (T)emin_; o[1] = (T)emaxv; o[2] = (T)amin;
+      o[0] = (T)ldexp(emin_, ex); o[1] = (T)ldexp(emaxv, ex); o[2] = (T)ldexp(amin, ex);
     }
   }
 }

@@ -367,7 +367,7 @@ int mo_plan_create(const mo_plan_desc* desc, mo_plan** out) {
   // sizes it is known here (shape, dtype, CU count), so it is allocated now -- for the larger of the two systems a plan launches there, the
   // full one and the k = m = 0 one of mo_linearize / mo_fill_qp (fewer LDS bytes per workgroup, hence possibly MORE workgroups per CU) --
   // and never touched again.  max_batch > 0 bounds the number of slots (a launch's grid never exceeds its batch).
-  // (mo_qp_eigenvalue_stats keeps its n x n fp64 matrix in the same slots once it exceeds the LDS, n > ~139)
+  // (mo_qp_eigenvalue_stats keeps its n x n fp64 matrix in the same slots once it exceeds the LDS: n <= 140 is LDS resident, n >= 141 is not)
   if (mo::generic_needs_large(a, p->elem) || mo::eig_needs_global(desc->n)) {
     mo::KernelArgs lin = a;
     lin.k = 0; lin.m = 0;

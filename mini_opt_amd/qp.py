@@ -353,7 +353,12 @@ class QPNullSpaceSolver:
 
 def eigenvalue_stats(problem: BatchedQP) -> torch.Tensor:
     """QP::ComputeEigenvalueStats (qp.hpp:122-123, qp.cc:12-16) for every QP of the batch: [B, 3] = QPEigenvalues {min, max, abs_min} of the
-    Hessian -- sym(G) from the lower triangle of (G, c) input, or J^T J + lambda I for (J, r, lambda) input."""
+    Hessian -- sym(G) from the lower triangle of (G, c) input, or J^T J + lambda I for (J, r, lambda) input.
+
+    A NaN or +-inf among the entries read (the lower triangle of G -- the strict upper triangle is never read -- or anywhere in J, or a
+    J^T J that overflows) gives [NaN, NaN, NaN] for that problem alone, as Eigen's solver propagates it; a NaN or negative lambda acts as 0.
+    The matrix is scaled by an exact power of two before the factorisation and the results are scaled back: 2^s G gives 2^s times the
+    results of G bit for bit, at any magnitude the dtype can hold."""
     lib = L.lib()
     ref = problem.J if problem.J is not None else problem.G
     B = int(ref.shape[0])

@@ -1912,6 +1912,7 @@ __global__ __launch_bounds__(kMaxThreads) void nullspace_kernel(const KernelArgs
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const NullOps<T> op{w, Mb, n, k};
   const T eps = sizeof(T) == 8 ? (T)2.220446049250313e-16 : (T)1.1920929e-7f;
+  const T tiny = sizeof(T) == 8 ? (T)__DBL_MIN__ : (T)__FLT_MIN__;   // the smallest normal number (makeHouseholder's tol)
   for (long long p = blockIdx.x; p < a.batch; p += gridDim.x) {
     __syncthreads();
     const bool j_level = a.J != nullptr;
@@ -1959,18 +1960,17 @@ __global__ __launch_bounds__(kMaxThreads) void nullspace_kernel(const KernelArgs
       }
       __syncthreads();
       // makeHouseholder on x = M(j.., j): beta = -sign(x0) |x|, tau = (beta - x0) / beta, essential = tail / (x0 - beta)
+      // The tail's squared norm is summed directly for every column, as Eigen does (big - c0^2 is 0 for a tail below sqrt(eps) |c0|, which
+      // is an ordinary row [1, 1e-9, ...]); tau = 0 with beta = c0 only for a tail that is zero up to the smallest normal number.
       const T c0 = op.M(j, j);
-      const T tail2 = big - c0 * c0 > (T)0 ? big - c0 * c0 : (T)0;
       T beta = c0, tj = (T)0;
-      if (tail2 > (T)0) {
-        T tsum = (T)0;                            // recomputed (not big - c0^2): no cancellation
-        for (int i = j + 1 + lane; i < n; i += 64) { const T v = op.M(i, j); tsum += v * v; }
-        tsum = wave_sum(tsum);
-        if (tsum > (T)0) {
-          beta = sqrtT(c0 * c0 + tsum);
-          if (c0 >= (T)0) beta = -beta;
-          tj = (beta - c0) / beta;
-        }
+      T tsum = (T)0;
+      for (int i = j + 1 + lane; i < n; i += 64) { const T v = op.M(i, j); tsum += v * v; }
+      tsum = wave_sum(tsum);
+      if (tsum > tiny) {
+        beta = sqrtT(c0 * c0 + tsum);
+        if (c0 >= (T)0) beta = -beta;
+        tj = (beta - c0) / beta;
       }
       __syncthreads();
       if (tj != (T)0) {
@@ -2022,26 +2022,30 @@ __global__ __launch_bounds__(kMaxThreads) void nullspace_kernel(const KernelArgs
       for (int j = 0; j < k && j < n; ++j) op.reflect(g, j, lane);             // Q^T g = H_{k-1} ... H_0 g
     __syncthreads();
 
-    // ---- G <- Q^T G Q (qp.cc:708), reflector by reflector on the block that still matters (indices >= j)
+    // ---- G <- Q^T G Q (qp.cc:708), reflector by reflector on the block that still matters: indices >= j while j < rank, indices >= rank
+    // beyond (a column under the rank threshold that is not exactly zero has a reflector too, and G_reduced = G[rank.., rank..] needs
+    // its rows rank .. j - 1 transformed as well; v is zero there)
     for (int j = 0; j < k && j < n; ++j) {
       const T tj = tau[j];
       if (tj == (T)0) continue;                                                // uniform
-      for (int i = j + tid; i < n; i += kThreads) {                            // p = tau G v
+      const int lo = j < rank ? j : rank;
+      const auto v = [&](int i) { return i < j ? (T)0 : i == j ? (T)1 : op.M(i, j); };
+      for (int i = lo + tid; i < n; i += kThreads) {                           // p = tau G v
         T acc = (T)0;
-        for (int l = j; l < n; ++l) acc += op.G(i, l) * (l == j ? (T)1 : op.M(l, j));
+        for (int l = j; l < n; ++l) acc += op.G(i, l) * v(l);
         pv[i] = acc * tj;
       }
       __syncthreads();
       if (wave == 0) {
         T s = (T)0;
-        for (int i = j + lane; i < n; i += 64) s += (i == j ? (T)1 : op.M(i, j)) * pv[i];
+        for (int i = j + lane; i < n; i += 64) s += v(i) * pv[i];
         s = wave_sum(s) * (T)0.5 * tj;                                         // alpha = tau (v^T p) / 2
-        for (int i = j + lane; i < n; i += 64) wv[i] = pv[i] - s * (i == j ? (T)1 : op.M(i, j));
+        for (int i = lo + lane; i < n; i += 64) wv[i] = pv[i] - s * v(i);
       }
       __syncthreads();
-      for (int l = j + wave; l < n; l += kWaves) {                             // G -= v w^T + w v^T
-        const T vl = l == j ? (T)1 : op.M(l, j), wl = wv[l];
-        for (int i = j + lane; i < n; i += 64) op.G(i, l) -= (i == j ? (T)1 : op.M(i, j)) * wl + wv[i] * vl;
+      for (int l = lo + wave; l < n; l += kWaves) {                            // G -= v w^T + w v^T
+        const T vl = v(l), wl = wv[l];
+        for (int i = lo + lane; i < n; i += 64) op.G(i, l) -= v(i) * wl + wv[i] * vl;
       }
       __syncthreads();
     }

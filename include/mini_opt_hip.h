@@ -759,6 +759,53 @@ int mo_qp_gradients_blocks_weighted_shared(mo_plan* plan, const mo_residual_layo
                                            const int32_t* status_fwd, const int32_t* status_adj,
                                            const mo_block_weighted_shared_grads* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Robust loss functions for residual-block costs (the reference has none): the weights of the weighted cost above
+ * derived from the residuals themselves, one loss per block b in the rho(s) convention with s_b = |r_b|^2 (all R_b rows) and scale a_b > 0,
+ *   f = 1/2 sum_b rho_b(s_b)        w_b = rho_b'(s_b)        G = sum_b w_b J_b^T J_b (+ lambda I)        c = sum_b w_b J_b^T r_b
+ *   TRIVIAL  rho = s                                                   rho' = 1
+ *   HUBER    rho = s (s <= a^2), 2 a sqrt(s) - a^2                     rho' = 1 (s <= a^2), a / sqrt(s)
+ *   SOFT_L1  rho = 2 a^2 (sqrt(1 + s / a^2) - 1)                       rho' = 1 / sqrt(1 + s / a^2)
+ *   CAUCHY   rho = a^2 log1p(s / a^2)                                  rho' = 1 / (1 + s / a^2)
+ *   TUKEY    rho = (a^2 / 3)(1 - (1 - s / a^2)^3) (s <= a^2), a^2 / 3  rho' = (1 - s / a^2)^2 (s <= a^2), 0
+ * Every row of a block carries the block's w_b; c is the exact gradient of f, G the positive semidefinite IRLS model (no rho'' term).
+ * TUKEY beyond its cutoff gives w_b EXACTLY 0 and falls under the ZERO WEIGHTS rule above.  A NaN in r_b makes w_b and f NaN.
+ * Fixed summation orders, the same bits on every launch: s_b adds the squares of its rows in order, each rounded before it is added; a lane
+ * adds the rho_b of blocks tid, tid + 256, ... in that order and the workgroup sums the lanes like half_sq_out of mo_linearize_blocks. */
+typedef enum { MO_LOSS_TRIVIAL = 0, MO_LOSS_HUBER = 1, MO_LOSS_SOFT_L1 = 2, MO_LOSS_CAUCHY = 3, MO_LOSS_TUKEY = 4 } mo_loss_kind;
+typedef struct mo_residual_loss mo_residual_loss;
+/* kinds[b] (mo_loss_kind), scales[b] = a_b: HOST arrays of the layout's num_blocks entries; the table is uploaded once, as double and as
+ * float (it serves plans of either dtype on the layout's device): all allocation happens here, none in a launch.  The layout is read here
+ * only.  MO_ERR_INVALID_ARGUMENT naming the block: an unknown kind; a scale that is not finite or not > 0 on a non-TRIVIAL block (a
+ * TRIVIAL block's scale is ignored).  A table whose every entry is TRIVIAL is flagged: every call below then IS its sibling, bit for bit. */
+int mo_residual_loss_create(const mo_residual_layout* layout, const int32_t* kinds, const double* scales, mo_residual_loss** out);
+int mo_residual_loss_destroy(mo_residual_loss* loss);
+/* weights_out [batch][sum R_b] (may be NULL; weights_stride in elements): w_b repeated over the block's rows, the layout
+ * mo_linearize_blocks_weighted reads.  rho_out [batch] (may be NULL) = 1/2 sum_b rho_b(s_b).  fp64 and fp32 plans; r_stride 0 = one
+ * instance.  For callers who run their own IRLS through the weighted calls, and the second route of mo_linearize_blocks_robust. */
+int mo_residual_loss_eval(mo_plan* plan, const mo_residual_layout* layout, const mo_residual_loss* loss, const void* r, int64_t r_stride,
+                          int64_t batch, void* weights_out, int64_t weights_stride, void* rho_out, void* stream);
+/* mo_linearize_blocks with the loss: ONE kernel stages r, forms s_b, w_b, rho_b per block into the LDS slot of the weighted kernel's weights
+ * and proceeds as mo_linearize_blocks_weighted -- no [batch][rows] weights go through memory.  half_sq_out = 1/2 sum rho.
+ * BITS: G_out, c_out and half_sq_out equal what mo_residual_loss_eval followed by mo_linearize_blocks_weighted (G, c) and rho_out
+ * (half_sq_out) give.  weights_out (may be NULL): the weights the kernel used, for outlier diagnosis.  Staging rule of the weighted sibling,
+ * (sum R_b P_b + 2 sum R_b) values within 48 KiB; a layout beyond it runs the two launches above through weights_out, and with weights_out
+ * NULL there the call returns MO_ERR_UNSUPPORTED before any launch ("... pass weights_out").  G_out == NULL, lambda_vec and J_stride == 0
+ * as in the siblings.  loss == NULL or all TRIVIAL: mo_linearize_blocks (weights_out, when given, is filled with 1 on the stream). */
+int mo_linearize_blocks_robust(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
+                               int64_t r_stride, double lambda, const void* lambda_vec, int64_t lambda_stride, int64_t batch, void* G_out,
+                               int64_t G_stride, int32_t G_ld, void* c_out, int64_t c_stride, void* half_sq_out, const mo_residual_loss* loss,
+                               void* weights_out, int64_t weights_stride, void* stream);
+/* mo_nls_solve_blocks minimising f = 1/2 sum_b rho_b(|r_b|^2) over the cost blocks: every outer iteration linearises with
+ * mo_linearize_blocks_robust (errors_pre.f = its 1/2 sum rho), every line-search candidate's f is mo_residual_loss_eval's rho_out on r_cand;
+ * penalty selection, directional derivatives (c^T dx is exact: c is the gradient of f), eigenvalue logging and the QP read the assembled
+ * (G, c) as before.  Equality residuals take no loss.  cost_loss NULL or all TRIVIAL: mo_nls_solve_blocks, same launches, same bits.
+ * The per-call scratch gains a [batch][sum R_b] weight buffer only when the cost layout does not stage. */
+int mo_nls_solve_blocks_robust(mo_plan* plan, const mo_nls_problem* np, const mo_residual_layout* cost_layout,
+                               const mo_residual_loss* cost_loss, const mo_residual_layout* eq_layout, int64_t batch,
+                               const mo_nls_params* params, mo_nls_eval_fn eval, void* user, int32_t* termination, int32_t* num_iterations,
+                               void* iterations, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,8 +15,14 @@ _DIFF_EXPORTS = ("solve_qp", "kkt_solve", "qp_gradients", "qp_gradients_shared",
                  "qp_jvp_blocks_weighted", "QPSolveWeightedBlocksFunction", "qp_gradients_blocks_weighted_shared")
 
 
+_QP_EXPORTS = ("ResidualLayout", "ResidualLoss", "loss_weights", "linearize_blocks")   # residual-block input and its robust losses
+
+
 def __getattr__(name):  # the differentiable front end needs torch: imported on first use, like qp
     if name in _DIFF_EXPORTS:
         from . import diff
         return getattr(diff, name)
+    if name in _QP_EXPORTS:
+        from . import qp
+        return getattr(qp, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -27,6 +27,7 @@ MO_KKT_TRANSPOSE = 4
 (MO_STATUS_OK, MO_STATUS_NONPOSITIVE_SLACK, MO_STATUS_FACTORIZATION_FAILED, MO_STATUS_NONFINITE, MO_STATUS_BAD_INDEX,
  MO_STATUS_NOT_POSITIVE_DEFINITE) = range(6)
 MO_KKT_RECORD, MO_IP_RECORD, MO_ITER_RECORD = 4, 6, 14
+MO_LOSS_TRIVIAL, MO_LOSS_HUBER, MO_LOSS_SOFT_L1, MO_LOSS_CAUCHY, MO_LOSS_TUKEY = range(5)   # mo_loss_kind
 
 # every symbol include/mini_opt_hip.h declares
 EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default_solve_params", "mo_plan_create",
@@ -39,7 +40,9 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_qp_gradients_blocks", "mo_qp_gradients_eq_blocks", "mo_qp_gradients_blocks_shared_workspace", "mo_qp_gradients_blocks_shared",
            "mo_qp_tangent_rhs", "mo_qp_tangent_rhs_blocks",
            "mo_linearize_blocks_weighted", "mo_qp_gradients_blocks_weighted", "mo_qp_tangent_rhs_blocks_weighted",
-           "mo_qp_gradients_blocks_weighted_shared_workspace", "mo_qp_gradients_blocks_weighted_shared"]
+           "mo_qp_gradients_blocks_weighted_shared_workspace", "mo_qp_gradients_blocks_weighted_shared",
+           "mo_residual_loss_create", "mo_residual_loss_destroy", "mo_residual_loss_eval", "mo_linearize_blocks_robust",
+           "mo_nls_solve_blocks_robust"]
 
 
 class PlanDesc(C.Structure):
@@ -243,6 +246,12 @@ def lib() -> C.CDLL:
     L.mo_qp_gradients_blocks_weighted_shared_workspace.argtypes = [vp, vp, i64, i64, i64, C.POINTER(BlockWeightedSharedGrads), C.POINTER(i64)]
     L.mo_qp_gradients_blocks_weighted_shared.argtypes = [vp, vp, vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, vp, vp,
                                                          C.POINTER(BlockWeightedSharedGrads), vp, i64, vp]
+    L.mo_residual_loss_create.argtypes = [vp, i32p, C.POINTER(dbl), C.POINTER(vp)]
+    L.mo_residual_loss_destroy.argtypes = [vp]
+    L.mo_residual_loss_eval.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp, vp]
+    L.mo_linearize_blocks_robust.argtypes = [vp, vp, vp, i64, vp, i64, dbl, vp, i64, i64, vp, i64, i32, vp, i64, vp, vp, vp, i64, vp]
+    L.mo_nls_solve_blocks_robust.argtypes = [vp, C.POINTER(NlsProblem), vp, vp, vp, i64, C.POINTER(NlsParams), NLS_EVAL_FN, vp, vp, vp, vp, vp,
+                                             vp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what the header declares
     _lib = L

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -64,6 +65,14 @@ struct mo_residual_layout {
   // the forward-mode schedule of an equality layout (mo_qp_tangent_rhs_blocks, mo::BlockTangentArgs): c_ptr / c_ent filtered by winners
   const int* w_ptr; const int4* w_ent;
   int has_dup;   // some block names a variable twice: d_dup and d_plist are non-empty (mo_qp_gradients_blocks_weighted_shared)
+  std::vector<int> block_rows;   // R_b on the host: what mo_residual_loss_create builds its table from
+};
+
+// Loss table of a layout's blocks (mo_loss_device.h): one device allocation [blk | scales as double | scales as float]
+struct mo_residual_loss {
+  int device, num_blocks, rows, all_trivial;
+  void* dev;
+  const int4* blk; const double* scale_d; const float* scale_f;
 };
 
 namespace {
@@ -872,9 +881,33 @@ mo::BlockGradArgs block_grad_args(const mo_plan* plan, const mo_residual_layout*
 
 // The SQP loop of mo_nls_solve and mo_nls_solve_blocks.  Without block input (dense stacks) it launches exactly the kernels of
 // mo_nls_solve; with block input every outer iteration first forms G, c and A_eq from the packed blocks into per-call scratch and the QP,
-// the eigenvalue statistics and the directional derivatives read that (G, c) input.
+// the eigenvalue statistics and the directional derivatives read that (G, c) input.  cost_loss (block input only; NULL = none): the cost is
+// 0.5 sum rho -- the linearise is the robust one and the f of both error pairs is the loss's, written over nonlinear_errors_kernel's.
+int check_loss(const mo_residual_layout* layout, const mo_residual_loss* loss) {
+  if (loss->device != layout->device) return fail(MO_ERR_INVALID_ARGUMENT, "loss table lives on device %d, layout on %d", loss->device, layout->device);
+  if (loss->num_blocks != layout->num_blocks || loss->rows != layout->rows)
+    return fail(MO_ERR_DIMENSION, "loss table built for %d blocks / %d rows, layout has %d / %d", loss->num_blocks, loss->rows,
+                layout->num_blocks, layout->rows);
+  return MO_OK;
+}
+
+mo::LossArgs loss_args(const mo_residual_loss* loss, int dtype, long long batch) {
+  mo::LossArgs a;
+  memset(&a, 0, sizeof(a));
+  a.num_blocks = loss->num_blocks; a.rows = loss->rows; a.batch = batch;
+  a.blk = loss->blk; a.scale = dtype == MO_F64 ? (const void*)loss->scale_d : (const void*)loss->scale_f;
+  a.rho_stride = 1;
+  return a;
+}
+
+void blocks_args_loss(mo::BlocksArgs* a, const mo_residual_loss* loss, int dtype) {
+  a->loss_blk = loss->blk; a->loss_blocks = loss->num_blocks;
+  a->loss_scale = dtype == MO_F64 ? (const void*)loss->scale_d : (const void*)loss->scale_f;
+  a->half_sq_stride = 1;
+}
+
 int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const mo_residual_layout* cost_layout,
-                   const mo_residual_layout* eq_layout, int64_t batch, const mo_nls_params* prm, mo_nls_eval_fn eval, void* user, int32_t* termination, int32_t* num_iterations,
+                   const mo_residual_loss* cost_loss, const mo_residual_layout* eq_layout, int64_t batch, const mo_nls_params* prm, mo_nls_eval_fn eval, void* user, int32_t* termination, int32_t* num_iterations,
                    void* iterations, int32_t* status, void* stream) {
   g_err[0] = 0;
   if (int rc = check_plan(plan)) return rc;
@@ -919,7 +952,10 @@ int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const m
       if (int rc = check_layout(plan, eq_layout)) return rc;
       if (eq_layout->rows != d.k) return fail(MO_ERR_DIMENSION, "equality layout has %d rows, plan k = %d", eq_layout->rows, d.k);
     }
+    if (cost_loss)
+      if (int rc = check_loss(cost_layout, cost_loss)) return rc;
   }
+  const bool loss_staged = cost_loss && mo::blocks_weighted_stages(cost_layout->values, cost_layout->rows, 8);
   if (batch == 0) return MO_OK;
   MO_HIP_CHECK(hipSetDevice(d.device));
   hipStream_t s = (hipStream_t)stream;
@@ -944,7 +980,9 @@ int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const m
     scratch.reserve<double>((size_t)batch * n * n);
     scratch.reserve<double>((size_t)batch * n);
     scratch.reserve<double>((size_t)batch * k * n);
+    if (cost_loss && !loss_staged) scratch.reserve<double>((size_t)batch * d.m_r);
   }
+  double* w_blk = nullptr;  // the weights of a robust cost whose layout does not stage: the two-launch route
   MO_HIP_CHECK(scratch.commit());
   MO_HIP_CHECK(scratch.alloc(&qp_vars, (size_t)batch * Vs));
   MO_HIP_CHECK(scratch.alloc(&cons_b, (size_t)batch * m));  // the QP's constraints: one stride for (variable, a, shifted b)
@@ -965,6 +1003,7 @@ int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const m
     MO_HIP_CHECK(scratch.alloc(&G_blk, (size_t)batch * n * n));
     MO_HIP_CHECK(scratch.alloc(&c_blk, (size_t)batch * n));
     MO_HIP_CHECK(scratch.alloc(&A_blk, (size_t)batch * k * n));
+    if (cost_loss && !loss_staged) MO_HIP_CHECK(scratch.alloc(&w_blk, (size_t)batch * d.m_r));
   }
 
   mo::NlsArgs na;
@@ -1011,6 +1050,14 @@ int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const m
     cost_ba.lambda_vec = sd + mo::NLS_SD_LAMBDA; cost_ba.lambda_vec_stride = mo::NLS_SD;
     cost_ba.G_out = G_blk; cost_ba.G_out_stride = (long long)n * n; cost_ba.G_out_ld = n;
     cost_ba.c_out = c_blk; cost_ba.c_out_stride = n;
+    if (cost_loss) {
+      if (loss_staged) {
+        blocks_args_loss(&cost_ba, cost_loss, d.dtype);
+        cost_ba.half_sq_out = errors_pre; cost_ba.half_sq_stride = 2;
+      } else {
+        cost_ba.weights = w_blk; cost_ba.weights_stride = d.m_r;
+      }
+    }
     if (k > 0) {
       eq_ba = blocks_args(eq_layout, batch);
       eq_ba.J = np->J_eq; eq_ba.J_stride = np->J_eq_stride; eq_ba.r = np->r_eq; eq_ba.r_stride = np->r_eq_stride;
@@ -1047,18 +1094,32 @@ int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const m
     da.A = A_blk; da.A_stride = (long long)k * n; da.A_ld = k;
   }
 
+  mo::LossArgs la{};  // 0.5 sum rho over nonlinear_errors_kernel's f
+  if (cost_loss) {
+    la = loss_args(cost_loss, d.dtype, batch);
+    la.rho_stride = 2;
+  }
+
   int host_counters[2];
   long long still_active = batch;  // problems the previous outer iteration left active (a hint for the QP kernel's ticket size)
   for (int iter = 0; iter < prm->max_iterations; ++iter) {
     na.iter = iter;
     if (eval(user, MO_NLS_EVAL_LINEARIZE, stream) != 0) return fail(MO_ERR_CALLBACK, "eval(LINEARIZE) failed at iteration %d", iter);
-    if (blocks) {  // LinearizeAndFillQP (nonlinear.cc:182-206) from the packed blocks
+    if (blocks && !cost_loss) {  // LinearizeAndFillQP (nonlinear.cc:182-206) from the packed blocks
       MO_HIP_CHECK(mo::launch_blocks_linearize(cost_ba, d.dtype, plan->num_cus, s));
       if (k > 0) MO_HIP_CHECK(mo::launch_blocks_jacobian(eq_ba, d.dtype, plan->num_cus, s));
     }
     // errors_pre (nonlinear.cc:184-186, 203) and the shifted constraints (:209-212)
     ea.r = np->r; ea.r_stride = np->r_stride; ea.b = np->r_eq; ea.b_stride = np->r_eq_stride; ea.out2 = errors_pre;
     MO_HIP_CHECK(mo::launch_nonlinear_errors(ea, d.dtype, s));
+    if (cost_loss) {  // the robust linearise, after the errors: its 0.5 sum rho replaces their f
+      if (!loss_staged) {
+        la.r = np->r; la.r_stride = np->r_stride; la.weights_out = w_blk; la.weights_stride = d.m_r; la.rho_out = errors_pre;
+        MO_HIP_CHECK(mo::launch_residual_loss(la, d.dtype, plan->num_cus, s));
+      }
+      MO_HIP_CHECK(mo::launch_blocks_linearize(cost_ba, d.dtype, plan->num_cus, s));
+      if (k > 0) MO_HIP_CHECK(mo::launch_blocks_jacobian(eq_ba, d.dtype, plan->num_cus, s));
+    }
     if (m > 0) MO_HIP_CHECK(mo::launch_shift_constraints(sa, d.dtype, s));
     // ComputeStepDirection (nonlinear.cc:216-247): the interior-point QP on device
     if (nls_takes_nullspace_path(plan)) {
@@ -1098,6 +1159,10 @@ int nls_solve_impl(mo_plan* plan, const mo_nls_problem* np, bool blocks, const m
       if (eval(user, MO_NLS_EVAL_ERRORS, stream) != 0) return fail(MO_ERR_CALLBACK, "eval(ERRORS) failed at iteration %d", iter);
       ea.r = np->r_cand; ea.r_stride = np->r_cand_stride; ea.b = np->r_eq_cand; ea.b_stride = np->r_eq_cand_stride; ea.out2 = errors_step;
       MO_HIP_CHECK(mo::launch_nonlinear_errors(ea, d.dtype, s));
+      if (cost_loss) {
+        la.r = np->r_cand; la.r_stride = np->r_cand_stride; la.weights_out = nullptr; la.rho_out = errors_step;
+        MO_HIP_CHECK(mo::launch_residual_loss(la, d.dtype, plan->num_cus, s));
+      }
       MO_HIP_CHECK(hipMemsetAsync(counters, 0, sizeof(int), s));
       MO_HIP_CHECK(mo::launch_nls_search_step(na, s));
       if (retract_cb && eval(user, MO_NLS_EVAL_RETRACT, stream) != 0) return fail(MO_ERR_CALLBACK, "eval(RETRACT) failed at iteration %d", iter);
@@ -1121,14 +1186,22 @@ extern "C" {
 
 int mo_nls_solve(mo_plan* plan, const mo_nls_problem* np, int64_t batch, const mo_nls_params* prm, mo_nls_eval_fn eval,
                  void* user, int32_t* termination, int32_t* num_iterations, void* iterations, int32_t* status, void* stream) {
-  return nls_solve_impl(plan, np, false, nullptr, nullptr, batch, prm, eval, user, termination, num_iterations, iterations, status, stream);
+  return nls_solve_impl(plan, np, false, nullptr, nullptr, nullptr, batch, prm, eval, user, termination, num_iterations, iterations, status, stream);
 }
 
 int mo_nls_solve_blocks(mo_plan* plan, const mo_nls_problem* np, const mo_residual_layout* cost_layout,
                         const mo_residual_layout* eq_layout, int64_t batch, const mo_nls_params* params, mo_nls_eval_fn eval, void* user,
                         int32_t* termination, int32_t* num_iterations, void* iterations, int32_t* status, void* stream) {
-  return nls_solve_impl(plan, np, true, cost_layout, eq_layout, batch, params, eval, user, termination, num_iterations, iterations, status,
-                        stream);
+  return nls_solve_impl(plan, np, true, cost_layout, nullptr, eq_layout, batch, params, eval, user, termination, num_iterations, iterations,
+                        status, stream);
+}
+
+int mo_nls_solve_blocks_robust(mo_plan* plan, const mo_nls_problem* np, const mo_residual_layout* cost_layout,
+                               const mo_residual_loss* cost_loss, const mo_residual_layout* eq_layout, int64_t batch,
+                               const mo_nls_params* params, mo_nls_eval_fn eval, void* user, int32_t* termination, int32_t* num_iterations,
+                               void* iterations, int32_t* status, void* stream) {
+  return nls_solve_impl(plan, np, true, cost_layout, cost_loss && !cost_loss->all_trivial ? cost_loss : nullptr, eq_layout, batch, params, eval,
+                        user, termination, num_iterations, iterations, status, stream);
 }
 
 int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int32_t* rows, const int32_t* params,
@@ -1290,6 +1363,7 @@ int mo_residual_layout_create(const mo_plan* plan, int32_t num_blocks, const int
   L->w_ent = (const int4*)dst[11]; L->w_ptr = (const int*)dst[12];
   L->d_pair = (const int*)dst[13]; L->d_plist = (const int*)dst[14];
   L->has_dup = !d_dup.empty();
+  L->block_rows.assign(rows, rows + num_blocks);
   *out = L;
   return MO_OK;
 }
@@ -1687,6 +1761,132 @@ int mo_residual_eval(mo_plan* plan, int32_t family, int32_t rows, const void* pa
   MO_HIP_CHECK(hipSetDevice(d.device));
   MO_HIP_CHECK(mo::launch_residual_family(family, d.n, rows, batch, d.dtype, params, x, x_stride, r, r_stride, J, J_stride, J_ld,
                                           J_layout == MO_ROW_MAJOR, (hipStream_t)stream));
+  return MO_OK;
+}
+
+// ---- robust loss functions for residual-block costs
+
+int mo_residual_loss_create(const mo_residual_layout* layout, const int32_t* kinds, const double* scales, mo_residual_loss** out) {
+  g_err[0] = 0;
+  if (!out) return fail(MO_ERR_INVALID_ARGUMENT, "out is NULL");
+  *out = nullptr;
+  if (!layout) return fail(MO_ERR_INVALID_ARGUMENT, "layout is NULL");
+  if (!kinds || !scales) return fail(MO_ERR_INVALID_ARGUMENT, "kinds / scales is NULL");
+  const int nb = layout->num_blocks;
+  std::vector<int4> blk((size_t)nb);
+  std::vector<double> sd((size_t)nb);
+  std::vector<float> sf((size_t)nb);
+  int trivial = 1, row = 0;
+  for (int b = 0; b < nb; ++b) {
+    if (kinds[b] < MO_LOSS_TRIVIAL || kinds[b] > MO_LOSS_TUKEY) return fail(MO_ERR_INVALID_ARGUMENT, "block %d: unknown loss kind %d", b, kinds[b]);
+    double a = 1.0;  // a TRIVIAL block's scale is ignored
+    if (kinds[b] != MO_LOSS_TRIVIAL) {
+      a = scales[b];
+      if (!(a > 0) || !std::isfinite(a)) return fail(MO_ERR_INVALID_ARGUMENT, "block %d: loss scale %g must be finite and > 0", b, a);
+      if (!((float)a > 0) || !std::isfinite((float)a))
+        return fail(MO_ERR_INVALID_ARGUMENT, "block %d: loss scale %g is not a finite positive float (the table serves fp32 plans too)", b, a);
+      trivial = 0;
+    }
+    blk[(size_t)b] = make_int4(row, layout->block_rows[(size_t)b], kinds[b], 0);
+    sd[(size_t)b] = a;
+    sf[(size_t)b] = (float)a;
+    row += layout->block_rows[(size_t)b];
+  }
+  mo_residual_loss* T = new (std::nothrow) mo_residual_loss();
+  if (!T) return fail(MO_ERR_HIP, "out of host memory");
+  T->device = layout->device; T->num_blocks = nb; T->rows = layout->rows; T->all_trivial = trivial; T->dev = nullptr;
+  auto pad = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
+  const size_t b_blk = pad(blk.size() * sizeof(int4)), b_d = pad(sd.size() * sizeof(double)), b_f = pad(sf.size() * sizeof(float));
+  if (hipSetDevice(layout->device) != hipSuccess || hipMalloc(&T->dev, b_blk + b_d + b_f) != hipSuccess) {
+    (void)hipGetLastError();
+    delete T;
+    return fail(MO_ERR_HIP, "hipMalloc of the %zu B loss table failed", b_blk + b_d + b_f);
+  }
+  char* base = (char*)T->dev;
+  if (hipMemcpy(base, blk.data(), blk.size() * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(base + b_blk, sd.data(), sd.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(base + b_blk + b_d, sf.data(), sf.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(T->dev);
+    delete T;
+    return fail(MO_ERR_HIP, "upload of the loss table failed");
+  }
+  T->blk = (const int4*)base; T->scale_d = (const double*)(base + b_blk); T->scale_f = (const float*)(base + b_blk + b_d);
+  *out = T;
+  return MO_OK;
+}
+
+int mo_residual_loss_destroy(mo_residual_loss* loss) {
+  if (!loss) return MO_OK;
+  if (loss->dev) {
+    (void)hipSetDevice(loss->device);
+    (void)hipFree(loss->dev);
+  }
+  delete loss;
+  return MO_OK;
+}
+
+int mo_residual_loss_eval(mo_plan* plan, const mo_residual_layout* layout, const mo_residual_loss* loss, const void* r, int64_t r_stride,
+                          int64_t batch, void* weights_out, int64_t weights_stride, void* rho_out, void* stream) {
+  g_err[0] = 0;
+  if (!loss) return fail(MO_ERR_INVALID_ARGUMENT, "loss is NULL");
+  if (!r) return fail(MO_ERR_INVALID_ARGUMENT, "r is NULL");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, layout)) return rc;
+  if (int rc = check_loss(layout, loss)) return rc;
+  if (weights_out && weights_stride < layout->rows) return fail(MO_ERR_DIMENSION, "weights_stride %lld < rows %d", (long long)weights_stride, layout->rows);
+  if (batch == 0 || (!weights_out && !rho_out)) return MO_OK;
+  mo::LossArgs a = loss_args(loss, plan->desc.dtype, batch);
+  a.r = r; a.r_stride = r_stride; a.weights_out = weights_out; a.weights_stride = weights_stride; a.rho_out = rho_out;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  MO_HIP_CHECK(mo::launch_residual_loss(a, plan->desc.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
+int mo_linearize_blocks_robust(mo_plan* plan, const mo_residual_layout* layout, const void* J_blocks, int64_t J_stride, const void* r,
+                               int64_t r_stride, double lambda, const void* lambda_vec, int64_t lambda_stride, int64_t batch, void* G_out,
+                               int64_t G_stride, int32_t G_ld, void* c_out, int64_t c_stride, void* half_sq_out, const mo_residual_loss* loss,
+                               void* weights_out, int64_t weights_stride, void* stream) {
+  if (!loss || loss->all_trivial) {  // the sibling itself; the weights asked for are the table's (all 1)
+    if (int rc = mo_linearize_blocks(plan, layout, J_blocks, J_stride, r, r_stride, lambda, lambda_vec, lambda_stride, batch, G_out, G_stride,
+                                     G_ld, c_out, c_stride, half_sq_out, stream)) return rc;
+    if (!loss || !weights_out) return MO_OK;
+    return mo_residual_loss_eval(plan, layout, loss, r, r_stride, batch, weights_out, weights_stride, nullptr, stream);
+  }
+  g_err[0] = 0;
+  if (int rc = check_plan(plan)) return rc;
+  if (int rc = check_layout(plan, layout)) return rc;
+  if (int rc = check_loss(layout, loss)) return rc;
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (layout->rows != plan->desc.m_r) return fail(MO_ERR_DIMENSION, "layout has %d rows, plan m_r = %d", layout->rows, plan->desc.m_r);
+  if (!J_blocks || !r) return fail(MO_ERR_INVALID_ARGUMENT, "J_blocks / r is NULL");
+  if (!c_out) return fail(MO_ERR_INVALID_ARGUMENT, "c_out is NULL");
+  if (G_out && G_ld < plan->desc.n) return fail(MO_ERR_DIMENSION, "G_ld %d < n", G_ld);
+  if (weights_out && weights_stride < layout->rows) return fail(MO_ERR_DIMENSION, "weights_stride %lld < rows %d", (long long)weights_stride, layout->rows);
+  const int dtype = plan->desc.dtype;
+  const bool staged = mo::blocks_weighted_stages(layout->values, layout->rows, plan->elem);
+  if (!staged && !weights_out)
+    return fail(MO_ERR_UNSUPPORTED, "the layout (%lld values + 2 x %d rows) does not fit the 48 KiB stage of the fused robust linearise: pass weights_out "
+                "(the weights then go through it: mo_residual_loss_eval, then mo_linearize_blocks_weighted)", layout->values, layout->rows);
+  if (batch == 0) return MO_OK;
+  MO_HIP_CHECK(hipSetDevice(plan->desc.device));
+  mo::BlocksArgs a = blocks_args(layout, batch);
+  a.J = J_blocks; a.J_stride = J_stride; a.r = r; a.r_stride = r_stride;
+  a.lambda = lambda; a.lambda_vec = lambda_vec; a.lambda_vec_stride = lambda_stride;
+  a.G_out = G_out; a.G_out_stride = G_stride; a.G_out_ld = G_ld;
+  a.c_out = c_out; a.c_out_stride = c_stride;
+  if (staged) {
+    blocks_args_loss(&a, loss, dtype);
+    a.half_sq_out = half_sq_out;
+    a.weights_out = weights_out; a.weights_out_stride = weights_stride;
+  } else {
+    mo::LossArgs la = loss_args(loss, dtype, batch);
+    la.r = r; la.r_stride = r_stride; la.weights_out = weights_out; la.weights_stride = weights_stride; la.rho_out = half_sq_out;
+    MO_HIP_CHECK(mo::launch_residual_loss(la, dtype, plan->num_cus, (hipStream_t)stream));
+    a.weights = weights_out; a.weights_stride = weights_stride;
+  }
+  MO_HIP_CHECK(mo::launch_blocks_linearize(a, dtype, plan->num_cus, (hipStream_t)stream));
   return MO_OK;
 }
 

@@ -190,7 +190,28 @@ struct BlocksArgs {
   // mo_linearize_blocks_weighted (behind every older field): one weight per stacked row, NULL = unweighted; g_ent's fourth component is the
   // first stacked row of the entry's block (c_ent.y has it already)
   const void* weights; long long weights_stride;
+  // mo_linearize_blocks_robust (behind every older field): the loss table in the plan's dtype, NULL = none.  The kernel forms the weights
+  // itself (mo_loss_device.h), copies them to weights_out when given and writes 0.5 sum rho to half_sq_out[p * half_sq_stride]
+  const int4* loss_blk;       // [loss_blocks] {first stacked row, R_b, kind, 0}
+  const void* loss_scale;     // [loss_blocks]
+  int loss_blocks;
+  void* weights_out; long long weights_out_stride;
+  long long half_sq_stride;   // read by the loss instantiations only
 };
+// whether the weighted / robust linearise of this layout goes through LDS: (values + 2 rows) elements within the stage budget
+bool blocks_weighted_stages(long long values, int rows, int elem_size);
+
+// mo_residual_loss_eval, residual_loss.hip: per block s_b, w_b = rho'(s_b) over the block's rows, 0.5 sum rho per problem
+struct LossArgs {
+  int num_blocks, rows;
+  long long batch;
+  const int4* blk;            // [num_blocks] {first stacked row, R_b, kind, 0}
+  const void* scale;          // [num_blocks], the plan's dtype
+  const void* r; long long r_stride;
+  void* weights_out; long long weights_stride;   // NULL: not written
+  void* rho_out; long long rho_stride;           // NULL: not written
+};
+hipError_t launch_residual_loss(const LossArgs& a, int dtype, int num_cus, hipStream_t stream);
 hipError_t launch_blocks_linearize(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
 hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, hipStream_t stream);
 

@@ -9,7 +9,7 @@
 // so there are no atomics, no G accumulator and the result is the same on every launch.  The schedule is shared by the batch: it stays in
 // L2 while the workgroups stream their problems' packed J and r (through LDS when they fit) and write whole lines of G.
 // kThreads and grid_for (the grid of the persistent workgroups) are those of every sensitivity kernel: mo_sens_device.h.
-#include "mo_sens_device.h"
+#include "mo_loss_device.h"
 
 namespace mo {
 namespace {
@@ -37,7 +37,10 @@ template <typename T> __device__ __forceinline__ T block_sum(T v, T* red) {
 // kW (mo_linearize_blocks_weighted): row rho of a block counts with its weight, G += w J_a J_b, c += w J_a r, half_sq += w r^2, each as
 // (w J_a) * (.) in the order of the unweighted sums -- with w = 1 the same operations, with w a power of four the bits of the call on
 // (sqrt(w) J, sqrt(w) r).  A row whose weight is exactly 0 is skipped: its J values and r are never multiplied (they may be NaN).
-template <typename T, bool kStaged, bool kW = false>
+// kL (mo_linearize_blocks_robust; staged and kW only): no weights are read.  Once r is staged a lane per block forms s_b, w_b = rho'(s_b) and
+// rho_b (mo_loss_device.h, the code of mo_residual_loss_eval), writes w_b over the block's rows of sW (and of weights_out when given) and the
+// kernel goes on as kW; half_sq_out receives 0.5 sum rho in the order of the stand-alone kernel.
+template <typename T, bool kStaged, bool kW = false, bool kL = false>
 __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const BlocksArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ T red[kThreads / 64];
@@ -51,11 +54,17 @@ __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const Blocks
     const T* gR = (const T*)a.r + p * a.r_stride;
     const T* Jv = gJ;
     const T* rv = gR;
-    const T* wv = kW ? (const T*)a.weights + p * a.weights_stride : nullptr;
+    const T* wv = (kW && !kL) ? (const T*)a.weights + p * a.weights_stride : nullptr;
+    T rho_part = 0;
     if (kStaged) {
       for (long long i = tid; i < a.values; i += kThreads) sJ[i] = gJ[i];
       for (int i = tid; i < a.rows; i += kThreads) sR[i] = gR[i];
-      if (kW) {
+      if (kL) {
+        __syncthreads();  // r is staged
+        rho_part = loss_blocks<T>(a.loss_blk, (const T*)a.loss_scale, a.loss_blocks, sR, sW,
+                                  a.weights_out ? (T*)a.weights_out + p * a.weights_out_stride : nullptr, tid);
+        wv = sW;
+      } else if (kW) {
         for (int i = tid; i < a.rows; i += kThreads) sW[i] = wv[i];
         wv = sW;
       }
@@ -113,7 +122,10 @@ __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const Blocks
     }
     if (a.half_sq_out) {
       T sq = 0;
-      if (kW) {
+      if (kL) {
+        sq = loss_rho_sum(rho_part, red);
+        if (tid == 0) ((T*)a.half_sq_out)[p * a.half_sq_stride] = (T)0.5 * sq;
+      } else if (kW) {
         for (int i = tid; i < a.rows; i += kThreads) {
           const T w = wv[i];
           if (w != (T)0) {
@@ -124,8 +136,10 @@ __global__ __launch_bounds__(kThreads) void blocks_linearize_kernel(const Blocks
       } else {
         for (int i = tid; i < a.rows; i += kThreads) sq += rv[i] * rv[i];
       }
-      sq = block_sum(sq, red);
-      if (tid == 0) ((T*)a.half_sq_out)[p] = (T)0.5 * sq;
+      if (!kL) {
+        sq = block_sum(sq, red);
+        if (tid == 0) ((T*)a.half_sq_out)[p] = (T)0.5 * sq;
+      }
     }
     __syncthreads();  // the next problem overwrites the staged values and the reduction slots
   }
@@ -304,6 +318,12 @@ __global__ __launch_bounds__(kThreads) void blocks_eq_grad_kernel(const BlockGra
 }
 
 template <typename T> hipError_t launch_linearize_t(const BlocksArgs& a, int num_cus, hipStream_t stream) {
+  if (a.loss_blk) {  // the weights are formed in LDS: staged layouts only (mo_linearize_blocks_robust takes the two-launch route otherwise)
+    const size_t stage = (size_t)(a.values + 2 * (long long)a.rows) * sizeof(T);
+    if (stage > kStageBudget) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((blocks_linearize_kernel<T, true, true, true>), dim3(grid_for(a.batch, num_cus, stage)), dim3(kThreads), stage, stream, a);
+    return hipGetLastError();
+  }
   if (a.weights) {  // the weights are staged with the values: rows more elements
     const size_t stage = (size_t)(a.values + 2 * (long long)a.rows) * sizeof(T);
     if (stage <= kStageBudget) {
@@ -356,6 +376,10 @@ hipError_t launch_blocks_jacobian(const BlocksArgs& a, int dtype, int num_cus, h
   if (dtype == MO_F64) hipLaunchKernelGGL(blocks_jacobian_kernel<double>, g, b, 0, stream, a);
   else hipLaunchKernelGGL(blocks_jacobian_kernel<float>, g, b, 0, stream, a);
   return hipGetLastError();
+}
+
+bool blocks_weighted_stages(long long values, int rows, int elem_size) {
+  return (size_t)(values + 2 * (long long)rows) * elem_size <= kStageBudget;
 }
 
 bool blocks_grad_fits(int n, int rows, int elem_size, bool weighted) {

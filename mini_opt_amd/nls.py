@@ -127,13 +127,39 @@ class DeviceFamily:
         return r, J
 
 
+@dataclass(frozen=True)
+class Loss:
+    """A robust loss rho(s) on s = |r|^2 of ONE residual (all its rows) with scale a > 0 (the reference has none; the table:
+    include/mini_opt_hip.h).  Built by Huber / SoftL1 / Cauchy / Tukey below; the solver minimises 0.5 sum_b rho_b(|r_b|^2)."""
+    kind: int
+    scale: float
+
+
+def Huber(a: float) -> Loss:
+    return Loss(L.MO_LOSS_HUBER, float(a))
+
+
+def SoftL1(a: float) -> Loss:
+    return Loss(L.MO_LOSS_SOFT_L1, float(a))
+
+
+def Cauchy(a: float) -> Loss:
+    return Loss(L.MO_LOSS_CAUCHY, float(a))
+
+
+def Tukey(a: float) -> Loss:
+    return Loss(L.MO_LOSS_TUKEY, float(a))
+
+
 @dataclass
 class Residual:
     """mini_opt::Residual as MakeResidual<R, P>(index, functor) builds it (residual.hpp:28-143): `fn(params [B, P], want_J) ->
-    (r [B, R], J [B, R, P] | None)` sees only the residual's own parameters, picked out of the full vector by `index`."""
+    (r [B, R], J [B, R, P] | None)` sees only the residual's own parameters, picked out of the full vector by `index`.
+    loss: a robust Loss on this residual as a cost (None: the plain 0.5 |r|^2); needs ConstrainedNonlinearLeastSquares(residual_blocks=True)."""
     index: Sequence[int]
     fn: ResidualFn
     rows: int
+    loss: Optional[Loss] = None
 
     def Dimension(self) -> int:
         return self.rows
@@ -143,8 +169,8 @@ class Residual:
         return 0.5 * (r * r).sum(dim=1)
 
 
-def MakeResidual(index: Sequence[int], fn: ResidualFn, rows: int) -> Residual:
-    return Residual(tuple(int(i) for i in index), fn, int(rows))
+def MakeResidual(index: Sequence[int], fn: ResidualFn, rows: int, loss: Optional[Loss] = None) -> Residual:
+    return Residual(tuple(int(i) for i in index), fn, int(rows), loss)
 
 
 def stack_residuals(residuals: Sequence[Residual], n: int) -> ResidualFn:
@@ -247,13 +273,22 @@ class ConstrainedNonlinearLeastSquares:
         self.variables_ = z(B, n)
         self.candidate_vars_ = z(B, n)
         self.residual_blocks = bool(residual_blocks)
-        self._cost_layout = self._eq_layout = None
+        self._cost_layout = self._eq_layout = self._cost_loss = None
+        if any(res.loss is not None for res in (problem.equality_residuals or ())):
+            raise L.MiniOptError(-1, "a loss on an equality residual: equality residuals take no loss")
+        has_loss = any(res.loss is not None for res in (problem.cost_residuals or ()))
+        if has_loss and not self.residual_blocks:
+            raise L.MiniOptError(-1, "a cost residual has a loss: robust losses need residual_blocks=True")
         if self.residual_blocks:
             if problem.cost_residuals is None or (k and problem.equality_residuals is None):
                 raise L.MiniOptError(-1, "residual_blocks needs a Problem built by Problem.FromResiduals")
             from .qp import create_layout
             self._cost_layout = create_layout(self._plan.h, [(res.index, res.rows) for res in problem.cost_residuals])
             self._eq_layout = create_layout(self._plan.h, [(res.index, res.rows) for res in problem.equality_residuals]) if k else None
+            if has_loss:   # with no loss anywhere no table is built: the solver makes the calls it made before losses existed
+                from .qp import create_loss
+                self._cost_loss = create_loss(self._cost_layout, [(res.loss.kind, res.loss.scale) if res.loss is not None
+                                                                  else (L.MO_LOSS_TRIVIAL, 1.0) for res in problem.cost_residuals])
             self._vals = int(L.lib().mo_residual_layout_values(self._cost_layout))
             self._vals_eq = int(L.lib().mo_residual_layout_values(self._eq_layout)) if k else 0
             self.J, self.r, self.r_cand = z(B, self._vals), z(B, m_r), z(B, m_r)            # J: packed blocks
@@ -337,6 +372,8 @@ class ConstrainedNonlinearLeastSquares:
 
     def __del__(self):
         try:
+            if self._cost_loss is not None:
+                L.lib().mo_residual_loss_destroy(self._cost_loss)
             for h in (self._cost_layout, self._eq_layout):
                 if h is not None:
                     L.lib().mo_residual_layout_destroy(h)
@@ -397,7 +434,10 @@ class ConstrainedNonlinearLeastSquares:
         null_path = bool(L.lib().mo_plan_nls_uses_nullspace(self._plan.h))   # the C side's own predicate (shape AND kernel capacity)
         self._outputs_view = NLSSolverOutputs(term, nit, its, status, qp_its, qp_lag, qp_eig, null_path)
         cb = L.NLS_EVAL_FN(self._eval)
-        if self.residual_blocks:
+        if self._cost_loss is not None:
+            rc = L.lib().mo_nls_solve_blocks_robust(self._plan.h, C.byref(prob), self._cost_layout, self._cost_loss, self._eq_layout, B,
+                                                    C.byref(sp), cb, None, _ptr(term), _ptr(nit), _ptr(its), _ptr(status), _stream())
+        elif self.residual_blocks:
             rc = L.lib().mo_nls_solve_blocks(self._plan.h, C.byref(prob), self._cost_layout, self._eq_layout, B, C.byref(sp), cb, None,
                                              _ptr(term), _ptr(nit), _ptr(its), _ptr(status), _stream())
         else:
@@ -412,10 +452,29 @@ class ConstrainedNonlinearLeastSquares:
         return self.variables_
 
     def EvaluateNonlinearErrors(self, vars_: torch.Tensor) -> torch.Tensor:
-        """nonlinear.cc:279-293: [B, 2] = {f, equality}."""
+        """nonlinear.cc:279-293: [B, 2] = {f, equality}; with losses f is the robust cost 0.5 sum_b rho_b(|r_b|^2)."""
         r, _ = self.p_.cost(vars_, False)
         r_eq = self.p_.equality(vars_, False)[0] if self.k else None
-        return nonlinear_errors(self._plan, r.contiguous(), None if r_eq is None else r_eq.contiguous())
+        out = nonlinear_errors(self._plan, r.contiguous(), None if r_eq is None else r_eq.contiguous())
+        if self._cost_loss is not None:
+            out[:, 0] = self._loss_eval(r.contiguous(), want_weights=False)[1]
+        return out
+
+    def _loss_eval(self, r: torch.Tensor, want_weights: bool):
+        B = int(r.shape[0])
+        w = torch.empty(B, self.m_r, dtype=r.dtype, device=r.device) if want_weights else None
+        f = torch.empty(B, dtype=r.dtype, device=r.device)
+        L.check(L.lib().mo_residual_loss_eval(self._plan.h, self._cost_layout, self._cost_loss, _ptr(r), self.m_r, B, _ptr(w), self.m_r,
+                                              _ptr(f), _stream()))
+        return w, f
+
+    def LossWeights(self) -> torch.Tensor:
+        """[B, m_r]: the weight rho_b'(|r_b|^2) of every stacked cost row at the current variables (1 everywhere without losses): small
+        weights mark the residuals the fit treats as outliers."""
+        r, _ = self.p_.cost(self.variables_, False)
+        if self._cost_loss is None:
+            return torch.ones_like(r)
+        return self._loss_eval(r.contiguous(), want_weights=True)[0]
 
 
 # ---- the static pieces, usable on their own ----------------------------------------------------------------------

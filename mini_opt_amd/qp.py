@@ -453,6 +453,51 @@ def create_layout(plan, blocks) -> C.c_void_p:
     return h
 
 
+TRIVIAL, HUBER, SOFT_L1, CAUCHY, TUKEY = range(5)   # mo_loss_kind
+
+
+def create_loss(layout_handle, losses) -> C.c_void_p:
+    """mo_residual_loss_create for a layout handle and [(kind, scale), ...], one per block; the caller destroys the handle."""
+    kinds = (C.c_int32 * max(len(losses), 1))(*[int(k) for k, _ in losses])
+    scales = (C.c_double * max(len(losses), 1))(*[float(a) for _, a in losses])
+    h = C.c_void_p()
+    L.check(L.lib().mo_residual_loss_create(layout_handle, kinds, scales, C.byref(h)))
+    return h
+
+
+class ResidualLoss:
+    """A robust-loss table (mo_residual_loss) for the blocks of `layout`: losses = [(kind, scale), ...], one per block, kind one of TRIVIAL,
+    HUBER, SOFT_L1, CAUCHY, TUKEY (rho(s) with s = |r_b|^2; the table: include/mini_opt_hip.h).  Serves fp64 and fp32 layouts of the same
+    blocks on the same device."""
+
+    def __init__(self, layout: ResidualLayout, losses):
+        self.h = None
+        self.losses = [(int(k), float(a)) for k, a in losses]
+        if len(self.losses) != len(layout.blocks):
+            raise L.MiniOptError(-2, f"{len(self.losses)} losses for a layout of {len(layout.blocks)} blocks")
+        self.layout = layout
+        self.h = create_loss(layout.h, self.losses)
+
+    def __del__(self):
+        try:
+            if self.h is not None:
+                L.lib().mo_residual_loss_destroy(self.h)
+        except Exception:
+            pass
+
+
+def loss_weights(layout: ResidualLayout, loss: ResidualLoss, r: torch.Tensor):
+    """mo_residual_loss_eval: (weights [B, rows], rho [B]) for r [B, rows] -- w_b = rho_b'(|r_b|^2) repeated over the block's rows (the
+    `weights` of linearize_blocks and solve_qp) and 0.5 sum_b rho_b(|r_b|^2)."""
+    if r.dim() != 2 or int(r.shape[1]) != layout.rows or not r.is_contiguous() or r.dtype != layout.dtype or r.device != layout.device:
+        raise ValueError(f"expected a contiguous [B, {layout.rows}] {layout.dtype} tensor on {layout.device}, got {tuple(r.shape)} {r.dtype}")
+    B = int(r.shape[0])
+    w = torch.empty(B, layout.rows, dtype=layout.dtype, device=layout.device)
+    f = torch.empty(B, dtype=layout.dtype, device=layout.device)
+    L.check(L.lib().mo_residual_loss_eval(layout._plan, layout.h, loss.h, _ptr(r), layout.rows, B, _ptr(w), layout.rows, _ptr(f), _stream()))
+    return w, f
+
+
 def _check_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor):
     for t, w in ((J_blocks, layout.values), (r, layout.rows)):
         if t.dim() != 2 or int(t.shape[1]) != w or not t.is_contiguous() or t.dtype != layout.dtype or t.device != layout.device:
@@ -462,13 +507,21 @@ def _check_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tenso
 
 
 def linearize_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Tensor, lam: float = 0.0, lam_vec: Optional[torch.Tensor] = None,
-                     want_G: bool = True, batch: Optional[int] = None, weights: Optional[torch.Tensor] = None):
+                     want_G: bool = True, batch: Optional[int] = None, weights: Optional[torch.Tensor] = None,
+                     loss: Optional["ResidualLoss"] = None, return_weights: bool = False):
     """Cost part of LinearizeAndFillQP (nonlinear.cc:182-189) from packed residual blocks: sum_b UpdateHessian (residual.hpp:186-226) +
     lambda I.  Returns (G [B,n,n] col-major lower, strict upper 0; c [B,n]; sum_b 0.5 |r_b|^2 [B]).  J_blocks / r / lam_vec with a leading
     dimension of 1 are read with stride 0; B is the largest leading dimension (or `batch`, if that is larger).  want_G=False: G is not
     formed (returned as None); c has the bits of the full call.  weights [B or 1, rows]: one weight per stacked residual row
     (mo_linearize_blocks_weighted): G = sum_b J_b^T W_b J_b by the same pair rule, c = sum_b J_b^T W_b r_b, the third result 0.5 sum w r^2; a
-    row whose weight is exactly 0 is never read into the arithmetic (its J values and r may be NaN)."""
+    row whose weight is exactly 0 is never read into the arithmetic (its J values and r may be NaN).
+    loss (a ResidualLoss; not together with weights): the robust cost, mo_linearize_blocks_robust -- the weights are rho_b'(|r_b|^2), formed
+    inside the kernel; the third result is 0.5 sum_b rho_b.  return_weights=True appends the weights the kernel used ([B, rows]) to the
+    results; a layout too large for the kernel's LDS stage needs it (the weights then go through that tensor)."""
+    if loss is not None and weights is not None:
+        raise ValueError("weights and loss cannot be combined")
+    if return_weights and loss is None:
+        raise ValueError("return_weights needs a loss")
     B, js, rs = _check_blocks(layout, J_blocks, r)
     ws = 0
     if weights is not None:
@@ -492,6 +545,11 @@ def linearize_blocks(layout: ResidualLayout, J_blocks: torch.Tensor, r: torch.Te
     G = torch.empty(B, n, n, dtype=layout.dtype, device=layout.device) if want_G else None
     c = torch.empty(B, n, dtype=layout.dtype, device=layout.device)
     f = torch.empty(B, dtype=layout.dtype, device=layout.device)
+    if loss is not None:
+        w = torch.empty(B, layout.rows, dtype=layout.dtype, device=layout.device) if return_weights else None
+        L.check(L.lib().mo_linearize_blocks_robust(layout._plan, layout.h, _ptr(J_blocks), js, _ptr(r), rs, float(lam), _ptr(lam_vec), ls, B,
+                                                   _ptr(G), n * n, n, _ptr(c), n, _ptr(f), loss.h, _ptr(w), layout.rows, _stream()))
+        return (G, c, f, w) if return_weights else (G, c, f)
     if weights is not None:
         L.check(L.lib().mo_linearize_blocks_weighted(layout._plan, layout.h, _ptr(J_blocks), js, _ptr(r), rs, _ptr(weights), ws, float(lam),
                                                      _ptr(lam_vec), ls, B, _ptr(G), n * n, n, _ptr(c), n, _ptr(f), _stream()))

@@ -246,6 +246,31 @@ typedef enum { MO_NULLSPACE_SUCCESS = 0, MO_NULLSPACE_NOT_POSITIVE_DEFINITE = 1 
 int mo_nullspace_solve(mo_plan* plan, const mo_problem* prob, int64_t batch, void* x_out, int64_t x_stride,
                        int32_t* termination, void* stream);
 
+/* Parameter covariance of an (equality-constrained) least-squares fit.  With S = sym(G) read from the LOWER triangle only (the strict upper
+ * triangle is never read), A = A_eq (k x n, k <= n; k = 0: absent) and Z an orthonormal basis of null(A):
+ *   C = scale_p Z (Z^T S Z)^-1 Z^T          (k = 0: C = scale_p S^-1)
+ * the top-left n x n block of the inverse of [[S, A^T], [A, 0]]: the covariance of the equality-constrained least-squares estimator with
+ * G = sum w J^T J.  C depends on S and null(A) alone; what decides success is the reduced Hessian: a singular or indefinite G that is positive
+ * definite on null(A) succeeds.  The rank of A follows mo_nullspace_solve (Eigen's threshold on the pivoted QR): a duplicated or zero row
+ * lowers the rank and does not fail the problem; rank n gives C = 0 exactly (every entry +0) with MO_STATUS_OK.  Inequality constraints are
+ * not part of this (the plan's m is ignored, as in mo_nullspace_solve): a caller who wants an active bound pinned passes it as an equality row.
+ * Input: (G, A_eq) only -- prob->J != NULL is MO_ERR_INVALID_ARGUMENT (linearise first); c, b_eq, cons_* and lambda* are ignored; G_stride = 0
+ * / A_stride = 0 share one instance among the batch.
+ *   sel      device, [q], shared by the batch: the variables wanted, unsorted and repeated indices allowed; NULL = all n (q must be n).  An
+ *            index outside [0, n) gives MO_STATUS_BAD_INDEX for EVERY problem and NaN outputs.
+ *   scale    per-problem factor in the plan's dtype, NULL = 1; scale_stride 0 = one value for the batch
+ *   cov_out  [batch] q x q column-major, leading dimension cov_ld >= q, BOTH triangles written, symmetric to the bit; may be NULL
+ *   var_out  [batch][q] the diagonal (the bits of cov_out's diagonal); may be NULL (not both)
+ *   status   [batch] MO_STATUS_OK; MO_STATUS_NOT_POSITIVE_DEFINITE iff a pivot of the reduced LLT is <= 0; MO_STATUS_NONFINITE iff an entry
+ *            that is read or a result is not finite.  Every output of a failed problem is NaN; no other problem is affected.  May be NULL.
+ * Padding (cov_ld > q, strides beyond the payload) is never written.  No absolute thresholds: 4 G gives C / 4 and a power-of-two scale scales
+ * the result, bit for bit (short of over- / underflow).  Two launches give the same bits.  No allocation, no host synchronisation.
+ * Limits: one workgroup per problem with G and A_eq^T in LDS, ((n | 1) (n + k) + 2 n + 2 k) scalars + 4 (q + 8) bytes <= 160 KiB
+ * (fp64: n = 128, k = 16, q = n fits; n + k <= 112 always does); beyond: MO_ERR_UNSUPPORTED before any launch. */
+int mo_qp_covariance(mo_plan* plan, const mo_problem* prob, int64_t batch, const int32_t* sel, int32_t q, const void* scale,
+                     int64_t scale_stride, void* cov_out, int64_t cov_stride, int32_t cov_ld, void* var_out, int64_t var_stride,
+                     int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * Batched constrained nonlinear least squares: ConstrainedNonlinearLeastSquares::Solve (nonlinear.cc:75-158) for a batch of
  * independent problems of one shape, every problem with its own lambda / penalty / optimizer state, in lock step.

@@ -15,7 +15,8 @@ _DIFF_EXPORTS = ("solve_qp", "kkt_solve", "qp_gradients", "qp_gradients_shared",
                  "qp_jvp_blocks_weighted", "QPSolveWeightedBlocksFunction", "qp_gradients_blocks_weighted_shared")
 
 
-_QP_EXPORTS = ("ResidualLayout", "ResidualLoss", "loss_weights", "linearize_blocks")   # residual-block input and its robust losses
+_QP_EXPORTS = ("ResidualLayout", "ResidualLoss", "loss_weights", "linearize_blocks",   # residual-block input and its robust losses
+                "covariance")                                                         # parameter covariance of a fit
 
 
 def __getattr__(name):  # the differentiable front end needs torch: imported on first use, like qp

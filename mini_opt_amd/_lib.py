@@ -42,7 +42,7 @@ EXPORTS = ["mo_version_string", "mo_status_string", "mo_last_error", "mo_default
            "mo_linearize_blocks_weighted", "mo_qp_gradients_blocks_weighted", "mo_qp_tangent_rhs_blocks_weighted",
            "mo_qp_gradients_blocks_weighted_shared_workspace", "mo_qp_gradients_blocks_weighted_shared",
            "mo_residual_loss_create", "mo_residual_loss_destroy", "mo_residual_loss_eval", "mo_linearize_blocks_robust",
-           "mo_nls_solve_blocks_robust"]
+           "mo_nls_solve_blocks_robust", "mo_qp_covariance"]
 
 
 class PlanDesc(C.Structure):
@@ -216,6 +216,7 @@ def lib() -> C.CDLL:
     L.mo_nullspace_solve.argtypes = [vp, C.POINTER(Problem), i64, vp, i64, vp, vp]
     L.mo_residual_eval.argtypes = [vp, i32, i32, vp, vp, i64, i64, vp, i64, vp, i64, i32, i32, vp]
     L.mo_qp_eigenvalue_stats.argtypes = [vp, C.POINTER(Problem), i64, vp, vp]
+    L.mo_qp_covariance.argtypes = [vp, C.POINTER(Problem), i64, vp, i32, vp, i64, vp, i64, i32, vp, i64, vp, vp]
     L.mo_default_nls_params.argtypes = [C.POINTER(NlsParams)]
     L.mo_default_nls_params.restype = None
     L.mo_nls_solve.argtypes = [vp, C.POINTER(NlsProblem), i64, C.POINTER(NlsParams), NLS_EVAL_FN, vp, vp, vp, vp, vp, vp]

@@ -802,6 +802,46 @@ int mo_nullspace_solve(mo_plan* plan, const mo_problem* prob, int64_t batch, voi
   return MO_OK;
 }
 
+int mo_qp_covariance(mo_plan* plan, const mo_problem* prob, int64_t batch, const int32_t* sel, int32_t q, const void* scale,
+                     int64_t scale_stride, void* cov_out, int64_t cov_stride, int32_t cov_ld, void* var_out, int64_t var_stride,
+                     int32_t* status, void* stream) {
+  g_err[0] = 0;
+  // (what can be judged from the arguments alone comes first)
+  if (!cov_out && !var_out) return fail(MO_ERR_INVALID_ARGUMENT, "cov_out and var_out are both NULL");
+  if (!prob) return fail(MO_ERR_INVALID_ARGUMENT, "Must pass a non-null problem");
+  if (prob->J) return fail(MO_ERR_INVALID_ARGUMENT, "J given: mo_qp_covariance takes (G, A_eq) input only (linearise first)");
+  if (batch < 0) return fail(MO_ERR_INVALID_ARGUMENT, "batch must be >= 0");
+  if (q < 1) return fail(MO_ERR_INVALID_ARGUMENT, "q = %d: at least one variable must be selected", q);
+  if (cov_out && cov_ld < q) return fail(MO_ERR_DIMENSION, "cov_ld %d < q %d", cov_ld, q);
+  if (int rc = check_plan(plan)) return rc;
+  const mo_plan_desc& d = plan->desc;
+  if (!sel && q != d.n) return fail(MO_ERR_INVALID_ARGUMENT, "sel is NULL but q = %d is not n = %d", q, d.n);
+  if (d.k > d.n) return fail(MO_ERR_DIMENSION, "k = %d equality rows for n = %d variables", d.k, d.n);
+  if (!prob->G) return fail(MO_ERR_INVALID_ARGUMENT, "G is NULL");
+  if (prob->G_ld < d.n) return fail(MO_ERR_DIMENSION, "G must be square: G_ld %d < n %d", prob->G_ld, d.n);
+  if (d.k > 0) {
+    if (!prob->A_eq) return fail(MO_ERR_DIMENSION, "k = %d but A_eq is NULL", d.k);
+    if (prob->A_ld < d.k) return fail(MO_ERR_DIMENSION, "A_ld %d < k %d", prob->A_ld, d.k);
+  }
+  const size_t need = mo::qp_covariance_lds_bytes(d.n, d.k, q, plan->elem);
+  if (need > mo::kLdsBytes)
+    return fail(MO_ERR_UNSUPPORTED, "the covariance kernel keeps G and A_eq^T in LDS: n = %d, k = %d, q = %d need %zu B (> 160 KiB)", d.n, d.k, q, need);
+  if (batch == 0) return MO_OK;
+  mo::CovArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = d.n; a.k = d.k; a.q = q; a.batch = batch;
+  a.G = prob->G; a.G_stride = prob->G_stride; a.G_ld = prob->G_ld;
+  if (d.k > 0) { a.A = prob->A_eq; a.A_stride = prob->A_stride; a.A_ld = prob->A_ld; }
+  a.sel = sel;
+  a.scale = scale; a.scale_stride = scale_stride;
+  a.cov = cov_out; a.cov_stride = cov_stride; a.cov_ld = cov_ld;
+  a.var = var_out; a.var_stride = var_stride;
+  a.status = status;
+  MO_HIP_CHECK(hipSetDevice(d.device));
+  MO_HIP_CHECK(mo::launch_qp_covariance(a, d.dtype, plan->num_cus, (hipStream_t)stream));
+  return MO_OK;
+}
+
 void mo_default_nls_params(mo_nls_params* p) {
   if (!p) return;
   memset(p, 0, sizeof(*p));

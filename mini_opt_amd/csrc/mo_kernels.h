@@ -87,6 +87,23 @@ int generic_large_grid(const KernelArgs& a, int elem_size, int num_cus);
 hipError_t launch_nullspace(const KernelArgs& a, int dtype, int num_cus, hipStream_t stream);
 size_t nullspace_lds_bytes(int n, int k, int m_r, int elem_size);
 
+// mo_qp_covariance, qp_covariance.hip: C = scale Z (Z^T sym(G) Z)^-1 Z^T per problem, gathered by `sel`.  The same factorisation as the
+// null-space solver carried one step further (triangular inverse, symmetric product, back-transform), in place in the LDS copy of G.
+struct CovArgs {
+  int n, k, q;
+  long long batch;
+  const void* G; long long G_stride; int G_ld;
+  const void* A; long long A_stride; int A_ld;
+  const int* sel;                                  // [q] shared by the batch, NULL: the identity (q = n)
+  const void* scale; long long scale_stride;       // NULL: 1
+  void* cov; long long cov_stride; int cov_ld;     // NULL: not written
+  void* var; long long var_stride;                 // NULL: not written
+  int* status;                                     // NULL: not written
+};
+size_t qp_covariance_lds_bytes(int n, int k, int q, int elem_size);
+int qp_covariance_grid(int n, int k, int q, int elem_size, int num_cus);   // workgroups of the persistent grid before the clamp to the batch
+hipError_t launch_qp_covariance(const CovArgs& a, int dtype, int num_cus, hipStream_t stream);
+
 // QP::ComputeEigenvalueStats (qp.cc:12-16): {min, max, min |.|} of the eigenvalues of sym(G) per problem, eig_kernels.hip.  `work`: the plan's
 // global workspace (one slot of work_slot_bytes per workgroup) for matrices beyond the LDS; out [batch][3] in the plan's dtype.
 bool eig_needs_global(int n);

@@ -476,6 +476,71 @@ class ConstrainedNonlinearLeastSquares:
             return torch.ones_like(r)
         return self._loss_eval(r.contiguous(), want_weights=True)[0]
 
+    def Covariance(self, select=None, scale=None):
+        """The covariance of the fitted parameters at the current variables(): (cov [B, q, q], status [B]), mo_qp_covariance on the
+        problem re-linearised there with lambda = 0 (the damping is a device of the algorithm, not part of the model):
+            C = scale Z (Z^T G Z)^-1 Z^T,   G = sum_b w_b J_b^T J_b,   Z a basis of null(J_eq)
+        -- dense input through mo_linearize, residual blocks through mo_linearize_blocks, losses through mo_linearize_blocks_robust
+        (w_b = rho_b', the Gauss-Newton form without the Triggs term), the equality Jacobian through mo_jacobian_blocks or the dense J_eq.
+        Inequality constraints are not part of it: model an active bound that is to be pinned as an equality residual.
+        select: the variables wanted (None: all).  scale: None, a [B] tensor, or "residual" = 2 f / (m_r - n + k) with f the (robust) cost
+        at the solution, the usual estimate of the residual variance; raises when m_r - n + k <= 0.
+        status: MO_STATUS_OK, NOT_POSITIVE_DEFINITE (the reduced Hessian has a pivot <= 0), NONFINITE; cov of a failed problem is NaN."""
+        lib = L.lib()
+        B, n, k, m_r = self.batch, self.n, self.k, self.m_r
+        dev, dt = self.variables_.device, self.variables_.dtype
+        if isinstance(scale, str):
+            if scale != "residual":
+                raise ValueError(f"scale = {scale!r}: expected None, a tensor [B] or \"residual\"")
+            if m_r - n + k <= 0:
+                raise ValueError(f"scale = \"residual\" needs m_r - n + k > 0 degrees of freedom (m_r = {m_r}, n = {n}, k = {k})")
+        self._callback_error = None
+        if self._eval(None, L.MO_NLS_EVAL_LINEARIZE, None):          # J, r (and J_eq) at variables()
+            raise self._callback_error
+        G = torch.empty(B, n, n, dtype=dt, device=dev)
+        c = torch.empty(B, n, dtype=dt, device=dev)
+        f = torch.empty(B, dtype=dt, device=dev)
+        A = self.J_eq
+        if self.residual_blocks:
+            if self._cost_loss is not None:
+                w = torch.empty(B, m_r, dtype=dt, device=dev)
+                L.check(lib.mo_linearize_blocks_robust(self._plan.h, self._cost_layout, _ptr(self.J), self._vals, _ptr(self.r), m_r, 0.0, None, 0,
+                                                       B, _ptr(G), n * n, n, _ptr(c), n, _ptr(f), self._cost_loss, _ptr(w), m_r, _stream()))
+            else:
+                L.check(lib.mo_linearize_blocks(self._plan.h, self._cost_layout, _ptr(self.J), self._vals, _ptr(self.r), m_r, 0.0, None, 0, B,
+                                                _ptr(G), n * n, n, _ptr(c), n, _ptr(f), _stream()))
+            if k:
+                A = torch.empty(B, n, k, dtype=dt, device=dev)
+                s = torch.empty(B, dtype=dt, device=dev)
+                L.check(lib.mo_jacobian_blocks(self._plan.h, self._eq_layout, _ptr(self.J_eq), self._vals_eq, _ptr(self.r_eq), k, B, _ptr(A),
+                                               k * n, k, L.MO_COL_MAJOR, _ptr(s), _stream()))
+        else:
+            lin = L.Problem()
+            lin.J, lin.J_stride, lin.J_ld, lin.J_layout = _ptr(self.J), m_r * n, n, L.MO_ROW_MAJOR
+            lin.r, lin.r_stride, lin.lam = _ptr(self.r), m_r, 0.0
+            L.check(lib.mo_linearize(self._plan.h, C.byref(lin), B, _ptr(G), n * n, n, _ptr(c), n, _ptr(f), _stream()))
+        scale_t = None
+        if isinstance(scale, str):
+            scale_t = f * (2.0 / (m_r - n + k))
+        elif scale is not None:
+            scale_t = scale
+            if not isinstance(scale_t, torch.Tensor) or tuple(scale_t.shape) != (B,) or scale_t.dtype != dt or scale_t.device != dev:
+                raise ValueError(f"scale: expected None, \"residual\" or a [{B}] {dt} tensor on {dev}")
+            scale_t = scale_t.contiguous()
+        sel_t, q = None, n
+        if select is not None:
+            sel_t = torch.as_tensor(select).to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+            q = int(sel_t.numel())
+        prob = L.Problem()
+        prob.G, prob.G_stride, prob.G_ld = _ptr(G), n * n, n
+        if k:
+            prob.A_eq, prob.A_stride, prob.A_ld = _ptr(A), n * k, k
+        cov = torch.empty(B, q, q, dtype=dt, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        L.check(lib.mo_qp_covariance(self._plan.h, C.byref(prob), B, _ptr(sel_t), q, _ptr(scale_t), 1, _ptr(cov), q * q, q, None, 0,
+                                     _ptr(status), _stream()))
+        return cov, status
+
 
 # ---- the static pieces, usable on their own ----------------------------------------------------------------------
 def nonlinear_errors(plan: _Plan, r: torch.Tensor, r_eq: Optional[torch.Tensor]) -> torch.Tensor:

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -372,6 +372,68 @@ def eigenvalue_stats(problem: BatchedQP) -> torch.Tensor:
         return out
     finally:
         lib.mo_plan_destroy(plan)
+
+
+class Covariance(NamedTuple):
+    """Result of covariance(): cov [B, q, q] or None, var [B, q] or None, status [B] int32 (MO_STATUS_*)."""
+    cov: Optional[torch.Tensor]
+    var: Optional[torch.Tensor]
+    status: torch.Tensor
+
+
+def covariance(G: torch.Tensor, A_eq: Optional[torch.Tensor] = None, select=None, scale=None, full: bool = True, diag: bool = False) -> Covariance:
+    """Parameter covariance of a fit (mo_qp_covariance): C = scale Z (Z^T S Z)^-1 Z^T per problem, with S = sym(G) from the lower triangle
+    and Z an orthonormal basis of null(A_eq) (no A_eq: C = scale S^-1) -- the top-left block of the inverse of [[S, A^T], [A, 0]].
+
+    G [B or 1, n, n] in BatchedQP's convention (column-major, lower triangle read), A_eq [B or 1, n, k] as BatchedQP.A_eq.  select: the
+    variables wanted (a sequence or int tensor, unsorted and repeated indices allowed; None = all n).  scale: None, a number or a [B] tensor.
+    full / diag choose the outputs: cov [B, q, q] (symmetric to the bit) and var [B, q] (the bits of its diagonal).  status [B]:
+    MO_STATUS_OK, NOT_POSITIVE_DEFINITE (the reduced Hessian has a pivot <= 0), NONFINITE or BAD_INDEX; the outputs of a failed problem are
+    NaN.  A singular G that is positive definite on null(A_eq) succeeds; a rank-deficient A_eq lowers the rank and does not fail.
+    Inequality constraints are not part of this: pass an active bound that is to be pinned as an equality row."""
+    if not (full or diag):
+        raise ValueError("nothing asked for: full and diag are both False")
+    if G.dim() != 3 or G.shape[1] != G.shape[2] or not G.is_cuda or not G.is_contiguous() or G.dtype not in _DT:
+        raise ValueError(f"G: expected a contiguous [B or 1, n, n] float tensor on a GPU, got {tuple(G.shape)} {G.dtype}")
+    n, dev, dt = int(G.shape[1]), G.device, G.dtype
+    k = 0
+    B = int(G.shape[0])
+    if A_eq is not None:
+        if A_eq.dim() != 3 or int(A_eq.shape[1]) != n or A_eq.device != dev or A_eq.dtype != dt or not A_eq.is_contiguous():
+            raise ValueError(f"A_eq: expected a contiguous [B or 1, {n}, k] {dt} tensor on {dev}, got {tuple(A_eq.shape)} {A_eq.dtype}")
+        k = int(A_eq.shape[2])
+        B = max(B, int(A_eq.shape[0]))
+    scale_t, scale_stride = None, 0
+    if scale is not None:
+        scale_t = scale if isinstance(scale, torch.Tensor) else torch.full((1,), float(scale), dtype=dt, device=dev)
+        if scale_t.dim() != 1 or scale_t.dtype != dt or scale_t.device != dev or not scale_t.is_contiguous():
+            raise ValueError(f"scale: expected a number or a contiguous [B] {dt} tensor on {dev}")
+        B = max(B, int(scale_t.shape[0]))
+        scale_stride = 0 if scale_t.shape[0] == 1 else 1
+    for t in (G, A_eq, scale_t):
+        if t is not None and int(t.shape[0]) not in (1, B):
+            raise ValueError(f"leading dimension {int(t.shape[0])}: expected {B} or 1")
+    sel_t, q = None, n
+    if select is not None:
+        sel_t = torch.as_tensor(select).to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+        q = int(sel_t.numel())
+    lib = L.lib()
+    desc = L.PlanDesc(n, k, 0, 0, _DT[dt], dev.index or 0, L.EXTRA_PLAN_FLAGS, 0, B)
+    plan = C.c_void_p()
+    L.check(lib.mo_plan_create(C.byref(desc), C.byref(plan)))
+    try:
+        prob = L.Problem()
+        prob.G, prob.G_stride, prob.G_ld = _ptr(G), (0 if G.shape[0] == 1 else n * n), n
+        if k > 0:
+            prob.A_eq, prob.A_stride, prob.A_ld = _ptr(A_eq), (0 if A_eq.shape[0] == 1 else n * k), k
+        cov = torch.empty(B, q, q, dtype=dt, device=dev) if full else None
+        var = torch.empty(B, q, dtype=dt, device=dev) if diag else None
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        L.check(lib.mo_qp_covariance(plan, C.byref(prob), B, _ptr(sel_t), q, _ptr(scale_t), scale_stride, _ptr(cov), q * q, q, _ptr(var), q,
+                                     _ptr(status), _stream()))
+    finally:
+        lib.mo_plan_destroy(plan)
+    return Covariance(cov, var, status)
 
 
 def linearize(problem: BatchedQP, force_generic: bool = False):
